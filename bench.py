@@ -24,7 +24,9 @@ is given without a rendezvous in the environment — re-launched by this script 
 builds the weights and RCCL-broadcasts the two weight arenas; there is no collective inside the step loop.
 
 Prints ONE JSON line (rank 0) with the contract's fields plus `roofline` (dominant kernel; per-launch HIP
-event timing) and, at N=1, `cpu_baseline`.
+event timing) and, at N=1, `cpu_baseline`.  `ms_per_step` is the wall time of one timed step.  With `--dump-outputs DIR`
+it also writes what the last timed step computed on rank 0 as DIR/<field>.npy: the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -249,6 +251,57 @@ class ClockSampler:
                     source=f"{self.path}, current level every {self.period}s over the timed region")
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: payload cap, leaving room under 64 MB for the .npy headers
+
+
+def gather_outputs(results):
+    """What a caller of the timed path receives for the images of one step: every array or number of the per-image
+    results (dicts of fields, or one tensor = "image"), on the host, gathered over the images per field — stacked on a
+    leading image axis, or flattened and concatenated where the images' shapes differ (layouts with different box
+    counts).  Fields without numeric content (None with --no-decode, empty lists) are left out."""
+    import numpy as np
+    import torch
+
+    def gather(parts):
+        parts = [p for p in parts if p is not None]
+        if not parts:
+            return None
+        if len({p.shape for p in parts}) == 1:
+            return np.stack(parts)
+        return np.concatenate([p.reshape(-1) for p in parts])
+
+    def host(v):
+        if isinstance(v, (list, tuple)):
+            return gather([host(x) for x in v])
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v) if v is not None else None
+        return a if a is not None and a.dtype.kind in "biuf" else None
+
+    results = [r if isinstance(r, dict) else dict(image=r) for r in results]
+    out = {k: gather([host(r[k]) for r in results]) for k in results[0]}
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float64 where the data is float64 and float32 otherwise, so that
+    two builds can be compared output for output.  Past DUMP_BYTES in all, the largest arrays are written as a fixed,
+    seeded sample of their flattened elements (ascending indices: the same for every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].size * kv[1].dtype.itemsize, kv[0]))
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = budget // (len(items) - i)                  # the smaller arrays leave their unused share to the larger
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        budget -= a.nbytes
+        print(f"[dump] {name}: {list(arrays[name].shape)} -> {list(a.shape)} {a.dtype}", file=sys.stderr)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -327,6 +380,8 @@ def main_sdxl(args):
     if rank != 0:
         return
     assert all(bool(torch.isfinite(o).all()) for o in outs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gather_outputs(outs))
     n_images = args.steps * n_img * world
     n_run = T - lanes[0].sampler.scheduler.img2img_start(T, ratio)
     # algorithmic work and the dominant kernel: ONE image eagerly (no graph) on lane 0 with HIP events around every launch
@@ -443,7 +498,14 @@ def main():
                          "rank pinning, weight broadcast, barrier and gather code path of an N-GPU run, rehearsed on one GPU")
     ap.add_argument("--cpu-dryrun", action="store_true",
                     help="rendezvous / weight broadcast / partition / timing collectives on CPU (gloo), no GPU work")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed on rank 0 (every array and "
+                         "number of the per-image results, per field) as DIR/<field>.npy; at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.cpu_dryrun:
+        ap.error("--dump-outputs needs the GPU path (no outputs are computed with --cpu-dryrun)")
 
     if (args.gpus > 1 or args.spawn) and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn(args.gpus))
@@ -491,7 +553,7 @@ def main():
         if rank == 0:
             ws.load_state_dict(weights.synth_state_dict(cfg, 0))
         bcast_s = ldist.broadcast_weights(ws, src=0, chunk_bytes=8 << 20)
-        ldist.barrier()
+        ldist.sum_over_ranks(0.0)     # the barrier, as a CPU all-reduce: gloo's own barrier initialises the HIP runtime
         t0 = time.perf_counter()
         # the rank's lanes as host threads: the same hand-out as the GPU path (whole steps, or one cost-balanced share
         # of the rank's layouts per lane), each job "running" for a time proportional to its algorithmic cost
@@ -644,13 +706,23 @@ def main():
     t0 = time.perf_counter()
     it_on = it_all = 0
     with clock:
-        for outs in lane_pool.map(one_step, jobs_of(args.steps)):
+        results = lane_pool.map(one_step, jobs_of(args.steps))
+        for outs in results:
             it_all += sum(o["guidance_iters"] for o in outs)
             it_on += sum(o["guidance_iters_fuser_on"] for o in outs)
         torch.cuda.synchronize()
     busy = time.perf_counter() - t0
     ldist.barrier()
     dt = ldist.max_over_ranks(time.perf_counter() - t0)
+    # the last step's results in layout order: the tail of the last job, or (one share of the layouts per lane) the
+    # last job of every lane
+    if len(step_jobs) > 1:
+        order = [j for sh in shares for j in sh]
+        tail = [o for outs in results[-len(step_jobs):] for o in outs]
+        last_step = [tail[order.index(j)] for j in range(len(lays))]
+    else:
+        last_step = results[-1][-len(lays):]
+    del results
     per_rank_busy = ldist.gather_floats(busy)
     tot_on, tot_all = ldist.sum_over_ranks(float(it_on)), ldist.sum_over_ranks(float(it_all))
     tot_boxes = ldist.sum_over_ranks(float(my_boxes))
@@ -663,6 +735,9 @@ def main():
     ldist.shutdown()            # all ranks together, right after the last collective; the rest is rank-0 local
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gather_outputs(last_step))
+    del last_step
     iters_on, iters_off = tot_on / n_images, (tot_all - tot_on) / n_images       # per image, job-wide means
     mean_boxes = tot_boxes / n_total
     # ---- roofline of the dominant kernel.  The timed region replays captured hipGraphs (one launch per

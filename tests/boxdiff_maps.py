@@ -1,7 +1,8 @@
 """Seeded inputs of the BoxDiff energy goldens: shared by oracle/make_golden_boxdiff.py (which runs the reference's own
 compute_ca_loss_boxdiff on them) and by the tests (which regenerate them instead of loading 13 MB of random maps from
 tests/golden/boxdiff_energy.npz — VERDICT r5 hygiene).  torch's CPU generator is deterministic for a given torch build; the
-golden records a checksum of every case's first map so that a drift would be noticed, not silently compared."""
+golden records a checksum of every case's first map, and tests/golden/boxdiff_maps_sample.npz the values of every map at
+seeded positions, so that a drift would be noticed, not silently compared."""
 import torch
 
 KEYS = [("down", 2, 0, 0), ("down", 2, 1, 0), ("up", 1, 0, 0), ("up", 1, 1, 0), ("up", 1, 2, 0)]    # generation/boxdiff.py:33-39

@@ -25,10 +25,18 @@ def test_oracle_boxdiff_energy_matches_the_reference_function():
     """compute_ca_loss_boxdiff (utils/boxdiff.py:121-196) incl. Python's max(0, nan) = 0 for a box too small for its
     top-k: value and the gradient on all five maps, to fp32 round-off."""
     g = np.load(os.path.join(GOLD, "boxdiff_energy.npz"))
+    sample = np.load(os.path.join(GOLD, "boxdiff_maps_sample.npz"))         # oracle/make_golden_boxdiff_maps.py
     for name in CASES:
         spec = json.loads(str(g[f"{name}_spec"]))
         maps = make_maps(spec["side"], spec["heads"], spec["seed"])             # the golden's inputs, regenerated from the seed
-        assert float(maps[tuple(KEYS[0])].double().sum()) == float(g[f"{name}_map0_checksum"]), name
+        # ... to fp32 round-off: ATen's soft-max / exp kernels round differently per CPU vector ISA (AVX2 vs AVX-512), so
+        # the checksum is exact only where it was recorded; the stored values at seeded positions pin every map
+        checksum = float(g[f"{name}_map0_checksum"])
+        assert abs(float(maps[tuple(KEYS[0])].double().sum()) - checksum) <= 1e-8 * abs(checksum), name
+        idx = sample[f"{name}_idx"]
+        for i, k in enumerate(KEYS):
+            np.testing.assert_allclose(maps[tuple(k)].reshape(-1).numpy()[idx], sample[f"{name}_values"][i], rtol=1e-5,
+                                       atol=0, err_msg=f"{name} map {i}")
         leaves = {tuple(k): maps[tuple(k)].clone().requires_grad_(True) for k in KEYS}
         loss = B.compute_ca_loss_boxdiff(leaves, spec["bboxes"], spec["pos"], KEYS)
         grads = torch.autograd.grad(loss, [leaves[tuple(k)] for k in KEYS])

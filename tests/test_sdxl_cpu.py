@@ -1,6 +1,6 @@
 """Host side and oracle of the SDXL-refiner row (no GPU): the restatement against what the reference CAN pin, the
 Euler sampler's algebra against the golden-pinned DDIM scheduler, the pipeline's bookkeeping, the drop-in's surface."""
-import ast
+import json
 import os
 import sys
 
@@ -98,14 +98,15 @@ def test_dropin_module_surface_matches_the_reference():
     assert list(inspect.signature(mod.refine).parameters) == ["image", "spec", "refine_seed", "refinement_step_ratio"]
     assert inspect.signature(mod.refine).parameters["refinement_step_ratio"].default == 0.5
     assert inspect.signature(mod.init).parameters["offload_model"].default is True
-    ref_file = "/root/reference/generation/sdxl_refinement.py"
-    if os.path.exists(ref_file):                                         # build container only
-        tree = ast.parse(open(ref_file).read())
-        consts = {n.targets[0].id: ast.literal_eval(n.value) for n in tree.body
-                  if isinstance(n, ast.Assign) and isinstance(n.value, ast.Constant)}
-        assert mod.sdxl_negative_prompt == consts["sdxl_negative_prompt"]
-        fns = {n.name: [a.arg for a in n.args.args] for n in tree.body if isinstance(n, ast.FunctionDef)}
-        assert fns["refine"] == ["image", "spec", "refine_seed", "refinement_step_ratio"] and "init" in fns
+    # the reference module's own surface, read from its source by oracle/make_golden_sdxl_surface.py
+    ref = json.load(open(os.path.join(GOLD, "sdxl_refinement_surface.json")))
+    assert mod.sdxl_negative_prompt == ref["constants"]["sdxl_negative_prompt"]
+    fns = ref["functions"]
+    assert fns["refine"]["params"] == ["image", "spec", "refine_seed", "refinement_step_ratio"] and "init" in fns
+    for name, f in fns.items():
+        params = inspect.signature(getattr(mod, name)).parameters
+        assert list(params)[:len(f["params"])] == f["params"], name
+        assert all(params[p].default == d for p, d in f["defaults"].items()), name
 
 
 def test_vae_encoder_host_algebra():
