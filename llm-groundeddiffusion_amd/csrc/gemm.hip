@@ -24,6 +24,8 @@
 //     M = B*HW is 128..512 and the weight stream must be spread over all 256 CUs.
 #include "common.h"
 #include "../../include/lgd_hip.h"
+#include <map>
+#include <mutex>
 #include <utility>
 #include <stdlib.h>
 
@@ -1870,6 +1872,162 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs ga) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Launch contract.  Every tile code lgd_gemm_f16 accepts, described once: main-loop family, block shape and what the
+// code serves beyond the generic rules of gemm_check.  launch_tile maps a code to its template instantiation; nothing
+// else spells a code (the tile == 0 heuristic in gemm_check picks among them).
+// ---------------------------------------------------------------------------------------------
+enum GemmLoop : int {
+  LOOP_REG,    // gemm_kernel, 4 waves: register-staged, any K
+  LOOP_DMA,    // gemm_dma_kernel, 4 waves: LDS-DMA where K % 64 == 0, else gemm_kernel of the same tile
+  LOOP_DMA8,   // gemm_dma_kernel, 8 waves: K % 64 == 0 only
+  LOOP_PIPE,   // gemm_pipe_kernel, 8 waves, 2..6 LDS stages: K, c0, c1 % 64 == 0
+  LOOP_PHASE,  // gemm_phase_kernel, 2 x 4 waves: K, c0 % 64 == 0, one source, one matrix per launch, and A / W byte
+               // ranges within one 32-bit buffer descriptor (2 GB)
+};
+enum : unsigned {
+  TILE_GEGLU = 1,       // pairs [16 value | 16 gate] column blocks (an even fragment count per wave: not 160 / 320 wide)
+  TILE_PLAIN = 2,       // plain contractions only: taps == 1, c1 == 0 (the two-stage rings)
+  TILE_ONE_SPLIT = 4,   // no split-K
+  TILE_LDS_EPI = 8,     // one split leaves through the LDS epilogue only: fp16 rows of whole 16-byte pieces, no fp32
+                        // residual, no residual together with GEGLU
+  TILE_CONV_SAME = 16,  // 3x3 convolutions only at stride 1 without upsampling fold, output size = input size
+  TILE_CNT = 32,        // split-K may combine inside the launch (LgdGemmDesc.cnt)
+};
+struct GemmTile {
+  int code;
+  GemmLoop loop;
+  int bm, bn;
+  unsigned flags;
+};
+constexpr unsigned TILE_STD = TILE_GEGLU | TILE_CNT;
+constexpr GemmTile GEMM_TILES[] = {
+    {1, LOOP_REG, 128, 128, TILE_STD},   {2, LOOP_REG, 128, 64, TILE_STD},     {3, LOOP_REG, 64, 128, TILE_STD},
+    {4, LOOP_REG, 64, 64, TILE_STD},     {5, LOOP_REG, 32, 128, TILE_STD},     {6, LOOP_REG, 128, 160, TILE_CNT},
+    {7, LOOP_REG, 64, 160, TILE_CNT},
+    {17, LOOP_DMA, 128, 128, TILE_STD},  {18, LOOP_DMA, 128, 64, TILE_STD},    {19, LOOP_DMA, 64, 128, TILE_STD},
+    {20, LOOP_DMA, 64, 64, TILE_STD},    {21, LOOP_DMA, 32, 128, TILE_STD},    {22, LOOP_DMA, 128, 160, TILE_CNT},
+    {23, LOOP_DMA, 64, 160, TILE_CNT},
+    {25, LOOP_DMA8, 256, 320, TILE_CNT}, {26, LOOP_DMA8, 256, 128, TILE_STD},
+    // three to six stages
+    {33, LOOP_PIPE, 256, 160, TILE_CNT}, {34, LOOP_PIPE, 256, 128, TILE_STD}, {35, LOOP_PIPE, 256, 64, TILE_STD},
+    {37, LOOP_PIPE, 128, 160, TILE_CNT}, {38, LOOP_PIPE, 128, 128, TILE_STD}, {39, LOOP_PIPE, 128, 64, TILE_STD},
+    {40, LOOP_PIPE, 64, 160, TILE_CNT},  {41, LOOP_PIPE, 64, 128, TILE_STD},  {42, LOOP_PIPE, 64, 64, TILE_STD},
+    // two stages: eight waves of 64 x 128; 128 x 128 at two workgroups per CU
+    {44, LOOP_PIPE, 256, 256, TILE_GEGLU | TILE_PLAIN | TILE_ONE_SPLIT | TILE_LDS_EPI},
+    {45, LOOP_PIPE, 128, 128, TILE_STD | TILE_PLAIN},
+    {46, LOOP_PHASE, 256, 256, TILE_GEGLU | TILE_LDS_EPI | TILE_CONV_SAME},
+    {47, LOOP_PHASE, 256, 320, TILE_LDS_EPI | TILE_CONV_SAME},
+};
+
+// Every precondition of lgd_gemm_f16, host only: no HIP runtime call, and pointers count for NULL-ness and alignment
+// only (lgd_gemm_check answers with it on a host without a GPU).  Fills `ga` — the descriptor with batch and split
+// counts normalised, empty trailing splits dropped, the K range of a split — and returns the tile that serves it, or
+// nullptr (LGD_ERR_ARG).
+const GemmTile* gemm_check(const LgdGemmDesc& desc, GemmArgs& ga) {
+  ga.d = desc;
+  LgdGemmDesc& d = ga.d;
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0) return nullptr;
+  if (d.taps != 1 && d.taps != 9) return nullptr;
+  ga.cin = d.c0 + d.c1;
+  if (d.K != d.taps * ga.cin) return nullptr;
+  if ((d.c0 % 8) || (d.c1 % 8) || (d.N % 4) || (d.ldw % 8) || (d.lda0 % 8) || (d.lda1 % 8) ||
+      (d.ldc % 4))
+    return nullptr;
+  if (d.c1 > 0 && !d.a1) return nullptr;
+  if (d.res && (d.ldr % 4)) return nullptr;
+  if (d.nb_o < 1) d.nb_o = 1;
+  if (d.nb_i < 1) d.nb_i = 1;
+  if (d.splits < 1) d.splits = 1;
+  const bool geglu = d.epi & LGD_EPI_GEGLU;
+  if (geglu && (d.N % 32)) return nullptr;
+  if (d.splits > 1 && !d.ws) return nullptr;
+  // folded LayerNorm: statistics are indexed by the row of ONE matrix, the columns by the stored weight row
+  if ((d.epi & LGD_EPI_ROWNORM) && (!d.rowstat || !d.colsum || d.taps != 1 || d.nb_o * d.nb_i != 1 || d.c1 > 0))
+    return nullptr;
+  // K range of each split, multiple of BK
+  int ktiles = (d.K + BK - 1) / BK;
+  int tps = (ktiles + d.splits - 1) / d.splits;
+  ga.k_per_split = tps * BK;
+  // drop empty trailing splits
+  d.splits = (ktiles + tps - 1) / tps;
+
+  int code = d.tile;
+  if (code == 0) {
+    // heuristic: the largest tile that still yields >= ~2 workgroups per CU-pair
+    long batches = (long)d.nb_o * d.nb_i * d.splits;
+    auto wgs = [&](int bm, int bn) {
+      return batches * ((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn);
+    };
+    if (d.M <= 32) code = 21;
+    else if (!geglu && d.N % 160 == 0 && wgs(128, 160) >= 384) code = 22;
+    else if (!geglu && d.N % 160 == 0 && wgs(64, 160) >= 256) code = 23;
+    else if (wgs(128, 128) >= 384 && d.N % 128 == 0) code = 17;
+    else if (wgs(64, 128) >= 256 && d.N % 128 == 0) code = 19;
+    else code = 20;
+  }
+  const GemmTile* t = nullptr;
+  for (const GemmTile& e : GEMM_TILES)
+    if (e.code == code) t = &e;
+  if (!t) return nullptr;
+  const unsigned f = t->flags;
+  if (geglu && !(f & TILE_GEGLU)) return nullptr;
+  if (t->loop == LOOP_DMA8 && (d.K % BK)) return nullptr;
+  if ((t->loop == LOOP_PIPE || t->loop == LOOP_PHASE) && ((d.K % BK) || (ga.cin % BK) || (d.c0 % BK))) return nullptr;
+  if ((f & TILE_PLAIN) && (d.taps != 1 || d.c1 > 0)) return nullptr;
+  if (t->loop == LOOP_PHASE) {
+    if (d.c1 > 0 || d.nb_o * d.nb_i != 1) return nullptr;
+    // 32-bit byte offsets inside one buffer descriptor (2 GB each)
+    if (((long)d.M + 2L * d.win + 2) * d.lda0 * 2 + 2L * d.K >= (1L << 31) || (long)d.N * d.ldw * 2 >= (1L << 31))
+      return nullptr;
+  }
+  if ((f & TILE_CONV_SAME) && d.taps == 9 && (d.stride != 1 || d.ups != 0 || d.hin != d.hout || d.win != d.wout))
+    return nullptr;
+  if ((f & TILE_ONE_SPLIT) && d.splits != 1) return nullptr;
+  if ((f & TILE_LDS_EPI) && d.splits == 1) {
+    const long c_off_max = (long)(d.nb_o - 1) * d.c_bs_o + (long)(d.nb_i - 1) * d.c_bs_i;
+    if ((d.epi & LGD_EPI_OUT_F32) || (d.N & 7) || (d.ldc & 7) || (c_off_max & 7) || (d.c_bs_o & 7) || (d.c_bs_i & 7) ||
+        (reinterpret_cast<uintptr_t>(d.c) & 15) || (d.res && (d.epi & (LGD_EPI_RES_F32 | LGD_EPI_GEGLU))))
+      return nullptr;
+  }
+  if (d.splits > 1 && d.cnt && !(f & TILE_CNT)) return nullptr;
+  return t;
+}
+
+using GemmKernel = void (*)(GemmArgs);
+
+// Kernels that take more than the default 64 KB of dynamic LDS opt in through a function attribute.  The attribute
+// belongs to a (kernel, device) pair and a failure must not stick (boxdiff.hip): it is set on the first launch of a
+// kernel on a device and remembered once it took.  `resident` (optional) receives the persistent grid of the kernel on
+// that device: as many workgroups as the chip holds at once, a multiple of 8 (one share per XCD).  Several lane threads
+// launch GEMMs concurrently (lgd_amd/lanes.py), hence the mutex.
+int lds_kernel(GemmKernel kern, int smem, int threads, long* resident = nullptr) {
+  static std::mutex mu;
+  static std::map<std::pair<GemmKernel, int>, long> ready;  // (kernel, device) -> resident workgroups, -1 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return LGD_ERR_LAUNCH;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = ready.find({kern, dev});
+  if (it == ready.end()) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
+        hipSuccess)
+      return LGD_ERR_LAUNCH;
+    it = ready.emplace(std::make_pair(kern, dev), -1L).first;
+  }
+  if (resident) {
+    if (it->second < 0) {
+      int per_cu = 0, cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), threads, smem) !=
+              hipSuccess)
+        return LGD_ERR_LAUNCH;
+      it->second = (long)(cus / 8) * 8 * (per_cu > 0 ? per_cu : 1);
+    }
+    *resident = it->second;
+  }
+  return LGD_OK;
+}
+
 template <int MI, int NI, int WM = 2>
 int launch_gemm(const GemmArgs& ga, hipStream_t st, bool dma) {
   constexpr int BM = WM * 16 * MI, BN = 32 * NI;
@@ -1879,8 +2037,7 @@ int launch_gemm(const GemmArgs& ga, hipStream_t st, bool dma) {
   if constexpr (WM == 2) {
     if (dma) hipLaunchKernelGGL((gemm_dma_kernel<MI, NI, 2>), grid, dim3(256), 0, st, ga);
     else hipLaunchKernelGGL((gemm_kernel<MI, NI>), grid, dim3(256), 0, st, ga);
-  } else {
-    if (!dma) return LGD_ERR_ARG;  // the 8-wave tiles exist only with the LDS-DMA main loop
+  } else {  // the 8-wave tiles exist only with the LDS-DMA main loop
     hipLaunchKernelGGL((gemm_dma_kernel<MI, NI, WM>), grid, dim3(128 * WM), 0, st, ga);
   }
   return lgd_check_launch();
@@ -1890,185 +2047,141 @@ template <int MI, int NI, int WM, int WN, int NS, bool CM>
 int launch_gemm_pipe_cm(const GemmArgs& ga, hipStream_t st) {
   constexpr int BM = WM * 16 * MI, BN = WN * 16 * NI;
   constexpr int SMEM = NS * (BM + BN) * BK * 2;
+  constexpr int THREADS = 64 * WM * WN;
+  // no persistent form of the chunk-major (3x3 convolution) kernels, nor of the 256 x 160 tile: with 80 accumulator
+  // registers the tile-crossing state does not fit 256 VGPRs (58 spilled even after the trims above); measured gain
+  // of persistence on that tile's K <= 640 shapes was +4..9 % of ~2.5 % of the step
+  constexpr bool HAS_PERSIST = !CM && !(MI == 4 && NI == 5) && NS != 2;
   const LgdGemmDesc& d = ga.d;
-  // function-local statics with initialisers: C++11 guarantees one thread runs the initialiser while the others wait
-  // (several lane threads launch GEMMs concurrently, lgd_amd/lanes.py)
-  static const bool attr_set = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    return true;
-  }();
-  (void)attr_set;
   long tiles = (long)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-  // persistent launch: as many workgroups as the chip holds at once (a multiple of 8, one share per XCD); each walks
-  // tiles b, b + grid, ... with its DMA ring running across tile boundaries.  LGD_GEMM_PERSIST=0 = one tile per
-  // workgroup (A/B timing).  Split-K / batched launches already spread over blockIdx.z and keep one tile each.
-  static const long resident = [] {
-    // no persistent form of the chunk-major (3x3 convolution) kernels, nor of the 256 x 160 tile: with 80 accumulator
-    // registers the tile-crossing state does not fit 256 VGPRs (58 spilled even after the trims above); measured gain
-    // of persistence on that tile's K <= 640 shapes was +4..9 % of ~2.5 % of the step
-    if constexpr (CM || (MI == 4 && NI == 5) || NS == 2) return 0L;
-    else {
-      const char* e = getenv("LGD_GEMM_PERSIST");
-      int per_cu = 0, cus = 0, dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_kernel<MI, NI, WM, WN, NS, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, reinterpret_cast<const void*>(&gemm_pipe_kernel<MI, NI, WM, WN, NS, false, true>), 64 * WM * WN, SMEM);
-      return (e && e[0] == '0') ? 0L : (long)(cus / 8) * 8 * (per_cu > 0 ? per_cu : 1);
-    }
-  }();
+  // persistent launch: as many workgroups as the chip holds at once (lds_kernel); each walks tiles b, b + grid, ... with
+  // its DMA ring running across tile boundaries.  LGD_GEMM_PERSIST=0 = one tile per workgroup (A/B timing).  Split-K /
+  // batched launches already spread over blockIdx.z and keep one tile each.
+  GemmKernel kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM>;
+  long resident = 0;
+  if constexpr (HAS_PERSIST) {
+    static const bool persist_on = [] { const char* e = getenv("LGD_GEMM_PERSIST"); return !(e && e[0] == '0'); }();
+    if (persist_on)
+      if (int rc = lds_kernel(&gemm_pipe_kernel<MI, NI, WM, WN, NS, false, true>, SMEM, THREADS, &resident)) return rc;
+  }
   // measured (tools/gemm_ab.py, LGD_GEMM_PERSIST=0 vs 1): +4..9 % where K <= 640 (5-10 K tiles per output tile: the
   // pipeline fill is a visible share of a tile), neutral to -8 % from K = 1280 up — enabled for short K walks only
   const bool persist = resident > 0 && d.nb_o * d.nb_i * d.splits == 1 && tiles > resident && d.K <= 10 * BK && d.taps == 1;
   dim3 grid((unsigned)(persist ? resident : tiles), 1, (unsigned)(d.nb_o * d.nb_i * d.splits));
+  if constexpr (HAS_PERSIST)
+    if (persist) kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, false, true>;
 #ifdef LGD_GEMM_ABLATION
   static const int abl = [] { const char* e = getenv("LGD_GEMM_ABL"); return e ? atoi(e) : 0; }();
   if (abl) {
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-      hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), SMEM, st, ga);
-    };
     switch (abl) {
-      case 1: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 1>); break;
-      case 2: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 2>); break;
-      case 3: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 3>); break;
-      case 4: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 4>); break;
-      case 6: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 6>); break;
-      case 8: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 8>); break;
-      case 11: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 11>); break;
-      case 16: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 16>); break;
-      case 17: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 17>); break;
-      case 20: go(&gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 20>); break;
-      default: break;
+      case 1: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 1>; break;
+      case 2: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 2>; break;
+      case 3: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 3>; break;
+      case 4: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 4>; break;
+      case 6: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 6>; break;
+      case 8: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 8>; break;
+      case 11: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 11>; break;
+      case 16: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 16>; break;
+      case 17: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 17>; break;
+      case 20: kern = &gemm_pipe_kernel<MI, NI, WM, WN, NS, CM, false, 20>; break;
+      default: return lgd_check_launch();
     }
-    return lgd_check_launch();
   }
 #endif
-  if constexpr (!CM && !(MI == 4 && NI == 5) && NS != 2) {     // see `resident`: no such instantiations
-    if (persist) {
-      hipLaunchKernelGGL((gemm_pipe_kernel<MI, NI, WM, WN, NS, false, true>), grid, dim3(64 * WM * WN), SMEM, st, ga);
-      return lgd_check_launch();
-    }
-  }
-  hipLaunchKernelGGL((gemm_pipe_kernel<MI, NI, WM, WN, NS, CM>), grid, dim3(64 * WM * WN), SMEM, st, ga);
+  if (int rc = lds_kernel(kern, SMEM, THREADS)) return rc;
+  hipLaunchKernelGGL(kern, grid, dim3(THREADS), SMEM, st, ga);
   return lgd_check_launch();
 }
 
 // chunk-major K order for plain 3x3 convolutions (stride 1, no upsampling fold, one source); LGD_GEMM_NO_CM=1
-// in the environment keeps the weight layout's tap-major order (A/B timing of the two walks).
+// in the environment keeps the weight layout's tap-major order (A/B timing of the two walks).  The two-stage rings
+// take plain contractions only.
 template <int MI, int NI, int WM, int WN, int NS>
 int launch_gemm_pipe(const GemmArgs& ga, hipStream_t st) {
   const LgdGemmDesc& d = ga.d;
   static const int no_cm = [] { const char* e = getenv("LGD_GEMM_NO_CM"); return (e && e[0] == '1') ? 1 : 0; }();
-  if constexpr (NS == 2) {          // the two-stage 256 x 256 tile: plain single-source contractions only
-    if (d.taps != 1 || d.c1 > 0) return LGD_ERR_ARG;
-    if constexpr (MI * NI >= 32) {  // 256 x 256: the LDS epilogue only (one split, fp16 rows of whole 16-byte pieces)
-      const long c_off_max = (long)(d.nb_o - 1) * d.c_bs_o + (long)(d.nb_i - 1) * d.c_bs_i;
-      if (d.splits != 1 || (d.epi & LGD_EPI_OUT_F32) || (d.N & 7) || (d.ldc & 7) || (c_off_max & 7) || (d.c_bs_o & 7) ||
-          (d.c_bs_i & 7) || (reinterpret_cast<uintptr_t>(d.c) & 15) || d.K < BK ||
-          (d.res && (d.epi & (LGD_EPI_RES_F32 | LGD_EPI_GEGLU))))
-        return LGD_ERR_ARG;
-    }
-    return launch_gemm_pipe_cm<MI, NI, WM, WN, NS, false>(ga, st);
-  } else {
-  const bool cm = d.taps == 9 && d.stride == 1 && d.ups == 0 && d.c1 == 0 && !no_cm;
-  return cm ? launch_gemm_pipe_cm<MI, NI, WM, WN, NS, true>(ga, st) : launch_gemm_pipe_cm<MI, NI, WM, WN, NS, false>(ga, st);
+  if constexpr (NS != 2) {
+    if (d.taps == 9 && d.stride == 1 && d.ups == 0 && d.c1 == 0 && !no_cm)
+      return launch_gemm_pipe_cm<MI, NI, WM, WN, NS, true>(ga, st);
   }
+  return launch_gemm_pipe_cm<MI, NI, WM, WN, NS, false>(ga, st);
 }
 
 // Phase-split 256-row tiles (gemm_phase_kernel): plain single-source contractions and 3x3 stride-1 same-size
 // convolutions; one split leaves through the LDS epilogue (fp16 rows of whole 16-byte pieces), several splits write fp32
-// partials for splitk_reduce_kernel.  Everything else is the caller's business (LGD_ERR_ARG; ops._table_tile_applies).
+// partials for splitk_reduce_kernel.
 template <int MI, int NI>
 int launch_gemm_phase(const GemmArgs& ga, hipStream_t st) {
   constexpr int BM = 32 * MI, BN = 64 * NI;
   constexpr int SMEM = 2 * (BM + BN) * BK * 2;
   const LgdGemmDesc& d = ga.d;
   const bool conv = d.taps == 9;
-  if (d.c1 > 0 || d.K < BK || d.nb_o * d.nb_i != 1) return LGD_ERR_ARG;
-  if (conv && (d.stride != 1 || d.ups != 0 || d.hin != d.hout || d.win != d.wout)) return LGD_ERR_ARG;
-  // 32-bit byte offsets inside one buffer descriptor (2 GB each)
-  if (((long)d.M + 2L * d.win + 2) * d.lda0 * 2 + 2L * d.K >= (1L << 31) || (long)d.N * d.ldw * 2 >= (1L << 31)) return LGD_ERR_ARG;
-  if (d.splits == 1) {
-    const long c_off_max = (long)(d.nb_o - 1) * d.c_bs_o + (long)(d.nb_i - 1) * d.c_bs_i;
-    if ((d.epi & LGD_EPI_OUT_F32) || (d.N & 7) || (d.ldc & 7) || (c_off_max & 7) || (d.c_bs_o & 7) || (d.c_bs_i & 7) ||
-        (reinterpret_cast<uintptr_t>(d.c) & 15) || ((d.epi & LGD_EPI_GEGLU) && (NI & 1)) ||
-        (d.res && (d.epi & (LGD_EPI_RES_F32 | LGD_EPI_GEGLU))))
-      return LGD_ERR_ARG;
-  } else if (d.cnt) {
-    return LGD_ERR_ARG;
-  }
   long tiles = (long)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
   dim3 grid((unsigned)tiles, 1, (unsigned)(d.nb_o * d.nb_i * d.splits));
+  GemmKernel kern = conv ? &gemm_phase_kernel<MI, NI, true> : &gemm_phase_kernel<MI, NI, false>;
 #ifdef LGD_GEMM_ABLATION
   static const int abl = [] { const char* e = getenv("LGD_GEMM_ABL"); return e ? atoi(e) : 0; }();
   if (abl) {
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-      hipLaunchKernelGGL(kern, grid, dim3(512), SMEM, st, ga);
-    };
-#define LGD_PH_ABL(A) case A: if (conv) go(&gemm_phase_kernel<MI, NI, true, A>); else go(&gemm_phase_kernel<MI, NI, false, A>); break;
+#define LGD_PH_ABL(A) case A: kern = conv ? &gemm_phase_kernel<MI, NI, true, A> : &gemm_phase_kernel<MI, NI, false, A>; break;
     switch (abl) {
       LGD_PH_ABL(1) LGD_PH_ABL(2) LGD_PH_ABL(3) LGD_PH_ABL(4) LGD_PH_ABL(6) LGD_PH_ABL(16) LGD_PH_ABL(17) LGD_PH_ABL(20) LGD_PH_ABL(32) LGD_PH_ABL(64) LGD_PH_ABL(96)
-      default: break;
+      default: return lgd_check_launch();
     }
 #undef LGD_PH_ABL
-    return lgd_check_launch();
   }
 #endif
-  if (conv) {
-    static const bool attr_set = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_phase_kernel<MI, NI, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-      return true;
-    }();
-    (void)attr_set;
-    hipLaunchKernelGGL((gemm_phase_kernel<MI, NI, true>), grid, dim3(512), SMEM, st, ga);
-  } else {
-    static const bool attr_set = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_phase_kernel<MI, NI, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-      return true;
-    }();
-    (void)attr_set;
-    hipLaunchKernelGGL((gemm_phase_kernel<MI, NI, false>), grid, dim3(512), SMEM, st, ga);
-  }
+  if (int rc = lds_kernel(kern, SMEM, 512)) return rc;
+  hipLaunchKernelGGL(kern, grid, dim3(512), SMEM, st, ga);
   return lgd_check_launch();
+}
+
+// The instantiation behind each code of GEMM_TILES (gemm_check has accepted the descriptor for it).  The order of the
+// cases is the order of first instantiation, which fixes the kernels' order in the code object.
+int launch_tile(const GemmTile& t, const GemmArgs& ga, hipStream_t st) {
+  const bool dma = t.loop == LOOP_DMA && ga.d.K % BK == 0;
+  switch (t.code) {
+    case 33: return launch_gemm_pipe<4, 5, 4, 2, 3>(ga, st);
+    case 34: return launch_gemm_pipe<4, 4, 4, 2, 3>(ga, st);
+    case 35: return launch_gemm_pipe<4, 2, 4, 2, 4>(ga, st);
+    case 37: return launch_gemm_pipe<2, 5, 4, 2, 4>(ga, st);
+    case 38: return launch_gemm_pipe<2, 4, 4, 2, 4>(ga, st);
+    case 39: return launch_gemm_pipe<2, 2, 4, 2, 5>(ga, st);
+    case 40: return launch_gemm_pipe<1, 5, 4, 2, 5>(ga, st);
+    case 41: return launch_gemm_pipe<1, 4, 4, 2, 5>(ga, st);
+    case 42: return launch_gemm_pipe<1, 2, 4, 2, 6>(ga, st);
+    case 44: return launch_gemm_pipe<4, 8, 4, 2, 2>(ga, st);
+    case 45: return launch_gemm_pipe<2, 4, 4, 2, 2>(ga, st);
+    case 46: return launch_gemm_phase<8, 4>(ga, st);
+    case 47: return launch_gemm_phase<8, 5>(ga, st);
+    case 1: case 17: return launch_gemm<4, 4>(ga, st, dma);
+    case 2: case 18: return launch_gemm<4, 2>(ga, st, dma);
+    case 3: case 19: return launch_gemm<2, 4>(ga, st, dma);
+    case 4: case 20: return launch_gemm<2, 2>(ga, st, dma);
+    case 5: case 21: return launch_gemm<1, 4>(ga, st, dma);
+    case 6: case 22: return launch_gemm<4, 5>(ga, st, dma);
+    case 7: case 23: return launch_gemm<2, 5>(ga, st, dma);
+    case 25: return launch_gemm<4, 10, 4>(ga, st, true);
+    case 26: return launch_gemm<4, 4, 4>(ga, st, true);
+  }
+  return LGD_ERR_ARG;  // a code of GEMM_TILES without an instantiation
 }
 
 }  // namespace
 
 extern "C" int lgd_abi_version(void) { return LGD_ABI_VERSION; }
 
+extern "C" int lgd_gemm_check(const LgdGemmDesc* desc) {
+  GemmArgs ga;
+  return desc && gemm_check(*desc, ga) ? LGD_OK : LGD_ERR_ARG;
+}
+
 extern "C" int lgd_gemm_f16(const LgdGemmDesc* desc, void* stream) {
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (!desc) return LGD_ERR_ARG;
   GemmArgs ga;
-  ga.d = *desc;
-  LgdGemmDesc& d = ga.d;
+  const GemmTile* t = desc ? gemm_check(*desc, ga) : nullptr;
+  if (!t) return LGD_ERR_ARG;
+  const LgdGemmDesc& d = ga.d;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0) return LGD_ERR_ARG;
-  if (d.taps != 1 && d.taps != 9) return LGD_ERR_ARG;
-  ga.cin = d.c0 + d.c1;
-  if (d.K != d.taps * ga.cin) return LGD_ERR_ARG;
-  if ((d.c0 % 8) || (d.c1 % 8) || (d.N % 4) || (d.ldw % 8) || (d.lda0 % 8) || (d.lda1 % 8) ||
-      (d.ldc % 4))
-    return LGD_ERR_ARG;
-  if (d.c1 > 0 && !d.a1) return LGD_ERR_ARG;
-  if (d.res && (d.ldr % 4)) return LGD_ERR_ARG;
-  if (d.nb_o < 1) d.nb_o = 1;
-  if (d.nb_i < 1) d.nb_i = 1;
-  if (d.splits < 1) d.splits = 1;
-  const bool geglu = d.epi & LGD_EPI_GEGLU;
-  if (geglu && (d.N % 32)) return LGD_ERR_ARG;
-  if (d.splits > 1 && !d.ws) return LGD_ERR_ARG;
-  // folded LayerNorm: statistics are indexed by the row of ONE matrix, the columns by the stored weight row
-  if ((d.epi & LGD_EPI_ROWNORM) && (!d.rowstat || !d.colsum || d.taps != 1 || d.nb_o * d.nb_i != 1 || d.c1 > 0))
-    return LGD_ERR_ARG;
-  // K range of each split, multiple of BK
 #ifdef LGD_GEMM_ABLATION
   { const char* e = getenv("LGD_GEMM_STAGGER"); ga.stagger = e ? atoi(e) : 0; }
 #endif
@@ -2083,84 +2196,14 @@ extern "C" int lgd_gemm_f16(const LgdGemmDesc* desc, void* stream) {
       ga.group_m = forced > 0 ? forced : (int)(g < 1 ? 1 : g > 8 ? 8 : g);
     }
   }
-  int ktiles = (d.K + BK - 1) / BK;
-  int tps = (ktiles + d.splits - 1) / d.splits;
-  ga.k_per_split = tps * BK;
-  // drop empty trailing splits
-  d.splits = (ktiles + tps - 1) / tps;
-
-  int tile = d.tile;
-  if (tile == 0) {
-    // heuristic: the largest tile that still yields >= ~2 workgroups per CU-pair
-    long batches = (long)d.nb_o * d.nb_i * d.splits;
-    auto wgs = [&](int bm, int bn) {
-      return batches * ((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn);
-    };
-    if (d.M <= 32) tile = 21;
-    else if (!geglu && d.N % 160 == 0 && wgs(128, 160) >= 384) tile = 22;
-    else if (!geglu && d.N % 160 == 0 && wgs(64, 160) >= 256) tile = 23;
-    else if (wgs(128, 128) >= 384 && d.N % 128 == 0) tile = 17;
-    else if (wgs(64, 128) >= 256 && d.N % 128 == 0) tile = 19;
-    else tile = 20;
-  }
-  // tile codes 33.. = 8-wave three-stage pipelined main loop (K % 64 == 0 only)
-  if (tile > 32) {
-    if ((d.K % BK) || (ga.cin % BK) || (d.c0 % BK)) return LGD_ERR_ARG;
-    int rc;
-    switch (tile) {
-      case 33: rc = geglu ? LGD_ERR_ARG : launch_gemm_pipe<4, 5, 4, 2, 3>(ga, st); break;  // 256x160, 3 stages
-      case 34: rc = launch_gemm_pipe<4, 4, 4, 2, 3>(ga, st); break;                         // 256x128, 3
-      case 35: rc = launch_gemm_pipe<4, 2, 4, 2, 4>(ga, st); break;                         // 256x64,  4
-      case 37: rc = geglu ? LGD_ERR_ARG : launch_gemm_pipe<2, 5, 4, 2, 4>(ga, st); break;  // 128x160, 4
-      case 38: rc = launch_gemm_pipe<2, 4, 4, 2, 4>(ga, st); break;                         // 128x128, 4
-      case 39: rc = launch_gemm_pipe<2, 2, 4, 2, 5>(ga, st); break;                         // 128x64,  5
-      case 40: rc = geglu ? LGD_ERR_ARG : launch_gemm_pipe<1, 5, 4, 2, 5>(ga, st); break;  // 64x160,  5
-      case 41: rc = launch_gemm_pipe<1, 4, 4, 2, 5>(ga, st); break;                         // 64x128,  5
-      case 42: rc = launch_gemm_pipe<1, 2, 4, 2, 6>(ga, st); break;                         // 64x64,   6
-      case 44: rc = launch_gemm_pipe<4, 8, 4, 2, 2>(ga, st); break;                         // 256x256, 2 stages, eight waves of 64x128
-      case 45: rc = launch_gemm_pipe<2, 4, 4, 2, 2>(ga, st); break;                         // 128x128, 2 stages, two workgroups per CU
-      case 46: rc = launch_gemm_phase<8, 4>(ga, st); break;                                 // 256x256, phase-split (round 6)
-      case 47: rc = geglu ? LGD_ERR_ARG : launch_gemm_phase<8, 5>(ga, st); break;          // 256x320, phase-split
-      default: return LGD_ERR_ARG;
-    }
-    if (rc) return rc;
-    if (d.splits > 1 && !d.cnt) {
-      int n_out = geglu ? d.N / 2 : d.N;
-      long total = (long)d.M * (n_out / 4);
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      dim3 grid(blocks, 1, d.nb_o * d.nb_i);
-      hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, ga);
-      rc = lgd_check_launch();
-    }
-    return rc;
-  }
-  // tile codes 1..7 = register-staged main loop; 16 + code = LDS-DMA main loop (17..23, and the 8-wave 25/26)
-  bool dma = tile > 16;
-  if (dma) tile -= 16;
-  if (dma && (d.K % BK)) dma = false;
-  int rc;
-  switch (tile) {
-    case 1: rc = launch_gemm<4, 4>(ga, st, dma); break;
-    case 2: rc = launch_gemm<4, 2>(ga, st, dma); break;
-    case 3: rc = launch_gemm<2, 4>(ga, st, dma); break;
-    case 4: rc = launch_gemm<2, 2>(ga, st, dma); break;
-    case 5: rc = launch_gemm<1, 4>(ga, st, dma); break;
-    case 6: rc = geglu ? LGD_ERR_ARG : launch_gemm<4, 5>(ga, st, dma); break;  // 128x160: N = 320 k exactly
-    case 7: rc = geglu ? LGD_ERR_ARG : launch_gemm<2, 5>(ga, st, dma); break;  // 64x160
-    case 9: rc = geglu ? LGD_ERR_ARG : launch_gemm<4, 10, 4>(ga, st, dma); break;  // 256x320, 8 waves
-    case 10: rc = launch_gemm<4, 4, 4>(ga, st, dma); break;                         // 256x128, 8 waves
-    default: return LGD_ERR_ARG;
-  }
-  if (rc) return rc;
-  if (d.splits > 1 && !d.cnt) {
-    int n_out = geglu ? d.N / 2 : d.N;
-    long total = (long)d.M * (n_out / 4);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    dim3 grid(blocks, 1, d.nb_o * d.nb_i);
-    hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, ga);
-    rc = lgd_check_launch();
-  }
-  return rc;
+  int rc = launch_tile(*t, ga, st);
+  if (rc || d.splits == 1 || d.cnt) return rc;
+  // the split-K partials: a second launch sums them and applies the epilogue
+  int n_out = (d.epi & LGD_EPI_GEGLU) ? d.N / 2 : d.N;
+  long total = (long)d.M * (n_out / 4);
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  dim3 grid(blocks, 1, d.nb_o * d.nb_i);
+  hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, st, ga);
+  return lgd_check_launch();
 }

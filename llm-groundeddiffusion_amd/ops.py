@@ -119,71 +119,55 @@ def gemm_desc(a0, w, c, M, N, K, *, a1=None, lda0=None, lda1=0, c0=None, c1=0, t
     ent = tuning_table().get(shape_key(d)) if (splits is None or not tile) else None
     if splits is None:
         splits = ent["splits"] if ent else choose_splits(M, N, K, nb_o * nb_i)
-    if ent and not _table_tile_applies(ent["tile"], d, splits, epi, n_out):
-        ent = None                                        # same M/N/K key, but an epilogue form that tile does not have
-    if not tile:
-        tile = ent["tile"] if (ent and ent["splits"] == splits) else choose_tile(M, N, nb_o * nb_i * max(splits, 1), bool(epi & EPI_GEGLU), K,
-                                                                             pipe_ok=(K % 64 == 0 and d.c0 % 64 == 0 and d.c1 % 64 == 0))
     if splits > 1 and ws is None:
         need = splits * M * N * nb_o * nb_i
         ws = workspace(c.device if torch.is_tensor(c) else "cuda")
         if need > ws.numel():
             raise RuntimeError(f"split-K workspace too small for {splits}x{M}x{N}")
     d.splits, d.ws = splits, ptr(ws)
+    d.cnt = 0
     d.tile = tile
+    if not tile:
+        # the table is keyed by shape_key (M, N, K, gather, GEGLU flag), not by the whole descriptor: its tile serves
+        # this one only where the library accepts it (epilogue form, strides, alignment), else the heuristic's
+        if ent and ent["splits"] == splits:
+            d.tile = ent["tile"]
+        if not d.tile or not gemm_accepts(d):
+            d.tile = choose_tile(M, N, nb_o * nb_i * max(splits, 1), bool(epi & EPI_GEGLU), K,
+                                 pipe_ok=(K % 64 == 0 and d.c0 % 64 == 0 and d.c1 % 64 == 0))
     log = getattr(_TUNING_TLS, "log", None)
     if log is not None:                                  # tests: which table entries a plan was built from
-        log.append((shape_key(d), tile, splits))
-    d.cnt = 0
-    if splits > 1 and SPLITK_IN_LAUNCH and torch.is_tensor(c) and c.is_cuda and tile not in PHASE_TILES:   # phase tiles: reduce launch only
+        log.append((shape_key(d), d.tile, splits))
+    if splits > 1 and SPLITK_IN_LAUNCH and torch.is_tensor(c) and c.is_cuda:
         # the smallest tile of the library is 32 rows x 64 columns: an upper bound of the launch's output tiles
         if nb_o * nb_i * ((M + 31) // 32) * ((N + 63) // 64) <= N_COUNTERS:
             d.cnt = splitk_counters(c.device).data_ptr()
+            if not gemm_accepts(d):                      # a tile without the in-launch combine: reduce launch
+                d.cnt = 0
     return d
 
 
-def _table_tile_applies(tile, d, splits, epi, n_out) -> bool:
-    """The tuning table is keyed by shape_key (M, N, K, gather, GEGLU flag), not by the whole epilogue form.  The two-stage
-    ring tiles of round 4 take plain single-source contractions only, and the 256 x 256 one (44) leaves through the LDS
-    epilogue alone: one split, fp16 rows of N % 8 = 0 with an 8-aligned leading dimension and a 16-byte aligned base, no
-    fp32 output / residual, not GEGLU together with a residual (launch_gemm_pipe returns LGD_ERR_ARG otherwise).  A caller
-    with the same M/N/K but such an epilogue must get the heuristic tile, not a RuntimeError."""
-    if tile in PHASE_TILES:
-        # round 6, phase-split 256-row tiles: plain single-source contractions and 3x3 stride-1 same-size convolutions;
-        # one split through the LDS epilogue (as tile 44), several splits through fp32 partials; no GEGLU on 256 x 320
-        if d.c1 != 0 or d.nb_o * d.nb_i != 1 or (d.taps == 9 and (d.stride != 1 or d.ups != 0 or d.hin != d.hout or d.win != d.wout)):
-            return False
-        if (epi & EPI_GEGLU) and tile == 47:
-            return False
-        if splits != 1:
-            return True
-        if (epi & (EPI_OUT_F32 | EPI_RES_F32)) or ((epi & EPI_GEGLU) and d.res):
-            return False
-        return n_out % 8 == 0 and d.ldc % 8 == 0 and d.c % 16 == 0
-    if tile not in (44, 45):
-        return True
-    if d.taps != 1 or d.c1 != 0:
-        return False
-    if tile == 45:
-        return True
-    if splits != 1 or (epi & (EPI_OUT_F32 | EPI_RES_F32)) or ((epi & EPI_GEGLU) and d.res):
-        return False
-    return n_out % 8 == 0 and d.ldc % 8 == 0 and d.c % 16 == 0
+def gemm_accepts(d) -> bool:
+    """Whether lgd_gemm_f16 would launch descriptor `d` (lgd_gemm_check: host only, needs no GPU)."""
+    return _lib.load().lgd_gemm_check(C.byref(d)) == 0
 
 
-_TILE_DIMS = {1: (4, 4), 2: (4, 2), 3: (2, 4), 4: (2, 2), 5: (1, 4), 6: (4, 5), 7: (2, 5)}
-TILE_NAMES = {t: f"gemm_kernel<{mi},{ni}> {32 * mi}x{32 * ni}" for t, (mi, ni) in _TILE_DIMS.items()}
-TILE_NAMES.update({16 + t: f"gemm_dma_kernel<{mi},{ni},2> {32 * mi}x{32 * ni}" for t, (mi, ni) in _TILE_DIMS.items()})
-TILE_NAMES.update({25: "gemm_dma_kernel<4,10,4> 256x320", 26: "gemm_dma_kernel<4,4,4> 256x128"})
-# 8-wave pipelined main loop: code -> (MI, NI, stages); tile = 64*MI x 32*NI
-_PIPE_DIMS = {33: (4, 5, 3), 34: (4, 4, 3), 35: (4, 2, 4), 37: (2, 5, 4), 38: (2, 4, 4), 39: (2, 2, 5), 40: (1, 5, 5),
-              41: (1, 4, 5), 42: (1, 2, 6)}
-TILE_NAMES.update({t: f"gemm_pipe_kernel<{mi},{ni},4,2,{ns}> {64 * mi}x{32 * ni}" for t, (mi, ni, ns) in _PIPE_DIMS.items()})
-# round 4: 256 x 256, two-stage ring (plain single-source contractions only), eight waves of 64 x 128
-TILE_NAMES.update({44: "gemm_pipe_kernel<4,8,4,2,2> 256x256", 45: "gemm_pipe_kernel<2,4,4,2,2> 128x128 x2/CU"})
-# round 6: phase-split main loop (two wave groups one interval apart, four phases per K tile), 2 x 4 waves of 128 x (64 | 80)
-PHASE_TILES = {46: (256, 256), 47: (256, 320)}
-TILE_NAMES.update({46: "gemm_phase_kernel<8,4> 256x256", 47: "gemm_phase_kernel<8,5> 256x320"})
+# profiler kernel names of the tile codes (tools/ and profiles/ key on them); which descriptors a code serves is the
+# library's to say (gemm_accepts)
+TILE_NAMES = {
+    1: "gemm_kernel<4,4> 128x128", 2: "gemm_kernel<4,2> 128x64", 3: "gemm_kernel<2,4> 64x128", 4: "gemm_kernel<2,2> 64x64",
+    5: "gemm_kernel<1,4> 32x128", 6: "gemm_kernel<4,5> 128x160", 7: "gemm_kernel<2,5> 64x160",
+    17: "gemm_dma_kernel<4,4,2> 128x128", 18: "gemm_dma_kernel<4,2,2> 128x64", 19: "gemm_dma_kernel<2,4,2> 64x128",
+    20: "gemm_dma_kernel<2,2,2> 64x64", 21: "gemm_dma_kernel<1,4,2> 32x128", 22: "gemm_dma_kernel<4,5,2> 128x160",
+    23: "gemm_dma_kernel<2,5,2> 64x160", 25: "gemm_dma_kernel<4,10,4> 256x320", 26: "gemm_dma_kernel<4,4,4> 256x128",
+    33: "gemm_pipe_kernel<4,5,4,2,3> 256x160", 34: "gemm_pipe_kernel<4,4,4,2,3> 256x128",
+    35: "gemm_pipe_kernel<4,2,4,2,4> 256x64", 37: "gemm_pipe_kernel<2,5,4,2,4> 128x160",
+    38: "gemm_pipe_kernel<2,4,4,2,4> 128x128", 39: "gemm_pipe_kernel<2,2,4,2,5> 128x64",
+    40: "gemm_pipe_kernel<1,5,4,2,5> 64x160", 41: "gemm_pipe_kernel<1,4,4,2,5> 64x128",
+    42: "gemm_pipe_kernel<1,2,4,2,6> 64x64", 44: "gemm_pipe_kernel<4,8,4,2,2> 256x256",
+    45: "gemm_pipe_kernel<2,4,4,2,2> 128x128 x2/CU", 46: "gemm_phase_kernel<8,4> 256x256",
+    47: "gemm_phase_kernel<8,5> 256x320",
+}
 
 
 def choose_tile(M, N, batches=1, geglu=False, K=64, pipe_ok=False):

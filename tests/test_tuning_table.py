@@ -4,6 +4,8 @@ import json
 import os
 import re
 
+import pytest
+
 import lgd_amd  # noqa: F401
 from lgd_amd import ops
 
@@ -15,6 +17,23 @@ TWO_STAGE = {44, 45}                                  # plain single-source cont
 PHASE = {46, 47}                                      # round 6: single source; plain or 3x3 stride-1 same-size convolution
 LEGAL = (set(range(1, 11)) | {16 + t for t in range(1, 11)} | set(PIPE)) - {8, 24}
 TILE_BN = {1: 128, 2: 64, 3: 128, 4: 64, 5: 128, 6: 160, 7: 160, 9: 320, 10: 128}
+KEY = r"M(\d+)_N(\d+)_K(\d+)_t(\d)_c(\d+)\+(\d+)_h(\d+)x(\d+)_s(\d)_u(\d)_e(\d)_b(\d+)$"
+P = 1 << 20                                           # an aligned placeholder address: descriptors are only checked here
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _library():
+    """gemm_desc asks the library (lgd_gemm_check) whether a table tile serves a descriptor."""
+    import __graft_entry__ as ge
+    ge.build()
+
+
+def _table_desc(key, tile, splits, **kw):
+    """The descriptor of a table shape in its plain form (no bias / residual, fp16 rows of n_out columns)."""
+    M, N, K, taps, c0, c1, hin, hout, stride, ups, geglu, nb = (int(g) for g in re.match(KEY, key).groups())
+    return ops.gemm_desc(P, P, P, M, N, K, a1=P if c1 else None, c0=c0, c1=c1, lda1=c1, taps=taps, hin=hin, win=hin,
+                         hout=hout, wout=hout, stride=stride, ups=ups, epi=ops.EPI_GEGLU if geglu else 0,
+                         splits=splits, ws=P if splits > 1 else None, tile=tile, nb_o=nb, **kw)
 
 
 def test_table_entries_are_legal():
@@ -105,3 +124,40 @@ def test_table_tile_44_is_not_handed_to_an_epilogue_it_does_not_have():
         assert ops.gemm_desc(a, a, a, M, N, K, ldc=N + 4).tile != 44
         assert ops.gemm_desc(a[0:0].new_empty(9)[1:], a, a, M, N, K).tile == 44      # the OPERAND's alignment is not the rule
         assert ops.gemm_desc(a, a, torch.empty(9, dtype=torch.float16)[1:], M, N, K).tile != 44   # output base not 16-byte aligned
+
+
+def _entries():
+    lanes = TABLE.replace("tuning_gfx950.json", "tuning_gfx950_lanes.json")
+    return list(json.load(open(TABLE)).items()) + list(json.load(open(lanes)).items())
+
+
+def test_table_entries_pass_the_library_check():
+    """Every entry of both tables is a descriptor the library launches: its own (tile, splits) on its shape."""
+    entries = _entries()
+    assert len(entries) >= 400
+    refused = [(key, e["tile"], e["splits"]) for key, e in entries
+               if not ops.gemm_accepts(_table_desc(key, e["tile"], e["splits"]))]
+    assert not refused, refused[:10]
+
+
+def test_phase_table_tile_is_not_handed_a_wide_stride_view():
+    """The table key holds M / N / K, not the row stride of A: a phase-split tile (46 / 47) addresses A through one
+    32-bit buffer descriptor, so a table hit on a view whose (M + 2 win + 2) lda0 spans 2 GB must get the heuristic tile
+    (a launch the library takes), not a RuntimeError at launch."""
+    found = 0
+    for mode in ("latency", "throughput"):
+        with ops.tuning(mode):
+            for key, e in ops.tuning_table().items():
+                if e["tile"] not in PHASE:
+                    continue
+                M, N, K, taps, c0, c1, hin = (int(g) for g in re.match(KEY, key).groups()[:7])
+                plain = _table_desc(key, 0, e["splits"], lda0=c0)
+                assert (plain.tile, plain.splits) == (e["tile"], e["splits"]), key
+                lda0 = ((1 << 31) // (2 * (M + 2 * hin + 2)) // 8 + 1) * 8        # lda0 >> c0: past 2 GB
+                wide = _table_desc(key, 0, e["splits"], lda0=lda0)
+                assert wide.tile not in PHASE and wide.splits == e["splits"], key
+                assert wide.tile == ops.choose_tile(M, N, e["splits"], bool(wide.epi & ops.EPI_GEGLU), K,
+                                                    pipe_ok=(K % 64 == 0 and c0 % 64 == 0 and c1 % 64 == 0)), key
+                assert ops.gemm_accepts(wide), key
+                found += 1
+    assert found >= 2

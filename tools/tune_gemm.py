@@ -74,11 +74,22 @@ TILE_DIMS = {17: (128, 128), 18: (128, 64), 19: (64, 128), 20: (64, 64), 21: (32
              44: (256, 256), 45: (128, 128),
              # round 6: phase-split 256-row tiles (plain single-source contractions and 3x3 stride-1 same-size convolutions)
              46: (256, 256), 47: (256, 320)}
-PLAIN_ONLY = {44, 45}
-PHASE = {46, 47}
-NO_GEGLU = {22, 23, 33, 37, 40, 47}              # odd fragment counts cannot pair value | gate column blocks
+BATCHED_SKIP = {44, 45}    # tuner policy: batched problems (the VAE's mid-block attention GEMMs) keep the older tiles
 VERIFY_TOL = 2e-3                                # fp16 outputs, different summation orders
 rejected = []
+
+
+def accepts(sh, key, tile, splits):
+    """Whether the library launches `tile` with `splits` on this shape: lgd_gemm_check on the descriptor make_desc
+    builds, with aligned placeholder pointers and the key's batch count."""
+    P = 1 << 20
+    n_out = sh["N"] // 2 if sh["epi"] & 1 else sh["N"]
+    d = ops.gemm_desc(P, P, P, sh["M"], sh["N"], sh["K"], a1=P if sh["c1"] else None, c0=sh["c0"], c1=sh["c1"],
+                      lda0=sh["c0"], lda1=sh["c1"], taps=sh["taps"], hin=sh["hin"], win=sh["win"], hout=sh["hout"],
+                      wout=sh["wout"], stride=sh["stride"], ups=sh["ups"], bias=P if sh["has_bias"] else None,
+                      res=P if sh["has_res"] else None, ldr=n_out, epi=sh["epi"] & 1, ldc=n_out, splits=splits,
+                      ws=P if splits > 1 else None, tile=tile, nb_o=int(key.rsplit("_b", 1)[1]))
+    return ops.gemm_accepts(d)
 
 
 def make_problem(sh):
@@ -181,32 +192,24 @@ for key, sh in sorted(shapes.items(), key=lambda kv: -kv[1]["count"] * kv[1]["M"
         continue
     M, N, K = sh["M"], sh["N"], sh["K"]
     geglu = bool(sh["epi"] & 1)
-    pipe_ok = K % 64 == 0 and (sh["c0"] + sh["c1"]) % 64 == 0 and sh["c0"] % 64 == 0
     cands = []
     for tile, (bm, bn) in TILE_DIMS.items():
-        if geglu and tile in NO_GEGLU:
+        if tile > 32 and M < bm:
             continue
-        if tile > 32 and (not pipe_ok or M < bm):
-            continue
-        if tile in PLAIN_ONLY and (sh["taps"] != 1 or sh["c1"] > 0):
-            continue
-        if (tile in PLAIN_ONLY or tile in PHASE) and not key.endswith("_b1"):
-            continue   # one matrix per launch: batched problems (the VAE's mid-block attention GEMMs) keep the older tiles
-        if tile in PHASE and (sh["c1"] > 0 or (sh["taps"] == 9 and (sh["stride"] != 1 or sh["ups"] != 0 or sh["hin"] != sh["hout"]))):
+        if tile in BATCHED_SKIP and not key.endswith("_b1"):
             continue
         wgs = -(-M // bm) * -(-N // bn)
         for sp in (1, 2, 3, 4, 6, 8, 12, 16):
             if sp > 1 and (K // 64 < 4 * sp or wgs * sp > 2048 or sp * M * N > (1 << 26)):
                 continue
-            if tile == 44 and sp > 1:
-                continue   # the 256 x 256 tile leaves through the LDS epilogue only (one split)
             if wgs * sp < (8 if N_STREAMS > 1 else 48) and sp < 16 and K // 64 >= 8 * sp:
                 continue   # hopelessly under-filled, a larger split exists (shared GPU: other sequences fill it)
-            cands.append((tile, sp))
+            if accepts(sh, key, tile, sp):
+                cands.append((tile, sp))
     only = os.environ.get("LGD_TUNE_ONLY_TILES")      # "44,45": try just these tiles against the entry the table holds
     if only:
         keep = {int(t) for t in only.split(",")}
-        cands = [(t, sp) for t, sp in cands if t in keep and (sp == 1 or t != 44)]
+        cands = [(t, sp) for t, sp in cands if t in keep]
         if not cands:
             if key in old_entries:
                 table[key] = old_entries[key]
