@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LGD_ABI_VERSION 11
+#define LGD_ABI_VERSION 12
 int lgd_abi_version(void);
 /* Kernel-variant switches of the library (A/B timing and tests; the defaults are what the benchmark runs).  No
  * counterpart in the reference.  "attn32": self-attention forward without map capture — 0 = the 16x16x32 kernel,
@@ -255,6 +255,22 @@ int lgd_cfg_ddim_step_f32(const float* eps, const float* x, float* x_out, const 
 int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, float* x0_prev,
                                const float* coef_table, const int32_t* dyn, const float* frozen_ref,
                                const float* mask, float* hist, int B, int C, int HW, void* stream);
+/* The same fused step for PLMS (ABI v12) — [ext] diffusers 0.18.0 PNDMScheduler with skip_prk_steps=True, the sampler of
+ * StableDiffusionPipeline for SD 1.5 / SD 2.1-base (generation/stable_diffusion_generate.py:13) driving the plain CFG loop
+ * of models/pipelines.py:257-273.  One launch per UNet evaluation k (n steps make n+1 evaluations: the second one is
+ * re-evaluated and averaged):
+ *   m = eu + gs*(ec-eu);
+ *   comb = w_m m + w_0 ets[0] + w_1 ets[1] + w_2 ets[2]          (PLMS weights 1; 1/2,1/2; 3/2,-1/2; 23/12,-16/12,5/12;
+ *                                                                 55/24,-59/24,37/24,-9/24 over the newest outputs)
+ *   if push >= 0: ets[push] = m                                   (ring of the last 3 pushed outputs; k = 1 does not push)
+ *   src = from_cur ? cur_sample : x;  if save_cur: cur_sample = x  (k = 0 saves, k = 1 restarts from it)
+ *   x' = a src + b comb;  hist[step+1] = x' when hist != NULL.  x_out may alias x.
+ * a, b fold PNDMScheduler._get_prev_sample (and, for v_prediction, m <- sqrt(a_t) m + sqrt(1-a_t) src) into one affine map.
+ * coef_table: device fp32 [E][16] = {w_m, w_0, w_1, w_2, a, b, guidance_scale, push slot (-1 = none), from_cur, save_cur,
+ * 0...} (host: scheduler.PNDMScheduler.plms_table); dyn: device int32 {evaluation index, ...}.
+ * ets: fp32 [3][B,C,L,L]; cur_sample: fp32 (B,C,L,L).  B*C*HW % 4 == 0 and 16-byte aligned buffers, else LGD_ERR_ARG. */
+int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
+                          const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW, void* stream);
 /* Model-input scaling of sigma-space samplers — [ext] diffusers EulerDiscreteScheduler.scale_model_input, which the
  * SDXL-refiner pass applies before every UNet call (generation/sdxl_refinement.py:29 -> StableDiffusionXLImg2ImgPipeline):
  *   out[r][i] = x[i] * table[dyn[0] * row_stride + col]   for r < reps   (reps = 2: the CFG pair reads one latent).

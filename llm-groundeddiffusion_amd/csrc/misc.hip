@@ -345,6 +345,46 @@ __global__ __launch_bounds__(256) void cfg_multistep_kernel(
   }
 }
 
+// Classifier-free guidance + one evaluation of PLMS ([ext] diffusers PNDMScheduler, skip_prk_steps): see lgd_hip.h.
+// Four fp32 lanes per thread (16-byte loads), grid-stride over n/4 vectors; everything that varies by evaluation is in
+// coefficient row dyn[0]:  {w_m, w_ring0, w_ring1, w_ring2, a, b, gs, push slot (-1: none), src = cur, save cur, ...}.
+// A ring slot is read only where its weight is non-zero, and written (push) after it was read.
+__global__ __launch_bounds__(256) void cfg_plms_kernel(
+    const float* __restrict__ eps, const float* x, float* x_out, float* __restrict__ ets,
+    float* __restrict__ cur, const float* __restrict__ coef_table, const int32_t* __restrict__ dyn,
+    float* __restrict__ hist, long n) {
+  const int step = dyn[0];
+  const float* c = coef_table + step * 16;
+  const float wm = c[0], w0 = c[1], w1 = c[2], w2 = c[3], A = c[4], Bc = c[5], gs = c[6];
+  const int push = (int)c[7];
+  const bool from_cur = c[8] != 0.f, save_cur = c[9] != 0.f;
+  const long nv = n >> 2;
+  const f32x4* eu4 = reinterpret_cast<const f32x4*>(eps);
+  const f32x4* ec4 = reinterpret_cast<const f32x4*>(eps + n);
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+  f32x4* r0 = reinterpret_cast<f32x4*>(ets);
+  f32x4* r1 = reinterpret_cast<f32x4*>(ets + n);
+  f32x4* r2 = reinterpret_cast<f32x4*>(ets + 2 * n);
+  f32x4* cur4 = reinterpret_cast<f32x4*>(cur);
+  for (long v = blockIdx.x * 256L + threadIdx.x; v < nv; v += gridDim.x * 256L) {
+    const f32x4 eu = eu4[v], ec = ec4[v];
+    const f32x4 m = eu + gs * (ec - eu);
+    f32x4 comb = wm * m;
+    if (w0 != 0.f) comb += w0 * r0[v];
+    if (w1 != 0.f) comb += w1 * r1[v];
+    if (w2 != 0.f) comb += w2 * r2[v];
+    if (push == 0) r0[v] = m;
+    else if (push == 1) r1[v] = m;
+    else if (push == 2) r2[v] = m;
+    const f32x4 xv = x4[v];
+    const f32x4 src = from_cur ? cur4[v] : xv;
+    if (save_cur) cur4[v] = xv;
+    const f32x4 xn = A * src + Bc * comb;
+    reinterpret_cast<f32x4*>(x_out)[v] = xn;
+    if (hist) reinterpret_cast<f32x4*>(hist + (long)(step + 1) * n)[v] = xn;
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                          const float* __restrict__ table,
                                                          const int32_t* __restrict__ dyn, int row_stride, int col,
@@ -508,6 +548,22 @@ extern "C" int lgd_cfg_multistep_step_f32(const float* eps, const float* x, floa
   hipLaunchKernelGGL(cfg_multistep_kernel, dim3(ew_blocks((long)B * C * HW)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), eps, x, x_out, x0_prev, coef_table, dyn, frozen_ref,
                      mask, hist, B, C * HW, HW);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
+                                     const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW,
+                                     void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (!eps || !x || !x_out || !ets || !cur_sample || !coef_table || !dyn || B < 1 || C < 1 || HW < 1)
+    return LGD_ERR_ARG;
+  const long n = (long)B * C * HW;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if ((n & 3) || misaligned(eps) || misaligned(x) || misaligned(x_out) || misaligned(ets) || misaligned(cur_sample) ||
+      misaligned(hist))
+    return LGD_ERR_ARG;  // 16-byte vectors: every plane starts on a vector boundary
+  hipLaunchKernelGGL(cfg_plms_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eps,
+                     x, x_out, ets, cur_sample, coef_table, dyn, hist, n);
   return lgd_check_launch();
 }
 

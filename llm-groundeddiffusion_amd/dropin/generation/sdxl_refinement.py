@@ -81,11 +81,13 @@ def init_synthetic(config="sdxl_refiner", device="cuda", seed=0):
 
 
 def refine(image, spec, refine_seed, refinement_step_ratio=0.5):
-    """sdxl_refinement.py:24-30.  image: uint8 [H, W, 3]; returns a PIL image like the reference."""
+    """sdxl_refinement.py:24-30.  image: uint8 [H, W, 3], or a PIL image (what the `sd` plugin returns,
+    generate.py:383); returns a PIL image like the reference."""
     if pipe is None:
         raise RuntimeError("call init() (or init_synthetic()) first")
     # sdxl_refinement.py:24-29: LANCZOS resize to 1024 x 1024, the layout's own negative prompt in front of the style list
-    resized = np.asarray(Image.fromarray(image).resize((REFINE_SIZE,) * 2, Image.LANCZOS))
+    src = image if isinstance(image, Image.Image) else Image.fromarray(image)
+    resized = np.asarray(src.resize((REFINE_SIZE,) * 2, Image.LANCZOS))
     text = dict(prompt=spec["prompt"], negative_prompt=", ".join([spec["extra_neg_prompt"], sdxl_negative_prompt]))
     if "sdxl_prompt_embeds" in spec:          # cached text side (no tokenizer / text tower offline)
         text.update(prompt_embeds=spec["sdxl_prompt_embeds"], pooled=spec["sdxl_pooled"])

@@ -4,8 +4,9 @@ return tuples, executed by lgd_amd.sampler.LMDSampler (captured hipGraphs of the
 Implemented: latent_backward_guidance :16-82, decode :117-127, generate_semantic_guidance :129-247,
 gligen_enable_fuser :280-283, prepare_gligen_condition :285-321, generate_gligen :323-473,
 generate_partial_frozen :541-599, and their `use_boxdiff=True` branch (:187-188, :564-565: one gradient step on the
-BoxDiff energy of utils/boxdiff.py per denoising step, csrc/boxdiff.hip).  Not on the hot path and not provided:
-encode / invert (DDIM inversion, unused by LMD / LMD+), generate (plain SD)."""
+BoxDiff energy of utils/boxdiff.py per denoising step, csrc/boxdiff.hip), and generate :250-279 (the plain CFG loop,
+under the DDIM, DPM-Solver++ or PNDM scheduler found at `model_dict[scheduler_key]`; PNDM runs the fused PLMS step of
+csrc/misc.hip).  Not on the hot path and not provided: encode / invert (DDIM inversion, unused by LMD / LMD+)."""
 import numpy as np
 import torch
 
@@ -254,3 +255,35 @@ def generate_partial_frozen(model_dict, latents_all, frozen_mask, input_embeddin
                    frozen_steps=frozen_steps, frozen_mask=frozen_mask, save_all_latents=False)
     images = decode(model_dict.vae, r["latents"]) if model_dict.vae is not None else None
     return r["latents"], images
+
+
+@torch.no_grad()
+def generate(model_dict, latents, input_embeddings, num_inference_steps, guidance_scale=7.5, no_set_timesteps=False,
+             scheduler_key='scheduler'):
+    """pipelines.py:250-279 -> (latents, images): classifier-free guidance with `model_dict[scheduler_key]` (DDIM,
+    DPMSolverMultistep or PNDM), every image of the batch an independent job of the sampler.  no_set_timesteps: the
+    scheduler's schedule as it stands is run; it must be the one set_timesteps(num_inference_steps it was set for)
+    produces, the only kind the sampler's tables express."""
+    from lgd_amd.pipeline import sd_generate_batch
+    sm = _sampler(model_dict)
+    scheduler = model_dict[scheduler_key]
+    text_embeddings, _, _ = input_embeddings
+    T = num_inference_steps
+    if no_set_timesteps:
+        if scheduler.timesteps is None:
+            raise RuntimeError("no_set_timesteps=True but the scheduler has no timesteps")
+        T = scheduler.num_inference_steps
+        as_set = scheduler.timesteps
+        scheduler.set_timesteps(T)
+        if not torch.equal(torch.as_tensor(as_set).cpu(), torch.as_tensor(scheduler.timesteps).cpu()):
+            scheduler.timesteps = as_set
+            raise NotImplementedError("no_set_timesteps with a hand-made schedule is outside the HIP path")
+    n = latents.shape[0]
+    texts = [torch.stack([text_embeddings[i], text_embeddings[n + i]]) for i in range(n)]
+    lat, _ = sd_generate_batch(sm, texts, latents.float(), T, guidance_scale=guidance_scale, scheduler=scheduler,
+                               decode=False)
+    if no_set_timesteps:
+        scheduler.set_timesteps(T)                  # the sampler consumed the schedule; leave it as it was found
+    lat = lat.to(latents.dtype)
+    images = decode(model_dict.vae, lat) if model_dict.vae is not None else None
+    return lat, images

@@ -689,6 +689,16 @@ def cfg_multistep_step(eps, x, x_out, x0_prev, coef_table, dyn, *, frozen_ref=No
     return x_out
 
 
+def cfg_plms_step(eps, x, x_out, ets, cur_sample, coef_table, dyn, *, hist=None):
+    """CFG + one PLMS evaluation (PNDMScheduler, skip_prk_steps); coef_table fp32 [E][16], ets fp32 [3, *x.shape],
+    see lgd_hip.h."""
+    B, C_, L, _ = x.shape
+    _prof("cfg_plms_kernel", 4.0 * x.numel() * 7,
+          lambda: _call("lgd_cfg_plms_step_f32", _p(eps), _p(x), _p(x_out), _p(ets), _p(cur_sample), _p(coef_table),
+                        _p(dyn), _p(hist), B, C_, L * L, _stream()))
+    return x_out
+
+
 def axpy(g, x, coef_table, step_idx, col, active=None):
     per = x.numel() // x.shape[0] if active is not None else 0
     _prof("axpy_kernel", 12.0 * x.numel(),

@@ -426,3 +426,29 @@ def boxdiff_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num
     images = sampler.decode(torch.cat([r["latents"] for r in res])) if decode else [None] * len(lays)
     return [dict(image=images[i], latents=r["latents"], guidance_iters=r["guidance_iters"], guidance_iters_fuser_on=0)
             for i, r in enumerate(res)]
+
+
+def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=50, guidance_scale=7.5, scheduler=None,
+                      decode=True, save_all_latents=False):
+    """Plain Stable Diffusion, the `sd` baseline (generation/stable_diffusion_generate.py -> StableDiffusionPipeline, whose
+    denoising loop is models/pipelines.py:257-273): classifier-free guidance and the checkpoint's own sampler, by default
+    PLMS (scheduler.PNDMScheduler.from_config of the sampler's scheduler; n steps = n + 1 UNet evaluations).  `scheduler`
+    may also be a DDIMScheduler / DPMSolverMultistepScheduler.  Independent images share UNet calls (denoise_batch:
+    up to max_batch per call, padded to the buckets).
+
+    texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor, already scaled
+    by init_noise_sigma.  Returns (final latents (N,C,L,L), uint8 images (N,8L,8L,3) from sampler.decode or None), plus
+    the per-image histories (E+1,1,C,L,L) with save_all_latents."""
+    from .scheduler import PNDMScheduler
+    sch = PNDMScheduler.from_config(sampler.scheduler) if scheduler is None else scheduler
+    starts = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
+    if len(starts) != len(texts):
+        raise ValueError(f"{len(texts)} texts for {len(starts)} latents")
+    jobs = [Job(torch.as_tensor(lat).float(), txt) for lat, txt in zip(starts, texts)]
+    res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, scheduler=sch,
+                                save_all_latents=save_all_latents)
+    lat = torch.cat([r["latents"] for r in res])
+    images = sampler.decode(lat) if decode else None
+    if save_all_latents:
+        return lat, images, [r["latents_all"] for r in res]
+    return lat, images

@@ -110,6 +110,17 @@ class _State:
         self.x0_prev = torch.zeros((nb, C, L, L), device=dev, dtype=F32)
         self.gtab = torch.zeros((T, 4), device=dev, dtype=F32)
         self.graphs = {}
+        self.ptab = self.ets = self.cur_sample = None                 # PLMS (PNDMScheduler): allocated on first use
+
+    def plms_buffers(self):
+        """Coefficient table, ring of the last three outputs and saved sample of lgd_cfg_plms_step_f32 (fixed addresses
+        for the graphs; only states that run PNDM carry them)."""
+        if self.ptab is None:
+            dev = self.lat.device
+            self.ptab = torch.zeros((self.ctab.shape[0], 16), device=dev, dtype=F32)
+            self.ets = torch.zeros((3,) + tuple(self.lat.shape), device=dev, dtype=F32)
+            self.cur_sample = torch.zeros_like(self.lat)
+        return self
 
 
 def plan_chunks(n: int, cap: int, buckets: Sequence[int], max_pad: float = 0.25) -> List[Tuple[int, int]]:
@@ -430,7 +441,7 @@ class LMDSampler:
                        frozen_steps: int = 0, saved_cross_attn_keys: Sequence[Tuple] = (),
                        return_cond_ca_only: bool = False, save_all_latents: bool = True,
                        trace: Optional[list] = None, fast_after_steps: Optional[int] = None, fast_rate: int = 2,
-                       first_step: int = 0, n_steps: Optional[int] = None):
+                       first_step: int = 0, n_steps: Optional[int] = None, scheduler=None):
         """Generic 50-step loop over a batch of independent images (one UNet call serves all of them:
         B = 2*len(jobs) for the CFG pass, len(jobs) for the guidance pass).
 
@@ -445,22 +456,34 @@ class LMDSampler:
         first_step / n_steps: run only steps first_step .. first_step + n_steps - 1 of the schedule, starting from
           the given latents (which then stand for the state BEFORE step first_step).  Used by the teacher-forced
           parity tests (one guided step from the reference's own latents of that step) and by partial schedules.
+        scheduler: this call's scheduler instead of the sampler's own — a PNDMScheduler runs the plain CFG loop of
+          pipelines.py:257-273 under PLMS, whose schedule has more UNet evaluations than steps (n + 1); the state, the
+          tables and the history then follow the evaluation count, and guidance, GLIGEN, frozen steps, the fast schedule
+          and first_step > 0 are refused.
         Returns per job dict(latents (1,C,L,L), latents_all (T_run+1,1,C,L,L), saved {key: [T_run,Bp,H,HW,Tp]},
         guidance_iters).
         """
-        eng, sch, dev = self.eng, self.scheduler, self.dev
+        eng, dev = self.eng, self.dev
+        sch = self.scheduler if scheduler is None else scheduler
         nb = len(jobs)
         starts = [j.latents[0] if j.latents.dim() == 5 else j.latents for j in jobs]
         _, C, L, _ = starts[0].shape
         T = num_inference_steps
-        st = self._state(nb, C, L, T)
         sch.set_timesteps(T)
         ts = sch.timesteps
+        st = self._state(nb, C, L, len(ts))                                  # evaluations: T, or T + 1 under PLMS
         if fast_after_steps is not None:
             ts = sch.fast_schedule(ts, int(fast_after_steps), int(fast_rate))
         Tr = len(ts)                                                          # steps actually run
         multistep = bool(getattr(sch, "multistep", False))
-        if multistep:
+        plms = bool(getattr(sch, "plms", False))
+        if plms:
+            if (fast_after_steps is not None or frozen_steps > 0 or use_gligen or int(first_step) > 0 or
+                    any(j.guidance is not None for j in jobs)):
+                raise RuntimeError("PNDMScheduler runs the plain CFG loop only (pipelines.py:257-273): guidance, GLIGEN, "
+                                   "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
+            st.plms_buffers().ptab[:Tr].copy_(sch.plms_table(guidance_scale, dev, timesteps=ts))
+        elif multistep:
             if fast_after_steps is not None:
                 raise RuntimeError("the fast schedule (utils/schedule.py) re-derives DDIM step sizes; not defined for the "
                                    "multistep scheduler")
@@ -519,13 +542,15 @@ class LMDSampler:
                 ops.copy_(plan.latents_in[:nb], st.lat)                      # torch.cat([latents]*2)
                 ops.copy_(plan.latents_in[nb:], st.lat)
                 plan.forward()
-                if multistep:
+                if plms:
+                    ops.cfg_plms_step(plan.eps_out, st.lat, st.lat, st.ets, st.cur_sample, st.ptab, eng.dyn, hist=st.hist)
+                elif multistep:
                     ops.cfg_multistep_step(plan.eps_out, st.lat, st.lat, st.x0_prev, st.mtab, eng.dyn,
                                            frozen_ref=st.frozen_ref, mask=st.mask, hist=st.hist)
                 else:
                     ops.cfg_ddim_step(plan.eps_out, st.lat, st.lat, st.ctab, eng.dyn, frozen_ref=st.frozen_ref,
                                       mask=st.mask, hist=st.hist)
-            runners_main[f] = (main_fn, ("main", f, tuple(plan_keys), multistep))
+            runners_main[f] = (main_fn, ("main", f, tuple(plan_keys), "plms" if plms else multistep))
         if guided:
             for f in {fuser_at(i) for i in range(min(max_guided, Tr))}:
                 runners_guide[f] = self._guide_runners(st, nb, L, f, gkeys)

@@ -183,6 +183,130 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         return out, x0
 
 
+class PNDMScheduler(DDIMScheduler):
+    """[ext] diffusers 0.18.0 PNDMScheduler with skip_prk_steps=True, set_alpha_to_one=False (epsilon and v_prediction):
+    the PLMS sampler that StableDiffusionPipeline.from_pretrained takes from the runwayml/stable-diffusion-v1-5 and
+    stabilityai/stable-diffusion-2-1-base checkpoints, i.e. what generation/stable_diffusion_generate.py:13 runs.
+    diffusers is absent from the sandbox: restated from the published algorithm (PLMS, Liu et al. 2022) and the 0.18.0
+    class, parity unpinned at this boundary; pinned against a line-for-line stateful restatement (tests/pndm_restate.py)
+    and, for a constant noise prediction, against DDIM (tests/test_sd_generate_cpu.py).
+
+    n steps make n+1 UNet evaluations: timesteps = (_t[:-1], _t[-2], _t[-1]) reversed with _t = arange(n) * (1000 // n)
+    + steps_offset; the second evaluation re-runs the first step from the saved sample with the average of both outputs.
+    Every evaluation is one affine update of (source sample, PLMS combination of the current output and a ring of the
+    last three pushed ones), so the device side is the fused `lgd_cfg_plms_step_f32` kernel reading one coefficient
+    row per evaluation (`plms_table`); one captured hipGraph replays every evaluation."""
+    plms = True
+    # PLMS weights over (newest, ..., oldest) outputs by history length (PNDMScheduler.step_plms)
+    ORDER_WEIGHTS = {1: (1.0,), 2: (1.5, -0.5), 3: (23 / 12, -16 / 12, 5 / 12),
+                     4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+    TABLE_COLS = 16
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
+                 prediction_type="epsilon", skip_prk_steps=True, set_alpha_to_one=False):
+        if not skip_prk_steps:
+            raise NotImplementedError("PNDMScheduler: only skip_prk_steps=True (PLMS) is implemented")
+        if set_alpha_to_one:
+            raise NotImplementedError("PNDMScheduler: only set_alpha_to_one=False (the SD 1.5 / 2.1-base value) is implemented")
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"PNDMScheduler: prediction_type {prediction_type!r}")
+        super().__init__(num_train_timesteps, beta_start, beta_end, steps_offset, prediction_type)
+        self.config.update(skip_prk_steps=True)
+        self.counter = 0
+        self._host = None
+
+    @classmethod
+    def from_config(cls, scheduler):
+        """The PNDM scheduler of an SD 1.5 / SD 2.1-base checkpoint next to `scheduler` (model_dict.scheduler): its betas,
+        train step count and prediction type, with steps_offset=1, set_alpha_to_one=False, skip_prk_steps=True."""
+        c = scheduler.config
+        return cls(c.num_train_timesteps, c.beta_start, c.beta_end, steps_offset=1, prediction_type=c.prediction_type)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        ratio = self.config.num_train_timesteps // num_inference_steps
+        t = (np.arange(0, num_inference_steps) * ratio).round().astype(np.int64) + self.config.steps_offset
+        plms = np.concatenate([t[:-1], t[-2:-1], t[-1:]])[::-1].copy()
+        self.timesteps = torch.from_numpy(plms)
+        self.counter = 0
+        self._host = None
+
+    def plms_rows(self, timesteps=None):
+        """Per evaluation k: (w_m, w_ring0, w_ring1, w_ring2, a, b, push slot, from_cur, save_cur) of
+            comb = w_m m + sum_s w_rings ets[s];  ets[push] = m;  x' = a (cur_sample if from_cur else x) + b comb.
+        The j-th push goes to ring slot j % 3, so the oldest output of a fourth-order step sits in the slot the
+        current one is pushed to (the kernel reads it first)."""
+        ts = [int(t) for t in (self.timesteps if timesteps is None else timesteps)]
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        rows, pushes = [], 0
+        for k, t in enumerate(ts):
+            prev = t - ratio
+            ring = [0.0, 0.0, 0.0]
+            push = -1
+            if k != 1:
+                push, pushes = pushes % 3, pushes + 1
+                w = self.ORDER_WEIGHTS[min(pushes, 4)]
+                wm = w[0]
+                for j, wj in enumerate(w[1:]):            # ets[-2], ets[-3], ets[-4] = pushes - 2, - 3, - 4
+                    ring[(pushes - 2 - j) % 3] = wj
+            else:                                        # the averaged re-evaluation of the first step
+                prev, t = t, t + ratio
+                wm, ring[0] = 0.5, 0.5
+            a_t = float(self.alphas_cumprod[t])
+            a_p = float(self.alphas_cumprod[prev]) if prev >= 0 else float(self.final_alpha_cumprod)
+            sc = (a_p / a_t) ** 0.5                          # PNDMScheduler._get_prev_sample
+            c = (a_p - a_t) / (a_t * (1 - a_p) ** 0.5 + (a_t * (1 - a_t) * a_p) ** 0.5)
+            if self.config.prediction_type == "v_prediction":
+                a, b = sc - c * (1 - a_t) ** 0.5, -c * a_t ** 0.5
+            else:
+                a, b = sc, -c
+            rows.append((wm, ring[0], ring[1], ring[2], a, b, push, 1.0 if k == 1 else 0.0, 1.0 if k == 0 else 0.0))
+        return rows
+
+    def plms_table(self, guidance_scale: float, device, timesteps=None) -> torch.Tensor:
+        """fp32 [E][16] = {w_m, w_ring0..2, a, b, guidance_scale, push slot, from_cur, save_cur, 0...} (lgd_hip.h)."""
+        rows = [[wm, w0, w1, w2, a, b, guidance_scale, float(p), fc, sv] + [0.0] * (self.TABLE_COLS - 10)
+                for wm, w0, w1, w2, a, b, p, fc, sv in self.plms_rows(timesteps)]
+        return torch.tensor(rows, dtype=torch.float32, device=device)
+
+    def host_state(self, like):
+        """Ring + saved sample of `step_host`, shaped like one sample."""
+        return dict(ets=[torch.zeros_like(like) for _ in range(3)], cur=torch.zeros_like(like))
+
+    def step_host(self, model_output, index, sample, state):
+        """Torch form of evaluation `index` in the table form the kernel runs (tests): updates `state` (host_state)
+        and returns the new sample."""
+        wm, w0, w1, w2, a, b, push, from_cur, save_cur = self.plms_rows()[index]
+        comb = wm * model_output
+        for s, w in enumerate((w0, w1, w2)):
+            if w != 0.0:
+                comb = comb + w * state["ets"][s]
+        if push >= 0:
+            state["ets"][push] = model_output.clone()
+        src = state["cur"] if from_cur else sample
+        if save_cur:
+            state["cur"] = sample.clone()
+        return a * src + b * comb
+
+    def step(self, model_output, timestep, sample):
+        """Stateful host form with PNDMScheduler.step's surface (evaluations in schedule order)."""
+        if self._host is None:
+            self._host = self.host_state(sample)
+
+        class _O:
+            pass
+        o = _O()
+        o.prev_sample = self.step_host(model_output, self.counter, sample, self._host)
+        self.counter += 1
+        return o
+
+    def coef_table(self, guidance_scale, device, timesteps=None, step_ratios=None):
+        raise RuntimeError("PNDMScheduler drives lgd_cfg_plms_step_f32 (plms_table)")
+
+    def prev_timestep(self, t, index=None):
+        raise RuntimeError("PNDMScheduler: the step of evaluation k is a row of plms_rows")
+
+
 class EulerDiscreteScheduler:
     """[ext] diffusers EulerDiscreteScheduler as the SDXL refiner configures it (scheduler_config of
     stabilityai/stable-diffusion-xl-refiner-1.0: scaled_linear betas 0.00085..0.012, 1000 train steps, timestep_spacing
