@@ -23,10 +23,14 @@ sandbox).  One process per GPU: started by the driver under torch.distributed.ru
 is given without a rendezvous in the environment — re-launched by this script itself the same way.  Rank 0
 builds the weights and RCCL-broadcasts the two weight arenas; there is no collective inside the step loop.
 
-Prints ONE JSON line (rank 0) with the contract's fields plus `roofline` (dominant kernel; per-launch HIP
-event timing) and, at N=1, `cpu_baseline`.  `ms_per_step` is the wall time of one timed step.  With `--dump-outputs DIR`
-it also writes what the last timed step computed on rank 0 as DIR/<field>.npy: the inputs are seeded, so two builds run
-with the same arguments can be compared output for output.
+Prints ONE JSON line (rank 0) with the contract's fields.  `ms_per_step` is the wall time of one timed step.  With
+`--dump-outputs DIR` it also writes what the last timed step computed on rank 0 as DIR/<field>.npy: the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, the outputs, the line.  `--full` adds what
+takes runs of its own after the timed region: `roofline` (dominant kernel; per-launch HIP event timing of an eager replay,
+also behind `--shape-profile`) and, at N=1, `cpu_baseline` (the CPU oracle port on the host).  Without `--full` the line
+carries `roofline: null` and no `cpu_baseline`.
 """
 import argparse
 import json
@@ -485,11 +489,15 @@ def main():
                          "stage of --workload lmd has 8: one call of 8 measured +5.8 %% over two of 4)")
     ap.add_argument("--min-layouts-per-lane", type=int, default=8,
                     help="lmd_v0.1: a lane is added per this many layouts of the rank's share (at most --lanes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: the per-kernel "
+                         "roofline replay and, at N = 1, the CPU baseline (--no-roofline / --no-cpu-baseline leave either out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline")
     ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: no roofline")
     ap.add_argument("--shape-profile", default=None, metavar="PATH",
-                    help="also write the per-launch-shape table of the roofline replay (ms / launches / TF/s per image) to PATH")
+                    help="--full: also write the per-launch-shape table of the roofline replay (ms / launches / TF/s per "
+                         "image) to PATH")
     ap.add_argument("--sam", action="store_true",
                     help="refine every per-box mask with SAM (sam-vit-base architecture, seeded random weights, "
                          "device-side processor) as real runs do; the default uses box masks (SURVEY.md 8d)")
@@ -506,6 +514,11 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.cpu_dryrun:
         ap.error("--dump-outputs needs the GPU path (no outputs are computed with --cpu-dryrun)")
+    if args.shape_profile and not args.full:
+        ap.error("--shape-profile needs --full (it is written by the roofline replay)")
+    # a plain run measures the headline figure alone: the roofline replay and the CPU baseline are --full only
+    args.no_roofline = args.no_roofline or not args.full
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
 
     if (args.gpus > 1 or args.spawn) and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn(args.gpus))
@@ -601,7 +614,7 @@ def main():
     from lgd_amd.sampler import LMDSampler
     from lgd_amd.scheduler import DDIMScheduler
     from lgd_amd.unet import UNetEngine
-    from lgd_amd.vae import make_hip_vae
+    from lgd_amd.vae import HipVAEDecoder, synth_aekl_state_dict
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if world > 1 or args.spawn:
@@ -627,9 +640,12 @@ def main():
                     prm.normal_(0.0, 0.02)
         return SamRefiner(wrap_sam(hf_sam, "device", device=dev), height=side, width=side)
 
+    # every lane decodes with its own copy of the same seeded VAE (vae.make_hip_vae): the weights are synthesised once
+    vae_sd = None if args.no_decode else synth_aekl_state_dict(seed=0)
+
     def make_sampler(e):
         return LMDSampler(e, DDIMScheduler(prediction_type=cfg.prediction_type),
-                          vae=None if args.no_decode else make_hip_vae(dev), max_batch=mb, max_batch_guided=mbg)
+                          vae=None if args.no_decode else HipVAEDecoder(vae_sd, dev), max_batch=mb, max_batch_guided=mbg)
 
     # lanes: independent pipelines on their own HIP streams sharing one copy of the weights; with one lane this is
     # the plain sequential loop on a side stream

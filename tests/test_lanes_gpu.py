@@ -102,3 +102,30 @@ def test_bench_self_spawn_path_with_rccl_on_one_gpu():
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1 and line["value"] > 0
     assert line["config"]["weight_broadcast_s"] > 0.0                    # the collectives were really issued
     assert len(line["config"]["per_rank_busy_s"]) == 1
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_roofline(tmp_path):
+    """A plain `bench.py` run prints the headline line alone (no roofline replay, no CPU baseline); `--full` adds the
+    roofline of the eager replay after the timed region, and writes the `--shape-profile` table it feeds."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+            "--num-inference-steps", "2", "--layouts", "1", "--lanes", "1", "--no-decode"]
+    shapes = tmp_path / "shapes.json"
+    lines = []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--shape-profile", str(shapes)]):
+        r = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    plain, full = lines
+    for line in lines:
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "images/s" and line["dtype"] == "fp16"
+    assert plain["roofline"] is None and "cpu_baseline" not in plain
+    assert full["roofline"]["kernel"] and full["roofline"]["all_kernels"] and "cpu_baseline" not in full
+    assert json.loads(shapes.read_text())

@@ -16,9 +16,9 @@ prof() { # tag, bench args...
   rm -rf $OUT/$tag
   cut -c1-200 $OUT/${tag}_bench_line.json
 }
-prof ${R}_bench_lanes1 --lanes 1 --steps 1 --warmup 1 --no-cpu-baseline
+prof ${R}_bench_lanes1 --lanes 1 --steps 1 --warmup 1 --full --no-cpu-baseline
 prof ${R}_bench_driver --steps 4 --warmup 1 --no-cpu-baseline --no-roofline
-prof ${R}_lmd_lanes1 --workload lmd --lanes 1 --steps 1 --warmup 0 --no-cpu-baseline
+prof ${R}_lmd_lanes1 --workload lmd --lanes 1 --steps 1 --warmup 0 --full --no-cpu-baseline
 TAG=$R/traffic bash $ROOT/tools/bench_traffic.sh > $OUT/traffic.log 2>&1
 cp $OUT/traffic/bench_traffic_pmc.json $OUT/${R}_bench_traffic_pmc.json 2>/dev/null
 rm -rf $OUT/traffic/FETCH_SIZE $OUT/traffic/WRITE_SIZE

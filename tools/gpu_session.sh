@@ -115,20 +115,20 @@ PY
       timeout 900 python bench.py "$@" > $OUT/$n.log 2>&1
       grep '^{' $OUT/$n.log | tail -1 > $OUT/${T}_${n}_bench_line.json; echo "$n: $(cut -c1-150 $OUT/${T}_${n}_bench_line.json)"
     }
-    line bench_driver_command --gpus 1 --steps 20 --warmup 5
-    line bench_default
-    line lmd --workload lmd --steps 8 --warmup 2
+    line bench_driver_command --gpus 1 --steps 20 --warmup 5 --full
+    line bench_default --full
+    line lmd --workload lmd --steps 8 --warmup 2 --full
     line lmd_v0.1_100prompts --workload lmd_v0.1 --prompts 100 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline
     line lmd_v0.1_400prompts --workload lmd_v0.1 --prompts 400 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline
-    line backward_guidance_sd21 --workload backward_guidance --steps 4 --warmup 1 --no-cpu-baseline
-    line sdxl_refiner --workload sdxl_refiner --steps 2 --warmup 1 --no-cpu-baseline ;;
+    line backward_guidance_sd21 --workload backward_guidance --steps 4 --warmup 1 --full --no-cpu-baseline
+    line sdxl_refiner --workload sdxl_refiner --steps 2 --warmup 1 --full --no-cpu-baseline ;;
   baseline)   # args: TAG; GPU suite + the driver's command + one launch sequence alone with the per-shape profile
     T=${1:-r06}
     timeout 1500 python -m pytest tests -q -m gpu -rP > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"
     grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -n 3
-    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/driver.log 2>&1
+    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/driver.log 2>&1
     grep '^{' $OUT/driver.log | tail -1 > $OUT/${T}_bench_driver_command_bench_line.json; echo "driver: $(cut -c1-150 $OUT/${T}_bench_driver_command_bench_line.json)"
-    timeout 600 python bench.py --lanes 1 --steps 4 --warmup 1 --no-cpu-baseline --shape-profile $OUT/${T}_shape_profile.json > $OUT/lanes1.log 2>&1
+    timeout 600 python bench.py --lanes 1 --steps 4 --warmup 1 --full --no-cpu-baseline --shape-profile $OUT/${T}_shape_profile.json > $OUT/lanes1.log 2>&1
     grep '^{' $OUT/lanes1.log | tail -1 > $OUT/${T}_bench_lanes1_bench_line.json; echo "lanes1: $(cut -c1-150 $OUT/${T}_bench_lanes1_bench_line.json)" ;;
   phase_abl)  # ablation of the phase-split GEMM tiles (46, 47) on big shapes: builds the -DLGD_GEMM_ABLATION library on the box
     python llm-groundeddiffusion_amd/build.py --force > $OUT/build.log 2>&1
@@ -149,7 +149,7 @@ PY
       grep '^{' $OUT/$tag.log | tail -1 > $OUT/${tag}_bench_line.json
       f=$(find $OUT/$tag -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/${tag}_kernel_stats.csv
       rm -rf $OUT/$tag; cut -c1-160 $OUT/${tag}_bench_line.json; }
-    prof ${T}_bench_lanes1 --lanes 1 --steps 1 --warmup 1 --no-cpu-baseline
+    prof ${T}_bench_lanes1 --lanes 1 --steps 1 --warmup 1 --full --no-cpu-baseline
     prof ${T}_bench_driver --steps 4 --warmup 1 --no-cpu-baseline --no-roofline
     TAG=evidence/traffic bash $R/tools/bench_traffic.sh > $OUT/traffic.log 2>&1
     cp $OUT/traffic/bench_traffic_pmc.json $OUT/${T}_bench_traffic_pmc.json 2>/dev/null
