@@ -271,6 +271,25 @@ int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, f
  * ets: fp32 [3][B,C,L,L]; cur_sample: fp32 (B,C,L,L).  B*C*HW % 4 == 0 and 16-byte aligned buffers, else LGD_ERR_ARG. */
 int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
                           const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW, void* stream);
+/* One MultiDiffusion step (additive export: LGD_ABI_VERSION stays 12) — generation/multidiffusion.py:226-289 of the
+ * reference with its single 512x512 view, indep_uncond=True and normalization=False (count == 1), DDIM eta 0.  P region
+ * prompts (row 0 the background), padded to Pp UNet rows; one launch after the UNet of step i = dyn[0]:
+ *   d_k = DDIM(x_k, eu_k + gs*(ec_k - eu_k))    for k < P     (x_k = x_in row k: what the UNet consumed)
+ *   latent = sum_k masks[k] * d_k                (prompt order);  hist[i+1] = latent when hist != NULL
+ * and, when i+1 < n_steps, writes step i+1's UNet input, both CFG halves (x_in rows k and Pp+k, k < Pp):
+ *   x_k = latent, and for 1 <= k < P while i+1 < n_boot:  b = (masks[k] >= 0.5),
+ *   x_k = latent*b + (sqrt(a)*bg[picks[i+1][k-1]] + sqrt(1-a)*noise)*(1-b),  a = coef_table[i+1][0]
+ *   (DDIMScheduler.add_noise at timestep t_{i+1}).
+ * prep = 1 writes step dyn[0]'s input rows from `latent` only (once per run, before the first UNet call).
+ * eps: fp32 [2Pp][C][HW] = [uncond rows; cond rows]; x_in: fp32 [2Pp][C][HW]; latent, noise: fp32 [C][HW];
+ * masks: fp32 [>= P][HW] (broadcast over channels); bg: fp32 [n_boot][C][HW]; picks: device int32 [n_steps][P-1]
+ * (rows >= n_boot unused; indices clamped to [0, n_boot)); coef_table: lgd_cfg_ddim_step_f32's fp32 [n_steps][4]
+ * {alpha_bar_t, alpha_bar_prev, guidance_scale, v_pred}; dyn: device int32 {step, ...}.  HW % 4 == 0 and 16-byte
+ * aligned buffers, else LGD_ERR_ARG. */
+int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float* latent, const float* masks, const float* bg,
+                                const float* noise, const int32_t* picks, const float* coef_table, const int32_t* dyn,
+                                float* hist, int P, int Pp, int C, int HW, int n_steps, int n_boot, int prep,
+                                void* stream);
 /* Model-input scaling of sigma-space samplers — [ext] diffusers EulerDiscreteScheduler.scale_model_input, which the
  * SDXL-refiner pass applies before every UNet call (generation/sdxl_refinement.py:29 -> StableDiffusionXLImg2ImgPipeline):
  *   out[r][i] = x[i] * table[dyn[0] * row_stride + col]   for r < reps   (reps = 2: the CFG pair reads one latent).

@@ -385,6 +385,93 @@ __global__ __launch_bounds__(256) void cfg_plms_kernel(
   }
 }
 
+// One MultiDiffusion step over P region prompts (generation/multidiffusion.py of the reference, one 512x512 view,
+// indep_uncond, no normalization): see lgd_hip.h.  Four fp32 lanes of one latent plane per thread (16-byte accesses;
+// HW % 4 == 0, so the four lanes share one mask row), one wave per workgroup so that the 16K-element SD latent spreads
+// over 64 CUs.  A thread reads x_k (the UNet input rows it wrote one step earlier) and the CFG pair of every prompt in
+// prompt order and owns its output elements: no atomics, deterministic.  The DDIM arithmetic is cfg_ddim_kernel's,
+// lane by lane, so that one prompt with mask 1 reproduces the plain CFG + DDIM step bit for bit.
+__device__ __forceinline__ float md_ddim(float eu, float ec, float xv, float gs, bool vpred, float sa, float sb,
+                                         float pa, float pb) {
+  float m = eu + gs * (ec - eu);
+  float x0, e;
+  if (vpred) {
+    x0 = sa * xv - sb * m;
+    e = sa * m + sb * xv;
+  } else {
+    e = m;
+    x0 = (xv - sb * e) / sa;
+  }
+  return pa * x0 + pb * e;
+}
+
+__global__ __launch_bounds__(64) void multidiffusion_step_kernel(
+    const float* __restrict__ eps, float* __restrict__ x_in, float* __restrict__ latent,
+    const float* __restrict__ masks, const float* __restrict__ bg, const float* __restrict__ noise,
+    const int32_t* __restrict__ picks, const float* __restrict__ coef_table, const int32_t* __restrict__ dyn,
+    float* __restrict__ hist, int P, int Pp, int HW, long n, int n_steps, int n_boot, int prep) {
+  const int step = dyn[0];
+  if (step < 0 || step >= n_steps) return;
+  const long v = blockIdx.x * 64L + threadIdx.x;
+  if (v >= (n >> 2)) return;
+  const long e = v << 2;
+  const long p = e % HW;
+  f32x4 acc;
+  int next = step;
+  if (prep) {
+    acc = reinterpret_cast<const f32x4*>(latent)[v];
+  } else {
+    const float* c = coef_table + step * 4;
+    const float a_t = c[0], a_p = c[1], gs = c[2];
+    const bool vpred = c[3] != 0.f;
+    const float sa = sqrtf(a_t), sb = sqrtf(1.f - a_t), pa = sqrtf(a_p), pb = sqrtf(1.f - a_p);
+    for (int k = 0; k < P; ++k) {
+      const f32x4 eu = reinterpret_cast<const f32x4*>(eps + (long)k * n)[v];
+      const f32x4 ec = reinterpret_cast<const f32x4*>(eps + (long)(Pp + k) * n)[v];
+      const f32x4 xv = reinterpret_cast<const f32x4*>(x_in + (long)k * n)[v];
+      const f32x4 mk = *reinterpret_cast<const f32x4*>(masks + (long)k * HW + p);
+      f32x4 d;
+      d.x = md_ddim(eu.x, ec.x, xv.x, gs, vpred, sa, sb, pa, pb);
+      d.y = md_ddim(eu.y, ec.y, xv.y, gs, vpred, sa, sb, pa, pb);
+      d.z = md_ddim(eu.z, ec.z, xv.z, gs, vpred, sa, sb, pa, pb);
+      d.w = md_ddim(eu.w, ec.w, xv.w, gs, vpred, sa, sb, pa, pb);
+      acc = k == 0 ? mk * d : acc + mk * d;
+    }
+    reinterpret_cast<f32x4*>(latent)[v] = acc;
+    if (hist) reinterpret_cast<f32x4*>(hist + (long)(step + 1) * n)[v] = acc;
+    next = step + 1;
+  }
+  if (next >= n_steps) return;
+  // UNet input of step `next`: torch.cat([x_0 .. x_{Pp-1}] * 2), rows 1..P-1 bootstrapped while next < n_boot
+  const bool boot = next < n_boot && P > 1;
+  float sa = 0.f, sb = 0.f;
+  f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+  if (boot) {
+    const float a_n = coef_table[next * 4];
+    sa = sqrtf(a_n);
+    sb = sqrtf(1.f - a_n);
+    nz = reinterpret_cast<const f32x4*>(noise)[v];
+  }
+  for (int k = 0; k < Pp; ++k) {
+    f32x4 x = acc;
+    if (boot && k >= 1 && k < P) {
+      int pk = picks[(long)next * (P - 1) + (k - 1)];
+      pk = pk < 0 ? 0 : (pk >= n_boot ? n_boot - 1 : pk);
+      const f32x4 g = reinterpret_cast<const f32x4*>(bg + (long)pk * n)[v];
+      const f32x4 mk = *reinterpret_cast<const f32x4*>(masks + (long)k * HW + p);
+      f32x4 b;
+      b.x = mk.x >= 0.5f ? 1.f : 0.f;
+      b.y = mk.y >= 0.5f ? 1.f : 0.f;
+      b.z = mk.z >= 0.5f ? 1.f : 0.f;
+      b.w = mk.w >= 0.5f ? 1.f : 0.f;
+      const f32x4 noisy = sa * g + sb * nz;                   // DDIMScheduler.add_noise(bg, noise, t_next)
+      x = acc * b + noisy * (1.f - b);
+    }
+    reinterpret_cast<f32x4*>(x_in + (long)k * n)[v] = x;
+    reinterpret_cast<f32x4*>(x_in + (long)(Pp + k) * n)[v] = x;
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                          const float* __restrict__ table,
                                                          const int32_t* __restrict__ dyn, int row_stride, int col,
@@ -564,6 +651,27 @@ extern "C" int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_
     return LGD_ERR_ARG;  // 16-byte vectors: every plane starts on a vector boundary
   hipLaunchKernelGGL(cfg_plms_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eps,
                      x, x_out, ets, cur_sample, coef_table, dyn, hist, n);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float* latent, const float* masks,
+                                           const float* bg, const float* noise, const int32_t* picks,
+                                           const float* coef_table, const int32_t* dyn, float* hist, int P, int Pp,
+                                           int C, int HW, int n_steps, int n_boot, int prep, void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (!x_in || !latent || !masks || !coef_table || !dyn || P < 1 || Pp < P || C < 1 || HW < 1 || n_steps < 1 ||
+      n_boot < 0 || (prep != 0 && prep != 1) || (!prep && !eps))
+    return LGD_ERR_ARG;
+  if (n_boot > 0 && P > 1 && (!bg || !noise || !picks)) return LGD_ERR_ARG;
+  const long n = (long)C * HW;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if ((HW & 3) || misaligned(eps) || misaligned(x_in) || misaligned(latent) || misaligned(masks) || misaligned(bg) ||
+      misaligned(noise) || misaligned(hist))
+    return LGD_ERR_ARG;  // 16-byte vectors: every plane and mask row starts on a vector boundary
+  const long nv = n / 4;
+  hipLaunchKernelGGL(multidiffusion_step_kernel, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), eps, x_in, latent, masks, bg, noise, picks, coef_table,
+                     dyn, hist, P, Pp, HW, n, n_steps, n_boot, prep);
   return lgd_check_launch();
 }
 

@@ -1,0 +1,86 @@
+"""generation/multidiffusion.py of the reference: plugin `multidiffusion`, the MultiDiffusion region-prompt baseline
+(`generate.py --run-model multidiffusion`), on the HIP engine (lgd_amd.multidiffusion).
+
+generate.py does not call models.load_sd for this method (it is one of its `custom_models`): the reference builds its
+own networks from `models.sd_key` at import.  Here `init()` builds them from the same key through models.load_sd (it
+needs diffusers and the checkpoint), `init_synthetic()` builds seeded random networks of the same architecture, and
+`run()` calls `init()` the first time when neither was called.
+
+Only what run() can reach is served: one 512 x 512 view, indep_uncond, no normalization, DDIM.  The image is converted
+like the reference's T.ToPILImage (truncating), not rounded like the other plugins'."""
+from PIL import Image
+
+import models
+from lgd_amd import multidiffusion as md_core
+
+from ._common import EasyDict
+
+version = "multidiffusion"
+
+bg_negative = "artifacts, blurry, smooth texture, bad quality, distortions, unrealistic, distorted image, bad proportions, duplicate, headshot, close-up, partial, large, large, huge, gigantic"
+fg_negative_prompt = "artifacts, blurry, smooth texture, bad quality, distortions, unrealistic, distorted image, bad proportions, duplicate, headshot, close-up, partial, large, large, huge, gigantic, cut-out, partial, occluded, weird"
+
+sd_kw = dict(H=512, W=512)
+
+sd = None          # EasyDict(sampler, encoder, tokenizer, text_encoder, device) once init() / init_synthetic() ran
+
+
+def init(device="cuda"):
+    """Builds the networks of models.sd_key (generation/multidiffusion.py:353-356): UNet, text tower and VAE decoder
+    through models.load_sd, the VAE encoder of the same checkpoint on the HIP kernels."""
+    global sd
+    try:
+        from diffusers import AutoencoderKL
+    except ImportError as e:
+        raise RuntimeError("generation.multidiffusion.init() loads models.sd_key through diffusers, which is not "
+                           "installed here; use init_synthetic() for seeded random weights") from e
+    if not models.sd_key:
+        raise RuntimeError("models.sd_key is not set (generate.py sets it before importing the plugin)")
+    from lgd_amd.vae import HipVAEEncoder
+    md = models.load_sd(models.sd_key)
+    vae = AutoencoderKL.from_pretrained(models.sd_key, subfolder="vae")
+    sd = EasyDict(sampler=md.sampler, encoder=HipVAEEncoder(vae.state_dict(), device), tokenizer=md.tokenizer,
+                  text_encoder=md.text_encoder, device=device)
+    return sd
+
+
+def init_synthetic(name="sd15", seed=0, device="cuda", tokenizer=None, text_encoder=None):
+    """Offline stand-in for init(): the UNet config `name` and the SD VAE with seeded random parameters (the decoder
+    and encoder of one seeded AutoencoderKL state dict).  There is no tokenizer or text tower offline: pass stand-ins."""
+    global sd
+    from lgd_amd import vae as _vae
+    md = models.load_synthetic(name, seed=seed, device=device, with_vae=False)
+    state = _vae.synth_aekl_state_dict(seed=seed)
+    md.sampler.vae = _vae.HipVAEDecoder(state, device)
+    sd = EasyDict(sampler=md.sampler, encoder=_vae.HipVAEEncoder(state, device), tokenizer=tokenizer,
+                  text_encoder=text_encoder, device=device)
+    return sd
+
+
+def run(gen_boxes, bg_prompt, original_ind_base=None, bootstrapping=20, generate_kw=None, first_top=False, steps=50,
+        guidance_scale=10.0, extra_neg_prompt=""):
+    """generation/multidiffusion.py:383-451 -> EasyDict(image=<PIL.Image>)."""
+    if generate_kw:
+        # the reference passes every key of generate() explicitly and spreads generate_kw after them: any key is a
+        # "got multiple values for keyword argument" TypeError there
+        raise TypeError(f"generate() got multiple values for keyword argument '{next(iter(generate_kw))}'")
+    if sd is None:
+        init()
+    if sd.tokenizer is None or sd.text_encoder is None:
+        raise RuntimeError("no tokenizer / text encoder: init_synthetic() needs stand-ins for them")
+    print(f"gen_boxes = {gen_boxes}")
+    print(f'bg_prompt = "{bg_prompt}"')
+    print(f'extra_neg_prompt = "{extra_neg_prompt}"')
+    prep = md_core.prepare(gen_boxes, bg_prompt, bg_negative, fg_negative_prompt, extra_neg_prompt=extra_neg_prompt,
+                           first_top=first_top)
+    P = len(prep["prompts"])
+    if original_ind_base is None:
+        raise TypeError("original_ind_base (the seed) is required: the reference seeds generate() with it")
+    draws = md_core.draw_randomness(sd.encoder, sd.device, original_ind_base, bootstrapping, P, steps,
+                                    in_channels=sd.sampler.eng.cfg.in_channels, size=(sd_kw["H"], sd_kw["W"]))
+    texts = md_core.encode_texts(sd.tokenizer, sd.text_encoder, prep["prompts"], prep["negative_prompts"], sd.device)
+    out = md_core.multidiffusion_generate(sd.sampler, texts, prep["masks"], draws["start_latent"], draws["bg_latents"],
+                                          draws["picks"], steps=steps, guidance_scale=guidance_scale,
+                                          n_boot=bootstrapping)
+    return EasyDict(image=Image.fromarray(out["image"]))
+

@@ -699,6 +699,19 @@ def cfg_plms_step(eps, x, x_out, ets, cur_sample, coef_table, dyn, *, hist=None)
     return x_out
 
 
+def multidiffusion_step(eps, x_in, latent, masks, coef_table, dyn, *, n_prompts, n_steps, bg=None, noise=None,
+                        picks=None, n_boot=0, hist=None, prep=False):
+    """One MultiDiffusion step (CFG + P DDIM steps + masked sum) and the next step's UNet input rows, or with prep=True
+    only the input rows of step dyn[0] from `latent`; x_in / eps fp32 (2Pp, C, L, L), see lgd_hip.h."""
+    Pp2, C_, L, _ = x_in.shape
+    P = int(n_prompts)
+    _prof("multidiffusion_step_kernel", 4.0 * latent.numel() * (2 + (0 if prep else 3 * P) + Pp2),
+          lambda: _call("lgd_multidiffusion_step_f32", _p(None if prep else eps), _p(x_in), _p(latent), _p(masks),
+                        _p(bg), _p(noise), _p(picks), _p(coef_table), _p(dyn), _p(hist), P, Pp2 // 2, C_, L * L,
+                        int(n_steps), int(n_boot), 1 if prep else 0, _stream()))
+    return latent
+
+
 def axpy(g, x, coef_table, step_idx, col, active=None):
     per = x.numel() // x.shape[0] if active is not None else 0
     _prof("axpy_kernel", 12.0 * x.numel(),

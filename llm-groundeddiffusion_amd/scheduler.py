@@ -81,6 +81,20 @@ class DDIMScheduler:
             rows.append([a_t, a_p, guidance_scale, 1.0 if self.config.prediction_type == "v_prediction" else 0.0])
         return torch.tensor(rows, dtype=torch.float32, device=device)
 
+    def add_noise(self, original, noise, timestep):
+        """[ext] diffusers 0.18.0 DDIMScheduler.add_noise: sqrt(alpha_bar_t) * original + sqrt(1 - alpha_bar_t) * noise,
+        alpha_bar_t in the samples' dtype (the background bootstrapping of generation/multidiffusion.py:245-247; the
+        device form is lgd_multidiffusion_step_f32).  timestep: int, or a tensor of one per sample."""
+        ac = self.alphas_cumprod.to(device=original.device, dtype=original.dtype)
+        t = torch.as_tensor(timestep, device=original.device).long()
+        sqrt_alpha_prod = (ac[t] ** 0.5).flatten()
+        while sqrt_alpha_prod.dim() < original.dim():
+            sqrt_alpha_prod = sqrt_alpha_prod.unsqueeze(-1)
+        sqrt_one_minus_alpha_prod = ((1 - ac[t]) ** 0.5).flatten()
+        while sqrt_one_minus_alpha_prod.dim() < original.dim():
+            sqrt_one_minus_alpha_prod = sqrt_one_minus_alpha_prod.unsqueeze(-1)
+        return sqrt_alpha_prod * original + sqrt_one_minus_alpha_prod * noise
+
     def guidance_step_table(self, device, timesteps=None) -> torch.Tensor:
         """fp32 [T][4] with column 0 = sqrt(1 - alpha_bar_t): DDIM has no `sigmas`, so the latent
         update of backward guidance is scaled this way (pipelines.py:62-69)."""
