@@ -19,7 +19,8 @@ Process-wide state the lanes do share, and how it is kept safe:
     (a pageable host-to-device copy failed with "operation not permitted when stream is capturing" even under
     capture_error_mode="thread_local"), so a capture is an exclusive section: `GATE.exclusive()` waits until every
     other lane is parked at a `GATE.checkpoint()` (the samplers call it once per denoising step and guidance
-    iteration) or between jobs, and holds them there until the graph exists (`sampler.HipGraph`);
+    iteration: `loop.run_steps`, `LMDSampler.backward_guidance`) or between jobs, and holds them there until the
+    graph exists (`loop.HipGraph`, also importable as `sampler.HipGraph`);
   * split-K scratch of calls that bring none — thread-local (`ops.workspace`);
   * the interpreter lock: a lane that comes back from a device wait must not sit out CPython's default 5 ms switch
     interval behind the other lane's host code (65 guidance syncs per image) — the pool lowers it to 0.2 ms.

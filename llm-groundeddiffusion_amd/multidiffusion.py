@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .lanes import GATE
+from .loop import LoopState, clamp_steps, run_steps
 from .scheduler import DDIMScheduler
 
 F32 = torch.float32
@@ -189,19 +189,18 @@ def decode_truncating(vae, latent):
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------
-class _MDState:
+class _MDState(LoopState):
     """Persistent buffers of one (prompts, padded rows, latent shape, steps, bootstrapping): fixed addresses for the
     captured graph, allocated with torch and not in the engine's activation arena (plans alias each other there)."""
 
     def __init__(self, dev, P, Pp, C, L, T, n_boot):
-        self.lat = torch.zeros((C, L, L), device=dev, dtype=F32)
+        super().__init__(torch.zeros((C, L, L), device=dev, dtype=F32), T)
         self.noise = torch.zeros((C, L, L), device=dev, dtype=F32)
         self.masks = torch.zeros((Pp, L * L), device=dev, dtype=F32)
         self.bg = torch.zeros((max(n_boot, 1), C, L, L), device=dev, dtype=F32)
         self.picks = torch.zeros((T, max(P - 1, 1)), device=dev, dtype=torch.int32)
         self.ctab = torch.zeros((T, 4), device=dev, dtype=F32)
         self.hist = torch.zeros((T + 1, C, L, L), device=dev, dtype=F32)
-        self.graph = None
 
 
 def _ddim_of(sampler):
@@ -260,14 +259,7 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
             raise ValueError("picks index the n_boot backgrounds")
     Pp = padded_rows(sampler, P)
 
-    key = (P, Pp, C, L, T, n_boot)
-    states = sampler.__dict__.setdefault("_md_states", {})
-    st = states.pop(key, None)
-    if st is None:
-        st = _MDState(dev, P, Pp, C, L, T, n_boot)
-    states[key] = st
-    while len(states) > 4:
-        states.pop(next(iter(states)))
+    st = sampler.md_states.get((P, Pp, C, L, T, n_boot), lambda: _MDState(dev, P, Pp, C, L, T, n_boot))
 
     # ---- per-run constants (before graph capture so that the capture's warm-up launch sees valid inputs)
     st.ctab.copy_(sch.coef_table(guidance_scale, dev, timesteps=ts))
@@ -283,13 +275,7 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
         plan.forward()
         ops.multidiffusion_step(plan.eps_out, plan.latents_in, st.lat, st.masks, st.ctab, eng.dyn, n_prompts=P,
                                 n_steps=T, bg=st.bg, noise=st.noise, picks=st.picks, n_boot=n_boot, hist=st.hist)
-    if sampler.use_graphs:
-        if st.graph is None:
-            from .sampler import HipGraph
-            st.graph = HipGraph(step_fn)
-        runner = st.graph
-    else:
-        runner = step_fn
+    runner = st.runner("step", step_fn, sampler.use_graphs)
 
     # ---- state of this call
     st.masks.zero_()
@@ -300,20 +286,19 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
         st.bg.copy_(bg_latents.to(dev, F32))
         if n_pick:
             st.picks[:n_pick].copy_(picks[:n_pick].to(dev, torch.int32))
-    first_step = max(0, min(int(first_step), T))
-    last_step = T if n_steps is None else min(T, first_step + int(n_steps))
+    first_step, last_step = clamp_steps(first_step, n_steps, T)
     st.hist[first_step].copy_(st.lat)
     inputs = []
     if first_step < T:
         eng.set_step(first_step)
         ops.multidiffusion_step(None, plan.latents_in, st.lat, st.masks, st.ctab, eng.dyn, n_prompts=P, n_steps=T,
                                 bg=st.bg, noise=st.noise, picks=st.picks, n_boot=n_boot, prep=True)
-    for index in range(first_step, last_step):
-        GATE.checkpoint()                                                 # lanes.py
-        eng.set_step(index)
+
+    def one_step(index):
         if record_inputs:
             inputs.append(plan.latents_in[:P].clone())
         runner()
+    run_steps(eng, first_step, last_step, one_step)
     lat = st.lat.reshape(1, C, L, L).clone()
     image = decode_truncating(sampler.vae, lat)[0] if decode else None
     return dict(latent=lat, image=image, inputs=inputs,

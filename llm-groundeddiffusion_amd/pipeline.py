@@ -15,7 +15,11 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .sampler import DEFAULT_GUIDANCE_ATTN_KEYS, Job, LMDSampler, prepare_gligen_condition
+from .hostprep import (align_with_bboxes, compose as compose_latents, get_centered_box,
+                       input_latents_list as _input_latents_list, proportion_to_mask, seeded_noise, shift_tensor)
+from .sampler import (BOXDIFF_GUIDANCE_ATTN_KEYS, DEFAULT_GUIDANCE_ATTN_KEYS, Job, LMDSampler,
+                      prepare_gligen_condition)
+from .scheduler import PNDMScheduler
 from .weights import UNetConfig
 
 F32 = torch.float32
@@ -81,10 +85,6 @@ class CachedLayout:
             overall_word_token_indices=[3 + 4 * o for o in range(len(groups))],
             phrase_embeddings=g(7400 + index, (max(n, 1), cfg.gligen_positive_len))[:n],
             bg_seed=index, fg_seed_start=index + 123456789)                      # generate.py:226-229,317-344
-
-
-from .hostprep import (align_with_bboxes, compose as compose_latents, get_centered_box,
-                       input_latents_list as _input_latents_list, proportion_to_mask, seeded_noise, shift_tensor)
 
 
 def get_input_latents_list(bg_seed, fg_seed_start, so_boxes, fg_blending_ratio, in_channels=4, H=64, W=64):
@@ -157,6 +157,79 @@ def _so_mask(refiner, kind, image, box, L, token_attn=None):
     return torch.as_tensor(mask).bool()
 
 
+def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule,
+                     use_ref_ca, overall_max_index_step, so_center_box, **centered_box_kwargs):
+    """What LMD+ and LMD derive alike from their arguments.  use_fast_schedule (lmd_plus.py:360-367, lmd.py:399-406): the
+    per-box generations only feed the mask refinement after the steps needed for latent / attention transfer, so the rest
+    runs on every second timestep."""
+    L = height // 8
+    frozen_steps = int(T * min(max(frozen_step_ratio, 0.0), 1.0))
+    keys = [tuple(k) for k in (guidance_attn_keys or DEFAULT_GUIDANCE_ATTN_KEYS)]
+    so_boxes = [_centered_so_boxes(lay, so_center_box, **centered_box_kwargs) for lay in lays]    # lmd.py:314-324
+    prep = [get_input_latents_list(lay.bg_seed, lay.fg_seed_start, so_boxes[li], fg_blending_ratio,
+                                   sampler.eng.cfg.in_channels, L, L) for li, lay in enumerate(lays)]
+    fast_after = (max(frozen_steps, overall_max_index_step) if use_ref_ca else frozen_steps) if use_fast_schedule else None
+    comp_steps = fast_after if use_fast_schedule else T                       # latents.py:46-48,77-78
+    return L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps
+
+
+def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, **denoise_kw):
+    """One generation per box (job_of(layout, its index, box index, box)), all boxes of all layouts as one batched
+    denoising call -> per layout the histories, saved maps, foreground masks (mask_of(decoded image or None, box, result)),
+    decoded images and guidance iteration counts of its boxes."""
+    owner = [(li, i) for li in range(len(lays)) for i in range(len(so_boxes[li]))]
+    jobs = [job_of(lays[li], li, i, so_boxes[li][i]) for li, i in owner]
+    res_a = sampler.denoise_batch(jobs, T, return_cond_ca_only=True, **denoise_kw) if jobs else []
+    per_lay = [dict(latents_all=[], masks=[], saved=[], so_images=[], guidance_iters=[]) for _ in lays]
+    if decode and res_a:
+        imgs = sampler.decode(torch.cat([r["latents"] for r in res_a]))      # feeds SAM in the reference
+    for n, ((li, i), r) in enumerate(zip(owner, res_a)):
+        d = per_lay[li]
+        d["latents_all"].append(r["latents_all"])
+        d["saved"].append(r["saved"])
+        d["guidance_iters"].append(r["guidance_iters"])
+        d["masks"].append(mask_of(imgs[n] if decode else None, so_boxes[li][i], r))
+        if decode:
+            d["so_images"].append(imgs[n:n + 1])
+    return per_lay
+
+
+def _overall_guidance(sampler, lay, saved, keys, L, T, use_ref_ca, max_iter=None, **thresholds_and_weights):
+    """Guidance of the overall generation (lmd_plus.py:487 / lmd.py:521), or None for a layout without boxes."""
+    overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
+    if not overall_bboxes:
+        return None
+    return dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions, max_iter=max_iter or DEFAULT_MAX_ITER,
+                ref_ca_word_token_only=True, ref_ca_last_token_only=True,
+                word_token_indices=lay.overall_word_token_indices, use_ratio_based_loss=False, guidance_attn_keys=keys,
+                ref_maps=_ref_maps(sampler, saved, keys, L, T) if use_ref_ca else None, **thresholds_and_weights)
+
+
+def _stage_b(sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only,
+             use_ref_ca, overall, decode, gligen_of=lambda lay: None, overall_start=None, **denoise_kw):
+    """Alignment (latents.py:107-118), composition (lmd_plus.py:398-416) and the overall generation with attention guidance
+    (overall: _overall_guidance's keyword arguments) of all layouts as one batched denoising call -> (result dict per
+    layout, the denoising results).  gligen_of(layout): the GLIGEN conditioning of its job, if the method has one."""
+    jobs, comps = [], []
+    for li, lay in enumerate(lays):
+        d = per_lay[li]
+        _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_only)
+        composed, fg_idx = compose_latents(d["latents_all"], d["masks"], comp_steps, prep[li][1].to(sampler.dev))
+        comps.append((composed, fg_idx))
+        start = composed
+        if overall_start is not None:                     # rows 1.. still feed the frozen-mask blend
+            start = composed.clone()
+            start[0] = torch.as_tensor(overall_start[li]).to(start.device, start.dtype)
+        jobs.append(Job(start, torch.cat([lay.overall_uncond, lay.overall_cond]), gligen=gligen_of(lay),
+                        guidance=_overall_guidance(sampler, lay, d["saved"], keys, L, T, use_ref_ca, **overall),
+                        frozen_mask=(fg_idx != 0)))
+    res_b = sampler.denoise_batch(jobs, T, save_all_latents=False, **denoise_kw)
+    images = sampler.decode(torch.cat([r["latents"] for r in res_b])) if decode else [None] * len(lays)
+    return [dict(image=images[li], latents=r["latents"], so_images=per_lay[li]["so_images"],
+                 guidance_iters=r["guidance_iters"], composed=comps[li][0], fg_idx=comps[li][1],
+                 so_guidance_iters=per_lay[li]["guidance_iters"]) for li, r in enumerate(res_b)], res_b
+
+
 def lmd_plus_generate(sampler: LMDSampler, lay: CachedLayout, **kw):
     """LMD+ for one layout (generation/lmd_plus.py:193-520 with its default arguments)."""
     return lmd_plus_generate_batch(sampler, [lay], **kw)[0]
@@ -181,87 +254,41 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
     are independent of how layouts are batched (images only share kernel launches).
     overall_first_step / overall_n_steps / overall_start (one latent tensor per layout): run only those steps of the
     overall generation, from the given state — the teacher-forcing hook of the parity tests."""
-    L = height // 8
-    T = num_inference_steps
-    frozen_steps = int(T * min(max(frozen_step_ratio, 0.0), 1.0))
-    keys = [tuple(k) for k in (guidance_attn_keys or DEFAULT_GUIDANCE_ATTN_KEYS)]
-    dev = sampler.dev
-    C = sampler.eng.cfg.in_channels
-    so_boxes = [_centered_so_boxes(lay, so_center_box, horizontal_center_only=so_horizontal_center_only)
-                for lay in lays]
-    prep = [get_input_latents_list(lay.bg_seed, lay.fg_seed_start, so_boxes[li], fg_blending_ratio, C, L, L)
-            for li, lay in enumerate(lays)]
-    # use_fast_schedule (lmd_plus.py:360-367): the per-box generations only feed SAM after the steps needed
-    # for latent / attention transfer, so the rest runs on every second timestep.
-    fast_after = (max(frozen_steps, overall_max_index_step) if use_ref_ca else frozen_steps) if use_fast_schedule else None
-    comp_steps = fast_after if use_fast_schedule else T                       # latents.py:46-48,77-78
-    # ---- stage A: one GLIGEN generation per box (lmd_plus.py:44-145,162-188), all boxes batched
-    jobs, owner = [], []
-    if use_ref_ca or frozen_steps > 0:
-        for li, lay in enumerate(lays):
-            for i, box in enumerate(so_boxes[li]):
-                guid = None
-                if max_index_step > 0:                       # lmd_plus.py:320-328 (semantic_guidance_kwargs)
-                    guid = dict(bboxes=[list(box)], object_positions=[lay.so_object_positions[i]],
-                                loss_scale=loss_scale, loss_threshold=loss_threshold,
-                                max_iter=max_iter or DEFAULT_MAX_ITER, max_index_step=max_index_step,
-                                use_ratio_based_loss=False, guidance_attn_keys=keys)
-                jobs.append(Job(prep[li][0][i], torch.cat([lay.so_uncond, lay.so_cond[i:i + 1]]),
-                                gligen=prepare_gligen_condition([list(box)], lay.phrase_embeddings[i:i + 1], dev),
-                                guidance=guid, token=lay.so_word_token_index[i]))
-                owner.append((li, i))
-    res_a = sampler.denoise_batch(jobs, T, guidance_scale=guidance_scale, use_gligen=True,
-                                  gligen_scheduled_sampling_beta=so_gligen_scheduled_sampling_beta,
-                                  saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys] if use_ref_ca else [OBJ_ATTN_KEY],
-                                  return_cond_ca_only=True, fast_after_steps=fast_after) if jobs else []
-    per_lay = [dict(latents_all=[], masks=[], saved=[], so_images=[]) for _ in lays]
-    if decode and res_a:
-        imgs = sampler.decode(torch.cat([r["latents"] for r in res_a]))      # feeds SAM in the reference
-    for n, ((li, i), r) in enumerate(zip(owner, res_a)):
-        d = per_lay[li]
-        d["latents_all"].append(r["latents_all"])
-        d["saved"].append(r["saved"])
-        d["masks"].append(_so_mask(mask_refiner, "box", imgs[n] if decode else None, so_boxes[li][i], L))
-        if decode:
-            d["so_images"].append(imgs[n:n + 1])
-    # ---- composition (lmd_plus.py:398-416) and stage B: overall generation with attention guidance
-    jobs_b, comps = [], []
-    for li, lay in enumerate(lays):
-        d = per_lay[li]
-        _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_only)
-        composed, fg_idx = compose_latents(d["latents_all"], d["masks"], comp_steps, prep[li][1].to(dev))
-        comps.append((composed, fg_idx))
-        overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
-        flat = [i for grp in lay.overall_groups for i in grp]
+    T, dev = num_inference_steps, sampler.dev
+    L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps = _two_stage_setup(
+        sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule, use_ref_ca,
+        overall_max_index_step, so_center_box, horizontal_center_only=so_horizontal_center_only)
+
+    def so_job(lay, li, i, box):                             # one GLIGEN generation per box (lmd_plus.py:44-145,162-188)
         guid = None
-        if overall_bboxes:
-            guid = dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions,
-                        loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold,
-                        max_iter=overall_max_iter or DEFAULT_MAX_ITER, max_index_step=overall_max_index_step,
-                        fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p, fg_weight=overall_fg_weight,
-                        bg_weight=overall_bg_weight, ref_ca_word_token_only=True, ref_ca_last_token_only=True,
-                        word_token_indices=lay.overall_word_token_indices, ref_ca_loss_weight=ref_ca_loss_weight,
-                        use_ratio_based_loss=False, guidance_attn_keys=keys,   # lmd_plus.py:487 / lmd.py:521
-                        ref_maps=_ref_maps(sampler, d["saved"], keys, L, T) if use_ref_ca else None)
-        gl = prepare_gligen_condition([list(lay.boxes[i]) for i in flat], lay.phrase_embeddings[flat], dev)
-        start = composed
-        if overall_start is not None:                     # rows 1.. still feed the frozen-mask blend
-            start = composed.clone()
-            start[0] = torch.as_tensor(overall_start[li]).to(start.device, start.dtype)
-        jobs_b.append(Job(start, torch.cat([lay.overall_uncond, lay.overall_cond]), gligen=gl, guidance=guid,
-                          frozen_mask=(fg_idx != 0)))
-    res_b = sampler.denoise_batch(jobs_b, T, guidance_scale=guidance_scale, use_gligen=True,
-                                  gligen_scheduled_sampling_beta=overall_gligen_scheduled_sampling_beta,
-                                  frozen_steps=frozen_steps, save_all_latents=False, first_step=overall_first_step,
-                                  n_steps=overall_n_steps)
-    images = sampler.decode(torch.cat([r["latents"] for r in res_b])) if decode else [None] * len(lays)
-    return [dict(image=images[li], latents=res_b[li]["latents"], so_images=per_lay[li]["so_images"],
-                 guidance_iters=res_b[li]["guidance_iters"],
-                 guidance_iters_fuser_on=res_b[li]["guidance_iters_fuser_on"], composed=comps[li][0],
-                 fg_idx=comps[li][1],
-                 so_latents_all=per_lay[li]["latents_all"],
-                 so_guidance_iters=[r["guidance_iters"] for (lj, _), r in zip(owner, res_a) if lj == li])
-            for li in range(len(lays))]
+        if max_index_step > 0:                               # lmd_plus.py:320-328 (semantic_guidance_kwargs)
+            guid = dict(bboxes=[list(box)], object_positions=[lay.so_object_positions[i]], loss_scale=loss_scale,
+                        loss_threshold=loss_threshold, max_iter=max_iter or DEFAULT_MAX_ITER,
+                        max_index_step=max_index_step, use_ratio_based_loss=False, guidance_attn_keys=keys)
+        return Job(prep[li][0][i], torch.cat([lay.so_uncond, lay.so_cond[i:i + 1]]),
+                   gligen=prepare_gligen_condition([list(box)], lay.phrase_embeddings[i:i + 1], dev),
+                   guidance=guid, token=lay.so_word_token_index[i])
+
+    def overall_gligen(lay):
+        flat = [i for grp in lay.overall_groups for i in grp]
+        return prepare_gligen_condition([list(lay.boxes[i]) for i in flat], lay.phrase_embeddings[flat], dev)
+    per_lay = _stage_a(sampler, lays, so_boxes if use_ref_ca or frozen_steps > 0 else [[]] * len(lays), T, decode, so_job,
+                       lambda image, box, r: _so_mask(mask_refiner, "box", image, box, L),
+                       guidance_scale=guidance_scale, use_gligen=True,
+                       gligen_scheduled_sampling_beta=so_gligen_scheduled_sampling_beta,
+                       saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys] if use_ref_ca else [OBJ_ATTN_KEY],
+                       fast_after_steps=fast_after)
+    out, res_b = _stage_b(
+        sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only, use_ref_ca,
+        dict(loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold, max_iter=overall_max_iter,
+             max_index_step=overall_max_index_step, fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p,
+             fg_weight=overall_fg_weight, bg_weight=overall_bg_weight, ref_ca_loss_weight=ref_ca_loss_weight),
+        decode, overall_gligen, overall_start, guidance_scale=guidance_scale, use_gligen=True,
+        gligen_scheduled_sampling_beta=overall_gligen_scheduled_sampling_beta, frozen_steps=frozen_steps,
+        first_step=overall_first_step, n_steps=overall_n_steps)
+    for d, r, pl in zip(out, res_b, per_lay):
+        d.update(guidance_iters_fuser_on=r["guidance_iters_fuser_on"], so_latents_all=pl["latents_all"])
+    return out
 
 
 def lmd_generate(sampler: LMDSampler, lay: CachedLayout, **kw):
@@ -283,73 +310,53 @@ def lmd_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num_inf
     generate_semantic_guidance WITH guidance (lmd.py:340-352), all boxes of all layouts in one batched
     denoising call (each image keeps its own guidance loop exit); overall stage = generate_partial_frozen
     with the reference-attention term (lmd.py:530-542), all layouts in another."""
-    L = height // 8
     T = num_inference_steps
-    frozen_steps = int(T * min(max(frozen_step_ratio, 0.0), 1.0))
-    keys = [tuple(k) for k in (guidance_attn_keys or DEFAULT_GUIDANCE_ATTN_KEYS)]
-    dev = sampler.dev
+    L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps = _two_stage_setup(
+        sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule, use_ref_ca,
+        overall_max_index_step, so_center_box, horizontal_center_only=so_horizontal_center_only,
+        vertical_placement=so_vertical_placement, floor_padding=so_floor_padding)
+
+    def so_job(lay, li, i, box):
+        guid = dict(bboxes=[list(box)], object_positions=[lay.so_object_positions[i]], loss_scale=loss_scale,
+                    loss_threshold=loss_threshold, max_iter=max_iter or DEFAULT_MAX_ITER,
+                    max_index_step=max_index_step, fg_top_p=fg_top_p, bg_top_p=bg_top_p, fg_weight=fg_weight,
+                    bg_weight=bg_weight, use_ratio_based_loss=False, guidance_attn_keys=keys)   # lmd.py:349
+        return Job(prep[li][0][i], torch.cat([lay.so_uncond, lay.so_cond[i:i + 1]]), guidance=guid,
+                   token=lay.so_word_token_index[i])
+
+    def so_mask(image, box, r):
+        return _so_mask(mask_refiner, "attn", image, box, L,
+                        token_attn=_token_attn(r["saved"], attn_aggregation_step_start) if mask_refiner else None)
+    per_lay = _stage_a(sampler, lays, so_boxes, T, decode, so_job, so_mask, guidance_scale=guidance_scale,
+                       saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys], fast_after_steps=fast_after)
+    return _stage_b(
+        sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only, use_ref_ca,
+        dict(loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold, max_iter=overall_max_iter,
+             max_index_step=overall_max_index_step, fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p,
+             fg_weight=overall_fg_weight, bg_weight=overall_bg_weight, ref_ca_loss_weight=ref_ca_loss_weight),
+        decode, guidance_scale=guidance_scale, frozen_steps=frozen_steps)[0]
+
+
+def _single_shot(sampler, lays, keys, guidance_kw, *, num_inference_steps, guidance_scale, height, decode, first_step,
+                 n_steps, start, trace):
+    """One generate_semantic_guidance call per layout on seeded noise (or `start`), no per-box stage; guidance_kw: what the
+    method adds to the overall boxes, token positions and attention keys of each layout's guidance."""
+    L = height // 8
     C = sampler.eng.cfg.in_channels
-    so_boxes = [_centered_so_boxes(lay, so_center_box, horizontal_center_only=so_horizontal_center_only,
-                                   vertical_placement=so_vertical_placement, floor_padding=so_floor_padding)
-                for lay in lays]                                              # lmd.py:314-324
-    prep = [get_input_latents_list(lay.bg_seed, lay.fg_seed_start, so_boxes[li], fg_blending_ratio, C, L, L)
-            for li, lay in enumerate(lays)]
-    fast_after = (max(frozen_steps, overall_max_index_step) if use_ref_ca else frozen_steps) \
-        if use_fast_schedule else None                                        # lmd.py:399-406
-    comp_steps = fast_after if use_fast_schedule else T
-    # ---- stage A
-    jobs, owner = [], []
-    for li, lay in enumerate(lays):
-        for i, box in enumerate(so_boxes[li]):
-            guid = dict(bboxes=[list(box)], object_positions=[lay.so_object_positions[i]], loss_scale=loss_scale,
-                        loss_threshold=loss_threshold, max_iter=max_iter or DEFAULT_MAX_ITER,
-                        max_index_step=max_index_step, fg_top_p=fg_top_p, bg_top_p=bg_top_p, fg_weight=fg_weight,
-                        bg_weight=bg_weight, use_ratio_based_loss=False, guidance_attn_keys=keys)   # lmd.py:349
-            jobs.append(Job(prep[li][0][i], torch.cat([lay.so_uncond, lay.so_cond[i:i + 1]]), guidance=guid,
-                            token=lay.so_word_token_index[i]))
-            owner.append((li, i))
-    res_a = sampler.denoise_batch(jobs, T, guidance_scale=guidance_scale,
-                                  saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys], return_cond_ca_only=True,
-                                  fast_after_steps=fast_after) if jobs else []
-    per_lay = [dict(latents_all=[], masks=[], saved=[], so_images=[]) for _ in lays]
-    if decode and res_a:
-        imgs = sampler.decode(torch.cat([r["latents"] for r in res_a]))
-    for n, ((li, i), r) in enumerate(zip(owner, res_a)):
-        d = per_lay[li]
-        d["latents_all"].append(r["latents_all"])
-        d["saved"].append(r["saved"])
-        d["masks"].append(_so_mask(mask_refiner, "attn", imgs[n] if decode else None, so_boxes[li][i], L,
-                                  token_attn=_token_attn(r["saved"], attn_aggregation_step_start) if mask_refiner else None))
-        if decode:
-            d["so_images"].append(imgs[n:n + 1])
-    # ---- alignment (latents.py:107-118), composition, stage B
-    jobs_b, comps = [], []
-    for li, lay in enumerate(lays):
-        d = per_lay[li]
-        _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_only)
-        composed, fg_idx = compose_latents(d["latents_all"], d["masks"], comp_steps, prep[li][1].to(dev))
-        comps.append((composed, fg_idx))
+    jobs = []
+    for lay in lays:
+        lat = seeded_noise(lay.bg_seed, C, L, L) if start is None else torch.as_tensor(start[len(jobs)]).float()
         overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
-        flat = [i for grp in lay.overall_groups for i in grp]
         guid = None
         if overall_bboxes:
-            guid = dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions,
-                        loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold,
-                        max_iter=overall_max_iter or DEFAULT_MAX_ITER, max_index_step=overall_max_index_step,
-                        fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p, fg_weight=overall_fg_weight,
-                        bg_weight=overall_bg_weight, ref_ca_word_token_only=True, ref_ca_last_token_only=True,
-                        word_token_indices=lay.overall_word_token_indices, ref_ca_loss_weight=ref_ca_loss_weight,
-                        use_ratio_based_loss=False, guidance_attn_keys=keys,   # lmd_plus.py:487 / lmd.py:521
-                        ref_maps=_ref_maps(sampler, d["saved"], keys, L, T) if use_ref_ca else None)
-        jobs_b.append(Job(composed, torch.cat([lay.overall_uncond, lay.overall_cond]), guidance=guid,
-                          frozen_mask=(fg_idx != 0)))
-    res_b = sampler.denoise_batch(jobs_b, T, guidance_scale=guidance_scale, frozen_steps=frozen_steps,
-                                  save_all_latents=False)
-    images = sampler.decode(torch.cat([r["latents"] for r in res_b])) if decode else [None] * len(lays)
-    return [dict(image=images[li], latents=res_b[li]["latents"], so_images=per_lay[li]["so_images"],
-                 guidance_iters=res_b[li]["guidance_iters"], composed=comps[li][0], fg_idx=comps[li][1],
-                 so_guidance_iters=[r["guidance_iters"] for (lj, _), r in zip(owner, res_a) if lj == li])
-            for li in range(len(lays))]
+            guid = dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions, guidance_attn_keys=keys,
+                        **guidance_kw)
+        jobs.append(Job(lat, torch.cat([lay.overall_uncond, lay.overall_cond]), guidance=guid))
+    res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, save_all_latents=False,
+                                first_step=first_step, n_steps=n_steps, trace=trace)
+    images = sampler.decode(torch.cat([r["latents"] for r in res])) if decode else [None] * len(lays)
+    return [dict(image=images[i], latents=r["latents"], guidance_iters=r["guidance_iters"], guidance_iters_fuser_on=0)
+            for i, r in enumerate(res)]
 
 
 def backward_guidance_generate(sampler: LMDSampler, lay: CachedLayout, **kw):
@@ -372,24 +379,11 @@ def backward_guidance_generate_batch(sampler: LMDSampler, lays: List[CachedLayou
     (`use_ratio_based_loss=False, fg_top_p=...`) for experiments; nothing in the reference's plugin does.
     `first_step` / `n_steps` / `start` (one latent tensor per layout, the state BEFORE step first_step) / `trace` run a
     slice of the schedule from given latents: the teacher-forced parity tests."""
-    L = height // 8
-    C = sampler.eng.cfg.in_channels
     keys = [tuple(k) for k in (guidance_attn_keys or DEFAULT_GUIDANCE_ATTN_KEYS)]
-    jobs = []
-    for lay in lays:
-        lat = seeded_noise(lay.bg_seed, C, L, L) if start is None else torch.as_tensor(start[len(jobs)]).float()
-        overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
-        guid = None
-        if overall_bboxes:
-            guid = dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions, loss_scale=loss_scale,
-                        loss_threshold=loss_threshold, max_iter=max_iter, max_index_step=max_index_step,
-                        guidance_attn_keys=keys, **energy_kw)
-        jobs.append(Job(lat, torch.cat([lay.overall_uncond, lay.overall_cond]), guidance=guid))
-    res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, save_all_latents=False,
-                                first_step=first_step, n_steps=n_steps, trace=trace)
-    images = sampler.decode(torch.cat([r["latents"] for r in res])) if decode else [None] * len(lays)
-    return [dict(image=images[i], latents=r["latents"], guidance_iters=r["guidance_iters"],
-                 guidance_iters_fuser_on=0) for i, r in enumerate(res)]
+    return _single_shot(sampler, lays, keys, dict(loss_scale=loss_scale, loss_threshold=loss_threshold, max_iter=max_iter,
+                                                  max_index_step=max_index_step, **energy_kw),
+                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, height=height,
+                        decode=decode, first_step=first_step, n_steps=n_steps, start=start, trace=trace)
 
 
 def boxdiff_generate(sampler: LMDSampler, lay: CachedLayout, **kw):
@@ -408,24 +402,10 @@ def boxdiff_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num
     None / weight 0).  `boxdiff_kw` may carry latent_backward_guidance_boxdiff's own arguments (amp_loss_scale,
     latent_scale, scale_range, P, L, smooth_attentions, sigma); the plugin passes none.
     `first_step` / `n_steps` / `start` / `trace`: a slice of the schedule from given latents (teacher-forced tests)."""
-    from .sampler import BOXDIFF_GUIDANCE_ATTN_KEYS
-    L = height // 8
-    C = sampler.eng.cfg.in_channels
     keys = [tuple(k) for k in (guidance_attn_keys or BOXDIFF_GUIDANCE_ATTN_KEYS)]
-    jobs = []
-    for lay in lays:
-        lat = seeded_noise(lay.bg_seed, C, L, L) if start is None else torch.as_tensor(start[len(jobs)]).float()
-        overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
-        guid = None
-        if overall_bboxes:
-            guid = dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions, use_boxdiff=True,
-                        max_index_step=max_index_step, guidance_attn_keys=keys, **boxdiff_kw)
-        jobs.append(Job(lat, torch.cat([lay.overall_uncond, lay.overall_cond]), guidance=guid))
-    res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, save_all_latents=False,
-                                first_step=first_step, n_steps=n_steps, trace=trace)
-    images = sampler.decode(torch.cat([r["latents"] for r in res])) if decode else [None] * len(lays)
-    return [dict(image=images[i], latents=r["latents"], guidance_iters=r["guidance_iters"], guidance_iters_fuser_on=0)
-            for i, r in enumerate(res)]
+    return _single_shot(sampler, lays, keys, dict(use_boxdiff=True, max_index_step=max_index_step, **boxdiff_kw),
+                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, height=height,
+                        decode=decode, first_step=first_step, n_steps=n_steps, start=start, trace=trace)
 
 
 def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=50, guidance_scale=7.5, scheduler=None,
@@ -439,7 +419,6 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor, already scaled
     by init_noise_sigma.  Returns (final latents (N,C,L,L), uint8 images (N,8L,8L,3) from sampler.decode or None), plus
     the per-image histories (E+1,1,C,L,L) with save_all_latents."""
-    from .scheduler import PNDMScheduler
     sch = PNDMScheduler.from_config(sampler.scheduler) if scheduler is None else scheduler
     starts = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
     if len(starts) != len(texts):

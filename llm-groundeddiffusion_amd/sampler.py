@@ -15,14 +15,13 @@ Per step (all on one HIP stream, no host round trip except the reference's own `
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
-import threading
-
 import torch
 
 from . import ops
 from .energy import BoxDiffTables, EnergyTables
 from .lanes import GATE
-from .scheduler import DDIMScheduler
+from .loop import HipGraph, LoopState, StateCache, clamp_steps, run_steps  # noqa: F401 (HipGraph: importable from here)
+from .scheduler import MULTISTEP, PLMS, DDIMScheduler
 from .unet import N_OBJ_TOKENS, UNetEngine
 
 F32 = torch.float32
@@ -70,57 +69,16 @@ class GuidanceState:
         return int(m)
 
 
-class HipGraph:
-    """A captured hipGraph of a launch sequence (torch.cuda.CUDAGraph drives hipStreamBeginCapture on
-    torch's current stream — the stream every lgd_* call is enqueued on).  Replaces ~400 host-side
-    launches per UNet call by one hipGraphLaunch; everything that varies between replays (timestep,
-    frozen-step count, latents, maps) lives in device memory at fixed addresses."""
-
-    def __init__(self, fn, warmup: int = 1):
-        # exclusive among the host threads of a lanes.LanePool: other lanes park at their next step boundary
-        with GATE.exclusive():
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    fn()                       # also triggers one-time hipFuncSetAttribute calls
-            cur.wait_stream(side)
-            cur.synchronize()
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                fn()
-
-    def __call__(self):
-        self.graph.replay()
-
-
-class _State:
-    """Persistent device buffers of one (batch, latent shape, step count): fixed addresses for the graphs."""
+class _State(LoopState):
+    """Persistent device buffers of one (batch, latent shape) with room for T steps: fixed addresses for the graphs."""
 
     def __init__(self, dev, nb, C, L, T):
-        self.lat = torch.zeros((nb, C, L, L), device=dev, dtype=F32)
+        super().__init__(torch.zeros((nb, C, L, L), device=dev, dtype=F32), T)
         self.hist = torch.zeros((T + 1, nb, C, L, L), device=dev, dtype=F32)
         self.frozen_ref = torch.zeros((T + 1, nb, C, L, L), device=dev, dtype=F32)
         self.mask = torch.zeros((nb, L * L), device=dev, dtype=F32)
         self.active = torch.zeros(nb, device=dev, dtype=F32)      # per-image guidance on/off
-        self.ctab = torch.zeros((T, 4), device=dev, dtype=F32)
-        self.mtab = torch.zeros((T, 8), device=dev, dtype=F32)      # linear-multistep schedulers (DPM-Solver++)
-        self.x0_prev = torch.zeros((nb, C, L, L), device=dev, dtype=F32)
         self.gtab = torch.zeros((T, 4), device=dev, dtype=F32)
-        self.graphs = {}
-        self.ptab = self.ets = self.cur_sample = None                 # PLMS (PNDMScheduler): allocated on first use
-
-    def plms_buffers(self):
-        """Coefficient table, ring of the last three outputs and saved sample of lgd_cfg_plms_step_f32 (fixed addresses
-        for the graphs; only states that run PNDM carry them)."""
-        if self.ptab is None:
-            dev = self.lat.device
-            self.ptab = torch.zeros((self.ctab.shape[0], 16), device=dev, dtype=F32)
-            self.ets = torch.zeros((3,) + tuple(self.lat.shape), device=dev, dtype=F32)
-            self.cur_sample = torch.zeros_like(self.lat)
-        return self
 
 
 def plan_chunks(n: int, cap: int, buckets: Sequence[int], max_pad: float = 0.25) -> List[Tuple[int, int]]:
@@ -173,7 +131,8 @@ class LMDSampler:
         self.max_pad = 0.25          # plan_chunks: a call is padded by at most this fraction of its bucket
         self.stats = dict(unet_main=0, guidance_iters=0, images=0, padded_images=0)
         self.pass_counts: Dict[Tuple, int] = {}      # (kind, fuser on?, images) -> launches of that plan
-        self._states = {}
+        self._states = StateCache(self.MAX_STATES)
+        self.md_states = StateCache(4)               # the states of multidiffusion.multidiffusion_generate on this engine
 
     # ------------------------------------------------------------------------------------------
     def map_hw(self, L: int) -> Dict[Tuple, int]:
@@ -258,29 +217,23 @@ class LMDSampler:
         """Device state + captured graphs per (batch bucket, latent shape), with room for T steps: the step count is a
         CAPACITY of the history / coefficient tables, not part of the identity, so the graphs captured during a short
         run (bench.py's 2-step pre-build before the timed region) are the ones a 50-step run replays.  A longer
-        schedule than the capacity re-creates the state (and its graphs).  Least recently used entries are dropped so
-        a long run over many shapes keeps a bounded footprint."""
-        key = (nb, C, L)
-        st = self._states.pop(key, None)
-        if st is None or st.ctab.shape[0] < T:
-            st = _State(self.dev, nb, C, L, max(T, self.STATE_MIN_STEPS))
-        self._states[key] = st                                  # (re)insert at the MRU end
-        while len(self._states) > self.MAX_STATES:
-            self._states.pop(next(iter(self._states)))
-        return st
+        schedule than the capacity re-creates the state (and its graphs)."""
+        return self._states.get((nb, C, L), lambda: _State(self.dev, nb, C, L, max(T, self.STATE_MIN_STEPS)),
+                                fits=lambda st: st.capacity >= T)
 
-    def _runner(self, st: _State, name, fn):
-        """fn enqueued eagerly or as a cached hipGraph."""
-        if not self.use_graphs:
-            return fn
-        if name not in st.graphs:
-            st.graphs[name] = HipGraph(fn)
-        return st.graphs[name]
+    def _main_pass(self, plan, st: _State, step, nb: int):
+        """The launch sequence of one denoising step for nb images: CFG pair in, UNet, fused CFG + scheduler step."""
+        def main_fn():
+            ops.copy_(plan.latents_in[:nb], st.lat)                          # torch.cat([latents]*2)
+            ops.copy_(plan.latents_in[nb:], st.lat)
+            plan.forward()
+            step.launch(plan.eps_out, st.lat, self.eng.dyn, frozen_ref=st.frozen_ref, mask=st.mask, hist=st.hist)
+        return main_fn
 
-    def _guide_runners(self, st: _State, nb: int, L: int, fuser: bool, gkeys):
-        """(plan, forward runner, backward+update runner) of the guidance pass for a batch of nb images:
-        B=nb grad plan on the conditional text (second half of the text batch) and the zero-masked GLIGEN
-        half (pipelines.py:381-384)."""
+    def _guide_pass(self, st: _State, nb: int, L: int, fuser: bool, gkeys):
+        """(plan, forward, backward + latent update) of the guidance pass for a batch of nb images; the energy launch
+        goes between the two: B=nb grad plan on the conditional text (second half of the text batch) and the
+        zero-masked GLIGEN half (pipelines.py:381-384)."""
         eng = self.eng
         pg = eng.plan(nb, L, grad=True, fuser=fuser, stop_key=eng.last_key(gkeys), save_keys=gkeys,
                       text_batch_offset=nb, obj_batch_offset=0)
@@ -291,8 +244,12 @@ class LMDSampler:
         def g_bwd():
             grad = pg.backward(self.grad_scale)
             ops.axpy(grad, st.lat, st.gtab, eng.dyn, 0, active=st.active)       # pipelines.py:62-69
+        return pg, g_fwd, g_bwd
+
+    def _guide_runners(self, st: _State, nb: int, L: int, fuser: bool, gkeys):
+        pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, fuser, gkeys)
         name = ("guide", fuser, tuple(gkeys))
-        return pg, self._runner(st, name + ("fwd",), g_fwd), self._runner(st, name + ("bwd",), g_bwd)
+        return pg, st.runner(name + ("fwd",), g_fwd, self.use_graphs), st.runner(name + ("bwd",), g_bwd, self.use_graphs)
 
     def _count(self, kind, fuser, nb):
         k = (kind, bool(fuser), int(nb))
@@ -372,19 +329,11 @@ class LMDSampler:
         for f in ([True, False] if gligen else [False]):
             for nb in main_batches:
                 plan = eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys)
-                st_m = self._state(nb, eng.cfg.in_channels, L, T)
-
-                def main(plan=plan, st=st_m, nb=nb):                       # as _denoise_chunk's main_fn
-                    ops.copy_(plan.latents_in[:nb], st.lat)
-                    ops.copy_(plan.latents_in[nb:], st.lat)
-                    plan.forward()
-                    ops.cfg_ddim_step(plan.eps_out, st.lat, st.lat, st.ctab, eng.dyn, frozen_ref=st.frozen_ref,
-                                      mask=st.mask, hist=st.hist)
-                out.append(("main", f, nb, main))
+                st = self._state(nb, eng.cfg.in_channels, L, T)
+                out.append(("main", f, nb, self._main_pass(plan, st, st.step_kernel(self.scheduler.step_kind), nb)))
             for nb in guide_batches:
                 st = self._state(nb, eng.cfg.in_channels, L, T)
-                pg = eng.plan(nb, L, grad=True, fuser=f, stop_key=eng.last_key(keys), save_keys=keys,
-                              text_batch_offset=nb)
+                pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, f, keys)
 
                 # the energy launch between the two halves: a canonical two-box layout per image (its cost depends on
                 # the item count only, 2 boxes x 3 tokens x 4 keys + reference terms, not on the boxes)
@@ -398,11 +347,10 @@ class LMDSampler:
                 energy = en[0] if nb == 1 else EnergyTables.merged(en)
                 energy.bind(pg.maps, pg.gmaps)
 
-                def guide(pg=pg, st=st, energy=energy):
-                    pg.forward(st.lat)
+                def guide(g_fwd=g_fwd, g_bwd=g_bwd, energy=energy):
+                    g_fwd()
                     energy.run(eng.dyn, grad_scale=self.grad_scale)
-                    pg.backward(self.grad_scale)
-                    ops.axpy(pg.g_latents, st.lat, st.gtab, eng.dyn, 0, active=st.active)
+                    g_bwd()
                 out.append(("guide", f, nb, guide))
         return out
 
@@ -468,29 +416,10 @@ class LMDSampler:
         nb = len(jobs)
         starts = [j.latents[0] if j.latents.dim() == 5 else j.latents for j in jobs]
         _, C, L, _ = starts[0].shape
-        T = num_inference_steps
-        sch.set_timesteps(T)
-        ts = sch.timesteps
-        st = self._state(nb, C, L, len(ts))                                  # evaluations: T, or T + 1 under PLMS
-        if fast_after_steps is not None:
-            ts = sch.fast_schedule(ts, int(fast_after_steps), int(fast_rate))
+        self._refuse_undefined(sch.step_kind, fast=fast_after_steps is not None, partial=int(first_step) > 0,
+                               conditioned=frozen_steps > 0 or use_gligen or any(j.guidance is not None for j in jobs))
+        st, ts, step = self._load_schedule(sch, nb, C, L, num_inference_steps, guidance_scale, fast_after_steps, fast_rate)
         Tr = len(ts)                                                          # steps actually run
-        multistep = bool(getattr(sch, "multistep", False))
-        plms = bool(getattr(sch, "plms", False))
-        if plms:
-            if (fast_after_steps is not None or frozen_steps > 0 or use_gligen or int(first_step) > 0 or
-                    any(j.guidance is not None for j in jobs)):
-                raise RuntimeError("PNDMScheduler runs the plain CFG loop only (pipelines.py:257-273): guidance, GLIGEN, "
-                                   "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
-            st.plms_buffers().ptab[:Tr].copy_(sch.plms_table(guidance_scale, dev, timesteps=ts))
-        elif multistep:
-            if fast_after_steps is not None:
-                raise RuntimeError("the fast schedule (utils/schedule.py) re-derives DDIM step sizes; not defined for the "
-                                   "multistep scheduler")
-            st.mtab[:Tr].copy_(sch.multistep_table(guidance_scale, dev, timesteps=ts))
-        else:
-            st.ctab[:Tr].copy_(sch.coef_table(guidance_scale, dev, timesteps=ts, step_ratios=sch.dynamic_step_sizes(ts)))
-        st.gtab[:Tr].copy_(sch.guidance_step_table(dev, timesteps=ts))
         n_ground = int(gligen_scheduled_sampling_beta * Tr) if use_gligen else 0   # pipelines.py:405
         save_keys = [tuple(k) for k in saved_cross_attn_keys]
         # a superset of keys is always captured by the main plans so that one graph serves every caller
@@ -498,6 +427,73 @@ class LMDSampler:
 
         def fuser_at(index):
             return bool(use_gligen and index < n_ground)                     # pipelines.py:408-414
+        gstates, gkeys, energy = self._guidance_states(jobs, L, st, Tr)
+        max_guided = max([gs.max_index_step for gs in gstates if gs is not None] + [0])
+
+        # ---- per-run constants (before graph capture so that warm-up launches see valid inputs)
+        eng.prepare_timesteps([int(t) for t in ts])
+        eng.prepare_text(torch.cat([j.text[0:1] for j in jobs] + [j.text[1:2] for j in jobs]))
+        eng.set_step(0)
+        eng.dyn[1:2].fill_(0)
+        plans_main, runners_main, runners_guide = self._plans_and_runners(
+            st, step, jobs, L, {fuser_at(i) for i in range(Tr)}, {fuser_at(i) for i in range(min(max_guided, Tr))},
+            plan_keys, gkeys, use_gligen)
+        first_step, last_step = self._load_call_state(st, jobs, starts, L, Tr, first_step, n_steps, frozen_steps)
+        hw = self.map_hw(L)
+        Bp = 1 if return_cond_ca_only else 2
+        saved = [{k: torch.zeros((Tr, Bp, self.heads_of(k), hw[k], 1 if j.token is not None else eng.text_len),
+                                 device=dev, dtype=F32) for k in save_keys} for j in jobs]
+
+        def one_step(index):
+            fuser_on = fuser_at(index)
+            if index < max_guided:
+                pg, gf, gb = runners_guide[fuser_on]
+                self.backward_guidance(gstates, energy, pg, index, st, gf, gb, trace, fuser=fuser_on)
+            runners_main[fuser_on]()
+            self.stats["unet_main"] += 1
+            self._count("main", fuser_on, nb)
+            maps = plans_main[fuser_on].maps
+            for b, j in enumerate(jobs):                                  # attention_processor.py:466-476
+                for k in save_keys:
+                    m = maps[k][nb + b:nb + b + 1] if return_cond_ca_only else maps[k][[b, nb + b]]
+                    saved[b][k][index].copy_(m[..., int(j.token):int(j.token) + 1] if j.token is not None else m)
+        run_steps(eng, first_step, last_step, one_step)
+        hist = st.hist[:Tr + 1].clone() if save_all_latents else None
+        return [dict(latents=st.lat[b:b + 1].clone(), latents_all=hist[:, b:b + 1] if hist is not None else None,
+                     saved=saved[b], guidance_iters=gstates[b].iterations if gstates[b] is not None else 0,
+                     guidance_iters_fuser_on=gstates[b].iterations_fuser_on if gstates[b] is not None else 0)
+                for b in range(nb)]
+
+    # ---- the phases of _denoise_chunk, in its order
+    @staticmethod
+    def _refuse_undefined(kind, *, fast, partial, conditioned):
+        """What a step kernel does not define is an error, not a fall-back."""
+        if kind == PLMS and (fast or partial or conditioned):
+            raise RuntimeError("PNDMScheduler runs the plain CFG loop only (pipelines.py:257-273): guidance, GLIGEN, "
+                               "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
+        if kind == MULTISTEP and fast:
+            raise RuntimeError("the fast schedule (utils/schedule.py) re-derives DDIM step sizes; not defined for the "
+                               "multistep scheduler")
+        if kind == MULTISTEP and partial:
+            # row `first_step` of a second-order schedule mixes in the data prediction of step first_step - 1, which a
+            # run that starts here does not have (the step kernel's x0_prev holds whatever run used this state last)
+            raise RuntimeError("partial schedules (first_step > 0) are not defined for the multistep scheduler")
+
+    def _load_schedule(self, sch, nb, C, L, T, guidance_scale, fast_after_steps, fast_rate):
+        """-> (state with room for every evaluation of the schedule: T, or T + 1 under PLMS; the timesteps actually run;
+        the step kernel of the scheduler's kind with its table loaded)."""
+        sch.set_timesteps(T)
+        ts = sch.timesteps
+        st = self._state(nb, C, L, len(ts))
+        if fast_after_steps is not None:
+            ts = sch.fast_schedule(ts, int(fast_after_steps), int(fast_rate))
+        step = st.step_kernel(sch.step_kind)
+        step.load(sch, guidance_scale, ts)
+        st.gtab[:len(ts)].copy_(sch.guidance_step_table(self.dev, timesteps=ts))
+        return st, ts, step
+
+    def _guidance_states(self, jobs, L, st, Tr):
+        """-> (GuidanceState or None per job, their shared attention keys, the energy of the whole batch)."""
         gstates: List[Optional[GuidanceState]] = []
         gkeys = None
         for j in jobs:
@@ -511,64 +507,40 @@ class LMDSampler:
                 raise RuntimeError("jobs guided in one batch must share guidance_attn_keys")
             gkeys = jk
             gstates.append(self.make_guidance(L, g.pop("bboxes"), g.pop("object_positions"), **g))
-        guided = any(gs is not None for gs in gstates)
-        energy = None
-        if guided:
-            kinds = {gs.kind for gs in gstates if gs is not None}
-            if len(kinds) != 1:
-                raise RuntimeError("jobs guided in one batch must share the energy (LMD guidance or BoxDiff)")
-            tables = BoxDiffTables if kinds == {"boxdiff"} else EnergyTables
-            if kinds == {"boxdiff"}:             # utils/boxdiff.py:236-238: the update's own step table (all jobs alike)
-                gs0 = next(gs for gs in gstates if gs is not None)
-                if any(gs is not None and getattr(gs, "step_params", None) != getattr(gs0, "step_params", None) for gs in gstates):
-                    raise RuntimeError("BoxDiff jobs guided in one batch must share amp_loss_scale / latent_scale / scale_range")
-                st.gtab[:Tr, 0].copy_(torch.tensor([gs0.step_scale(i, Tr) for i in range(Tr)], dtype=F32))
-            energy = gstates[[gs is not None for gs in gstates].index(True)].energy if nb == 1 else \
-                tables.merged([gs.energy if gs is not None else None for gs in gstates])
-        max_guided = max([gs.max_index_step for gs in gstates if gs is not None] + [0])
+        guided = [gs for gs in gstates if gs is not None]
+        if not guided:
+            return gstates, gkeys, None
+        kinds = {gs.kind for gs in guided}
+        if len(kinds) != 1:
+            raise RuntimeError("jobs guided in one batch must share the energy (LMD guidance or BoxDiff)")
+        tables = BoxDiffTables if kinds == {"boxdiff"} else EnergyTables
+        if kinds == {"boxdiff"}:             # utils/boxdiff.py:236-238: the update's own step table (all jobs alike)
+            if any(gs.step_params != guided[0].step_params for gs in guided):
+                raise RuntimeError("BoxDiff jobs guided in one batch must share amp_loss_scale / latent_scale / scale_range")
+            st.gtab[:Tr, 0].copy_(torch.tensor([guided[0].step_scale(i, Tr) for i in range(Tr)], dtype=F32))
+        energy = guided[0].energy if len(jobs) == 1 else \
+            tables.merged([gs.energy if gs is not None else None for gs in gstates])
+        return gstates, gkeys, energy
 
-        # ---- per-run constants (before graph capture so that warm-up launches see valid inputs)
-        eng.prepare_timesteps([int(t) for t in ts])
-        eng.prepare_text(torch.cat([j.text[0:1] for j in jobs] + [j.text[1:2] for j in jobs]))
-        eng.set_step(0)
-        eng.dyn[1:2].fill_(0)
-
-        # ---- plans + launch sequences (built/captured once per shape, cached)
-        runners_main, plans_main, runners_guide = {}, {}, {}
-        for f in {fuser_at(i) for i in range(Tr)}:
-            plan = plans_main[f] = eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys)
-
-            def main_fn(plan=plan):
-                ops.copy_(plan.latents_in[:nb], st.lat)                      # torch.cat([latents]*2)
-                ops.copy_(plan.latents_in[nb:], st.lat)
-                plan.forward()
-                if plms:
-                    ops.cfg_plms_step(plan.eps_out, st.lat, st.lat, st.ets, st.cur_sample, st.ptab, eng.dyn, hist=st.hist)
-                elif multistep:
-                    ops.cfg_multistep_step(plan.eps_out, st.lat, st.lat, st.x0_prev, st.mtab, eng.dyn,
-                                           frozen_ref=st.frozen_ref, mask=st.mask, hist=st.hist)
-                else:
-                    ops.cfg_ddim_step(plan.eps_out, st.lat, st.lat, st.ctab, eng.dyn, frozen_ref=st.frozen_ref,
-                                      mask=st.mask, hist=st.hist)
-            runners_main[f] = (main_fn, ("main", f, tuple(plan_keys), "plms" if plms else multistep))
-        if guided:
-            for f in {fuser_at(i) for i in range(min(max_guided, Tr))}:
-                runners_guide[f] = self._guide_runners(st, nb, L, f, gkeys)
+    def _plans_and_runners(self, st, step, jobs, L, fusers_main, fusers_guide, plan_keys, gkeys, use_gligen):
+        """Plans + launch sequences (built / captured once per shape, cached on the state) per GLIGEN-fuser setting ->
+        (main plans, main runners, guidance (plan, forward runner, backward runner))."""
+        eng, nb = self.eng, len(jobs)
+        plans = {f: eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys) for f in fusers_main}
+        guides = {f: self._guide_runners(st, nb, L, f, gkeys) for f in fusers_guide}
         if use_gligen:                                                        # after the plans exist
-            eng.prepare_gligen(boxes=torch.cat([j.gligen[0][0:1] for j in jobs] + [j.gligen[0][1:2] for j in jobs]),
-                               positive_embeddings=torch.cat([j.gligen[1][0:1] for j in jobs] +
-                                                             [j.gligen[1][1:2] for j in jobs]),
-                               masks=torch.cat([j.gligen[2][0:1] for j in jobs] + [j.gligen[2][1:2] for j in jobs]))
-        runners_main = {f: self._runner(st, name, fn) for f, (fn, name) in runners_main.items()}
+            boxes, embeddings, masks = (torch.cat([j.gligen[k][0:1] for j in jobs] + [j.gligen[k][1:2] for j in jobs])
+                                        for k in range(3))            # [uncond halves; cond halves], like the text
+            eng.prepare_gligen(boxes=boxes, positive_embeddings=embeddings, masks=masks)
+        mains = {f: st.runner(("main", f, tuple(plan_keys), step.kind), self._main_pass(plan, st, step, nb), self.use_graphs)
+                 for f, plan in plans.items()}
+        return plans, mains, guides
 
-        # ---- state of this call
+    def _load_call_state(self, st, jobs, starts, L, Tr, first_step, n_steps, frozen_steps):
+        """This call's latents, history seed and frozen-mask inputs -> (first, last) step to run."""
+        eng, dev = self.eng, self.dev
         st.lat.copy_(torch.cat([s.to(dev, F32) for s in starts]))
-        first_step = max(0, min(int(first_step), Tr))
-        last_step = Tr if n_steps is None else min(Tr, first_step + int(n_steps))
-        if multistep and first_step > 0:
-            # row `first_step` of a second-order schedule mixes in the data prediction of step first_step - 1, which a
-            # run that starts here does not have (st.x0_prev holds whatever run used this state last)
-            raise RuntimeError("partial schedules (first_step > 0) are not defined for the multistep scheduler")
+        first_step, last_step = clamp_steps(first_step, n_steps, Tr)
         st.hist[first_step].copy_(st.lat)
         st.mask.zero_()
         if frozen_steps > 0:
@@ -578,32 +550,7 @@ class LMDSampler:
                     st.frozen_ref[:rows, b].copy_(j.latents[:rows, 0].to(dev, F32))
                     st.mask[b].copy_(j.frozen_mask.to(dev, F32).clamp(0., 1.).reshape(L * L))
             eng.dyn[1:2].fill_(int(frozen_steps))
-        hw = self.map_hw(L)
-        Bp = 1 if return_cond_ca_only else 2
-        saved = [{k: torch.zeros((Tr, Bp, self.heads_of(k), hw[k], 1 if j.token is not None else eng.text_len),
-                                 device=dev, dtype=F32) for k in save_keys} for j in jobs]
-
-        for index in range(first_step, last_step):
-            GATE.checkpoint()                                            # lanes.py: another lane may be waiting to capture
-            eng.set_step(index)
-            fuser_on = fuser_at(index)
-            if guided and index < max_guided:
-                pg, gf, gb = runners_guide[fuser_on]
-                self.backward_guidance(gstates, energy, pg, index, st, gf, gb, trace, fuser=fuser_on)
-            runners_main[fuser_on]()
-            self.stats["unet_main"] += 1
-            self._count("main", fuser_on, nb)
-            if save_keys:
-                maps = plans_main[fuser_on].maps
-                for b, j in enumerate(jobs):                              # attention_processor.py:466-476
-                    for k in save_keys:
-                        m = maps[k][nb + b:nb + b + 1] if return_cond_ca_only else maps[k][[b, nb + b]]
-                        saved[b][k][index].copy_(m[..., int(j.token):int(j.token) + 1] if j.token is not None else m)
-        hist = st.hist[:Tr + 1].clone() if save_all_latents else None
-        return [dict(latents=st.lat[b:b + 1].clone(), latents_all=hist[:, b:b + 1] if hist is not None else None,
-                     saved=saved[b], guidance_iters=gstates[b].iterations if gstates[b] is not None else 0,
-                     guidance_iters_fuser_on=gstates[b].iterations_fuser_on if gstates[b] is not None else 0)
-                for b in range(nb)]
+        return first_step, last_step
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()

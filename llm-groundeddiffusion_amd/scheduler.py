@@ -15,7 +15,20 @@ class _Cfg(dict):
     __getattr__ = dict.__getitem__
 
 
+class _StepOutput:
+    """What `step` returns, as far as the reference reads it."""
+
+    def __init__(self, prev_sample):
+        self.prev_sample = prev_sample
+
+
+# `step_kind` of a scheduler class: the fused CFG + step kernel that its coefficient table drives (loop.StepKernel)
+DDIM, MULTISTEP, PLMS = "ddim", "multistep", "plms"
+
+
 class DDIMScheduler:
+    step_kind = DDIM                  # coef_table -> lgd_cfg_ddim_step_f32
+
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
                  steps_offset=1, prediction_type="epsilon"):
         self.config = _Cfg(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
@@ -55,12 +68,7 @@ class DDIMScheduler:
         else:
             x0 = a_t ** 0.5 * sample - (1 - a_t) ** 0.5 * model_output
             e = a_t ** 0.5 * model_output + (1 - a_t) ** 0.5 * sample
-
-        class _O:
-            pass
-        o = _O()
-        o.prev_sample = a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * e
-        return o
+        return _StepOutput(a_p ** 0.5 * x0 + (1 - a_p) ** 0.5 * e)
 
     def coef_table(self, guidance_scale: float, device, timesteps=None, step_ratios=None) -> torch.Tensor:
         """fp32 [T][4] = {alpha_bar_t, alpha_bar_prev, guidance_scale | sqrt(1-alpha_bar_t), v_pred}.
@@ -69,7 +77,6 @@ class DDIMScheduler:
         uses sqrt(1 - alpha_bar_t), exported separately by `guidance_step_table`."""
         ts = self.timesteps if timesteps is None else timesteps
         rows = []
-        n = len(ts)
         for i, t in enumerate(ts):
             t = int(t)
             if step_ratios is not None:
@@ -134,7 +141,7 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
     reading one coefficient row per step (`multistep_table`); nothing about the captured hipGraphs changes.
     Backward guidance scales its latent update by sqrt(1 - alpha_bar_t) as with DDIM: the 0.18.0 class has no
     `sigmas` attribute unless Karras sigmas are switched on (pipelines.py:60-69)."""
-    multistep = True
+    step_kind = MULTISTEP             # multistep_table -> lgd_cfg_multistep_step_f32
 
     def __init__(self, *a, solver_order=2, lower_order_final=True, **k):
         super().__init__(*a, **k)
@@ -210,7 +217,7 @@ class PNDMScheduler(DDIMScheduler):
     Every evaluation is one affine update of (source sample, PLMS combination of the current output and a ring of the
     last three pushed ones), so the device side is the fused `lgd_cfg_plms_step_f32` kernel reading one coefficient
     row per evaluation (`plms_table`); one captured hipGraph replays every evaluation."""
-    plms = True
+    step_kind = PLMS                  # plms_table -> lgd_cfg_plms_step_f32
     # PLMS weights over (newest, ..., oldest) outputs by history length (PNDMScheduler.step_plms)
     ORDER_WEIGHTS = {1: (1.0,), 2: (1.5, -0.5), 3: (23 / 12, -16 / 12, 5 / 12),
                      4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
@@ -306,13 +313,9 @@ class PNDMScheduler(DDIMScheduler):
         """Stateful host form with PNDMScheduler.step's surface (evaluations in schedule order)."""
         if self._host is None:
             self._host = self.host_state(sample)
-
-        class _O:
-            pass
-        o = _O()
-        o.prev_sample = self.step_host(model_output, self.counter, sample, self._host)
+        out = _StepOutput(self.step_host(model_output, self.counter, sample, self._host))
         self.counter += 1
-        return o
+        return out
 
     def coef_table(self, guidance_scale, device, timesteps=None, step_ratios=None):
         raise RuntimeError("PNDMScheduler drives lgd_cfg_plms_step_f32 (plms_table)")
@@ -333,7 +336,7 @@ class EulerDiscreteScheduler:
     so the device side is the fused `lgd_cfg_multistep_step_f32` kernel with rows {1, -sigma, sigma'/sigma,
     1 - sigma'/sigma, 0, guidance_scale, c_in, 0}; c_in = 1/sqrt(sigma^2 + 1) (scale_model_input) is applied by
     `lgd_scale_rows_f32` from the same row."""
-    multistep = True
+    step_kind = MULTISTEP
     C_IN_COL = 6
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
@@ -378,15 +381,15 @@ class EulerDiscreteScheduler:
     def add_noise(self, original, noise, timestep):
         return original + noise * float(self.sigmas[self.index_of(timestep)])
 
-    def multistep_rows(self, first=0):
+    def multistep_rows(self, timesteps=None):
         rows = []
-        for i in range(first, len(self.timesteps)):
+        for i in (range(len(self.timesteps)) if timesteps is None else map(self.index_of, timesteps)):
             s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
             rows.append((1.0, -s, sn / s, 1.0 - sn / s, 0.0, 1.0 / (s * s + 1.0) ** 0.5))
         return rows
 
-    def multistep_table(self, guidance_scale: float, device, first=0) -> torch.Tensor:
-        rows = [[c0, c1, A, B, C, guidance_scale, c_in, 0.0] for c0, c1, A, B, C, c_in in self.multistep_rows(first)]
+    def multistep_table(self, guidance_scale: float, device, timesteps=None) -> torch.Tensor:
+        rows = [[c0, c1, A, B, C, guidance_scale, c_in, 0.0] for c0, c1, A, B, C, c_in in self.multistep_rows(timesteps)]
         return torch.tensor(rows, dtype=torch.float32, device=device)
 
     def step_host(self, model_output, index, sample):

@@ -27,6 +27,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .hostprep import RNG_LOCK
+from .loop import LoopState, StateCache, run_steps
 from .scheduler import EulerDiscreteScheduler
 from .unet import UNetEngine
 
@@ -54,7 +56,7 @@ class SDXLRefiner:
         self.scheduler = scheduler or EulerDiscreteScheduler()
         self.scaling_factor = float(scaling_factor)
         self.use_graphs = use_graphs
-        self._state = {}
+        self._states = StateCache(1)         # one resident (latent size, step count) at a time
 
     # ---- text ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -68,17 +70,6 @@ class SDXLRefiner:
         out = self.text_encoder(ids.to(self.dev), output_hidden_states=True)
         return out.hidden_states[-2], out[0]
 
-    # ---- device state of one (latent size, step count) ------------------------------------------------------------
-    def _get_state(self, L, n_steps):
-        key = (L, n_steps)
-        if key not in self._state:
-            C = self.eng.cfg.in_channels
-            st = dict(lat=torch.zeros((1, C, L, L), device=self.dev, dtype=F32),
-                      x0_prev=torch.zeros((1, C, L, L), device=self.dev, dtype=F32),
-                      tab=torch.zeros((n_steps, 8), device=self.dev, dtype=F32), graph=None)
-            self._state = {key: st}              # one resident size at a time
-        return self._state[key]
-
     @torch.no_grad()
     def refine_latents(self, latents, prompt_embeds, pooled, *, first_index: int, num_inference_steps: int = 50,
                        guidance_scale: float = 5.0, height: int = 1024, width: int = 1024, aesthetic_score: float = 6.0,
@@ -89,35 +80,31 @@ class SDXLRefiner:
         sch.set_timesteps(num_inference_steps)
         ts = [float(t) for t in sch.timesteps[first_index:]]
         n = len(ts)
-        L = latents.shape[-1]
-        st = self._get_state(L, n)
-        st["lat"].copy_(latents.to(self.dev, F32))
-        st["tab"].copy_(sch.multistep_table(guidance_scale, self.dev, first=first_index))
+        C, L = eng.cfg.in_channels, latents.shape[-1]
+        st = self._states.get((L, n), lambda: LoopState(torch.zeros((1, C, L, L), device=self.dev, dtype=F32), n))
+        step = st.step_kernel(sch.step_kind)
+        step.load(sch, guidance_scale, ts)
         eng.prepare_text(prompt_embeds)
         eng.prepare_timesteps(ts, dict(text_embeds=pooled, time_ids=add_time_ids(height, width, aesthetic_score,
                                                                                    negative_aesthetic_score)))
         plan = eng.plan(2, L)
-        lat, tab, x0p = st["lat"], st["tab"], st["x0_prev"]
+        lat = st.lat
 
         def one_step():
             # scale_model_input for the (negative, positive) pair, UNet, classifier-free guidance + Euler update
-            ops.scale_rows(lat, plan.latents_in, tab, eng.dyn, EulerDiscreteScheduler.C_IN_COL, reps=2)
+            ops.scale_rows(lat, plan.latents_in, step.tab, eng.dyn, EulerDiscreteScheduler.C_IN_COL, reps=2)
             plan.forward()
-            ops.cfg_multistep_step(plan.eps_out, lat, lat, x0p, tab, eng.dyn)
-        if self.use_graphs and st["graph"] is None:
-            from .sampler import HipGraph
-            eng.set_step(0)
-            keep = lat.clone()
-            st["graph"] = HipGraph(one_step)     # the capture's warm-up run advanced the latents: restore them
-            lat.copy_(keep)
-        run = st["graph"] if self.use_graphs else one_step
-        from .lanes import GATE
-        for i in range(n):
-            GATE.checkpoint()                    # a safe point per step: another lane's graph capture may proceed
-            eng.set_step(i)
+            step.launch(plan.eps_out, lat, eng.dyn)
+        if self.use_graphs and not st.graphs:
+            eng.set_step(0)                      # the capture's warm-up launch reads the time-embedding row of a valid step
+        run = st.runner("step", one_step, self.use_graphs)
+        lat.copy_(latents.to(self.dev, F32))     # after the capture: its warm-up launch advanced whatever the state held
+
+        def record(i):
             run()
             if trace is not None:
                 trace.append(lat.clone())
+        run_steps(eng, 0, n, record)
         return lat.clone()
 
     @torch.no_grad()
@@ -126,7 +113,6 @@ class SDXLRefiner:
         (sdxl_refinement.py:25: `g = torch.manual_seed(refine_seed)`), scaled, then add_noise at the first timestep.
         The pipeline draws the posterior noise in the VAE's dtype (fp32: config.force_upcast) and the diffusion noise in
         the prompt embeddings' dtype (fp16) — a CPU fp16 draw consumes the generator differently from an fp32 one."""
-        from .hostprep import RNG_LOCK
         mean, logvar = self.enc.encode_moments(image)
         with RNG_LOCK:
             g = torch.manual_seed(int(seed))
