@@ -228,6 +228,23 @@ int lgd_nchw_to_nhwc8_f16(const float* x, void* y, int B, int C, int HW, void* s
 int lgd_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
 /* y = alpha * x (fp16) */
 int lgd_scale_f16(const void* x, void* y, float alpha, int64_t n, void* stream);
+/* uint8 HWC images -> the 8-channel fp16 operand of the VAE encoder's conv_in (additive export: LGD_ABI_VERSION stays
+ * 12) — models/pipelines.py:99-105 of the reference (`encode`: astype(float32) / 255, transpose to NCHW, 2 x - 1)
+ * followed by lgd_nchw_to_nhwc8_f16's layout, in one pass over the bytes:
+ *   x = table[u];  y[pixel] = {fp16(x_r), fp16(x_g), fp16(x_b), fp16(x_r - fp16(x_r)), ..g, ..b, 0, 0}
+ * img: uint8 [B][HW][3]; table: device fp32 [256], written by the host as 2 * (u / 255) - 1 in fp32 with true division
+ * (what numpy computes at :101-104, exactly); y: fp16 [B*HW][8].  B*HW % 4 == 0, img and table 4-byte and y 16-byte
+ * aligned, else LGD_ERR_ARG. */
+int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, void* y, int B, int HW, void* stream);
+/* Sample of the VAE posterior, scaled (additive export, ABI v12) — models/pipelines.py:110-112 of the reference:
+ * vae.encode(image).latent_dist.sample(generator) ([ext] diffusers DiagonalGaussianDistribution: chunk the moments,
+ * clamp logvar to [-30, 20], std = exp(0.5 logvar), mean + std * noise) times vae.config.scaling_factor:
+ *   out = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise)
+ * moments: fp16 [B*HW][2z] as the encoder's last convolution writes them (z means, then z log-variances per pixel);
+ * noise, out: NCHW fp32 (B, z, HW).  z % 4 == 0, HW % 4 == 0, moments 8-byte and noise / out 16-byte aligned, else
+ * LGD_ERR_ARG. */
+int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int B, int z, int HW, float scale,
+                       void* stream);
 /* y = softmax(scale * x) over the last dim, rows x n fp16 (VAE decoder mid-block attention, [ext]
  * AutoencoderKL; pipelines.py:117-127 decode). */
 int lgd_softmax_rows_f16(const void* x, void* y, int64_t rows, int n, float scale, void* stream);

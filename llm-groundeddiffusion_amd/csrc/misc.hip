@@ -472,6 +472,70 @@ __global__ __launch_bounds__(64) void multidiffusion_step_kernel(
   }
 }
 
+// uint8 HWC images [npix][3] -> the 8-channel fp16 operand of the VAE encoder's conv_in (lgd_hip.h): channels 0..2 =
+// fp16(x), 3..5 = fp16(x - fp16(x)), 6..7 zero, x = lut[u] (the host's 2 * (u / 255) - 1 in fp32, pipelines.py:101-104).
+// One thread = 4 pixels: three 4-byte loads (12 bytes), four 16-byte stores.
+__global__ __launch_bounds__(256) void image_u8_to_nhwc8_kernel(const uint32_t* __restrict__ img,
+                                                                 const float* __restrict__ table, half_t* __restrict__ y,
+                                                                 long nquad) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = table[threadIdx.x];
+  __syncthreads();
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < nquad; i += gridDim.x * 256L) {
+    const uint32_t w[3] = {img[3 * i], img[3 * i + 1], img[3 * i + 2]};
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      half8_t o = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int k = 3 * p + c;  // byte k of the 12 (little endian)
+        const float v = lut[(w[k >> 2] >> (8 * (k & 3))) & 255u];
+        const half_t hi = (half_t)v;
+        o[c] = hi;
+        o[c + 3] = (half_t)(v - (float)hi);
+      }
+      reinterpret_cast<half8_t*>(y)[4 * i + p] = o;
+    }
+  }
+}
+
+// DiagonalGaussianDistribution.sample of the VAE encoder's moments, scaled (lgd_hip.h).  moments fp16 [B*HW][2z]
+// (channels-last: z means, then z log-variances), noise / out NCHW fp32 (B, z, HW).  One thread = 4 pixels x 4 channels:
+// eight 8-byte loads of moments, four 16-byte loads of noise, four 16-byte stores.
+__global__ __launch_bounds__(256) void vae_sample_kernel(const half_t* __restrict__ moments,
+                                                          const float* __restrict__ noise, float* __restrict__ out,
+                                                          int z, long HW, float scale, long total) {
+  const long hw4 = HW / 4;
+  const int z4 = z / 4;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const long pq = i % hw4;
+    const int cg = (int)((i / hw4) % z4);
+    const long b = i / (hw4 * z4);
+    const long p0 = pq * 4;
+    f32x4 mean[4], sd[4];  // [pixel][channel of the group]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const half_t* row = moments + ((b * HW + p0 + j) * 2 * z + cg * 4);
+      const half4_t m = *reinterpret_cast<const half4_t*>(row);
+      const half4_t lv = *reinterpret_cast<const half4_t*>(row + z);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        mean[j][c] = (float)m[c];
+        sd[j][c] = expf(0.5f * fminf(fmaxf((float)lv[c], -30.f), 20.f));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long o = (b * z + cg * 4 + c) * HW + p0;
+      const f32x4 nz = *reinterpret_cast<const f32x4*>(noise + o);
+      f32x4 r;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = scale * (mean[j][c] + sd[j][c] * nz[j]);
+      *reinterpret_cast<f32x4*>(out + o) = r;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                          const float* __restrict__ table,
                                                          const int32_t* __restrict__ dyn, int row_stride, int col,
@@ -567,6 +631,31 @@ extern "C" int lgd_nchw_to_nhwc8_f16(const float* x, void* y, int B, int C, int 
   const long total = (long)B * HW;
   hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(ew_blocks(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
                      (half_t*)y, C, (long)HW, total);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, void* y, int B, int HW, void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (!img || !table || !y || B < 1 || HW < 1) return LGD_ERR_ARG;
+  const long npix = (long)B * HW;
+  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if ((npix & 3) || misaligned(img, 4) || misaligned(table, 4) || misaligned(y, 16))
+    return LGD_ERR_ARG;  // four pixels = three whole 4-byte words in, four 16-byte vectors out
+  hipLaunchKernelGGL(image_u8_to_nhwc8_kernel, dim3(ew_blocks(npix / 4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), (const uint32_t*)img, table, (half_t*)y, npix / 4);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int B, int z, int HW, float scale,
+                                  void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (!moments || !noise || !out || B < 1 || z < 4 || HW < 4) return LGD_ERR_ARG;
+  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if ((z & 3) || (HW & 3) || misaligned(moments, 8) || misaligned(noise, 16) || misaligned(out, 16))
+    return LGD_ERR_ARG;  // 8-byte vectors of 4 moments, 16-byte vectors of 4 pixels
+  const long total = (long)B * (z / 4) * (HW / 4);
+  hipLaunchKernelGGL(vae_sample_kernel, dim3(ew_blocks(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     (const half_t*)moments, noise, out, z, (long)HW, scale, total);
   return lgd_check_launch();
 }
 

@@ -7,7 +7,7 @@ import torch
 
 from lgd_amd import weights as _weights
 from lgd_amd.sampler import LMDSampler
-from lgd_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+from lgd_amd.scheduler import DDIMInverseScheduler, DDIMScheduler, DPMSolverMultistepScheduler
 from lgd_amd.unet import UNetEngine
 from utils import torch_device  # noqa: F401
 
@@ -25,8 +25,10 @@ class _EasyDict(dict):
 
 
 def build_model_dict(cfg, state_dict, vae=None, tokenizer=None, text_encoder=None, device="cuda",
-                     dtype=torch.float16, scheduler_config=None, use_dpm_multistep_scheduler=False):
-    """model_dict contract of models/models.py:55: vae, tokenizer, text_encoder, unet, scheduler, dtype.
+                     dtype=torch.float16, scheduler_config=None, use_dpm_multistep_scheduler=False,
+                     load_inverse_scheduler=False):
+    """model_dict contract of models/models.py:55: vae, tokenizer, text_encoder, unet, scheduler, dtype, and with
+    load_inverse_scheduler (models/models.py:57-59) `inverse_scheduler` = DDIMInverseScheduler.from_config(scheduler.config).
     scheduler_config: the checkpoint's own scheduler_config.json fields (models/models.py:49 reads them through
     DDIMScheduler.from_pretrained); only what the DDIM eta=0 path uses is honoured, anything else must match."""
     eng = UNetEngine(cfg, device, state_dict)
@@ -45,23 +47,28 @@ def build_model_dict(cfg, state_dict, vae=None, tokenizer=None, text_encoder=Non
         sched = DDIMScheduler(steps_offset=sc.get("steps_offset", 1), **skw)
     md = _EasyDict(vae=vae, tokenizer=tokenizer, text_encoder=text_encoder, unet=unet, scheduler=sched, dtype=dtype)
     md["sampler"] = LMDSampler(eng, sched, vae=vae)
+    if load_inverse_scheduler:
+        md["inverse_scheduler"] = DDIMInverseScheduler.from_config(sched.config)
     return md
 
 
-def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True):
-    """Seeded random weights of the exact architecture (no checkpoints in the sandbox)."""
-    from lgd_amd.vae import make_hip_vae
+def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True, load_inverse_scheduler=False):
+    """Seeded random weights of the exact architecture (no checkpoints in the sandbox).  The VAE is make_hip_vae's decoder
+    with the encoder of the same state dict behind it (built when pipelines.encode first asks for it)."""
+    from lgd_amd.vae import make_hip_vae_pair
     cfg = _weights.CONFIGS[name]
-    return build_model_dict(cfg, _weights.synth_state_dict(cfg, seed), vae=make_hip_vae(device) if with_vae else None,
-                            device=device)
+    return build_model_dict(cfg, _weights.synth_state_dict(cfg, seed), vae=make_hip_vae_pair(device) if with_vae else None,
+                            device=device, load_inverse_scheduler=load_inverse_scheduler)
 
 
 def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_scheduler=False,
             use_dpm_multistep_scheduler=False, scheduler_cls=None):
     """models/models.py:16-62.  Needs the Hugging Face checkpoint (diffusers + network/cache); the UNet
     state dict is repacked into the HIP engine's arenas, the CLIP text tower runs on the HIP kernels
-    (lgd_amd.clip), the VAE decoder's state dict is repacked for the HIP kernels (lgd_amd.vae.HipVAEDecoder;
-    LGD_HF_VAE=1 in the environment keeps the Hugging Face module, for A/B checks against it)."""
+    (lgd_amd.clip), the VAE's state dict is repacked for the HIP kernels (lgd_amd.vae.HipVAE: the decoder at once, the
+    encoder when pipelines.encode first needs it; LGD_HF_VAE=1 in the environment keeps the Hugging Face module, for A/B
+    checks against it).  load_inverse_scheduler (models/models.py:57-59): model_dict.inverse_scheduler for
+    pipelines.invert."""
     if not use_fp16:      # models/models.py:33-38: the reference then loads fp32 weights ("run final results in fp32")
         from generation._common import note_precision
         note_precision("models.load_sd", "use_fp16=False")
@@ -97,16 +104,23 @@ def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_s
         te = _hip_text_encoder(te, torch_device)         # HIP kernels: fp16 compute, 2-3e-3 of the fp32 tower's states
 
     class _HFVae:
+        config = vae.config
+
         def decode(self, z):
             return vae.decode(z.to(vae.dtype)).sample
+
+        def encode(self, image):
+            return vae.encode(image.to(vae.dtype))
     if _os.environ.get("LGD_HF_VAE", "0") == "1":
         dec = _HFVae()
     else:
-        from lgd_amd.vae import HipVAEDecoder
-        dec = HipVAEDecoder.from_state_dict(vae.state_dict(), torch_device)      # models/models.py:41 on the HIP kernels
+        from lgd_amd.vae import HipVAE
+        dec = HipVAE.from_state_dict(vae.state_dict(), torch_device,             # models/models.py:41 on the HIP kernels
+                                     scaling_factor=getattr(vae.config, "scaling_factor", 0.18215))
     return build_model_dict(cfg, {k: v.float() for k, v in hf.state_dict().items()}, vae=dec, tokenizer=tok,
                             text_encoder=te, scheduler_config=sched_cfg,
-                            use_dpm_multistep_scheduler=use_dpm_multistep_scheduler)
+                            use_dpm_multistep_scheduler=use_dpm_multistep_scheduler,
+                            load_inverse_scheduler=load_inverse_scheduler)
 
 
 def encode_prompts(tokenizer, text_encoder, prompts, negative_prompt="", return_full_only=False,

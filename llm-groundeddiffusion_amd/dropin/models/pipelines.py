@@ -6,7 +6,10 @@ gligen_enable_fuser :280-283, prepare_gligen_condition :285-321, generate_gligen
 generate_partial_frozen :541-599, and their `use_boxdiff=True` branch (:187-188, :564-565: one gradient step on the
 BoxDiff energy of utils/boxdiff.py per denoising step, csrc/boxdiff.hip), and generate :250-279 (the plain CFG loop,
 under the DDIM, DPM-Solver++ or PNDM scheduler found at `model_dict[scheduler_key]`; PNDM runs the fused PLMS step of
-csrc/misc.hip).  Not on the hot path and not provided: encode / invert (DDIM inversion, unused by LMD / LMD+)."""
+csrc/misc.hip), and DDIM inversion: encode :84-114 (the HIP VAE encoder; lgd_image_u8_to_nhwc8_f16 and
+lgd_vae_sample_f32 of csrc/misc.hip, so that no torch arithmetic sits between the uint8 image and the scaled latents),
+get_inverse_timesteps :476-487 and invert :489-539 (lgd_amd.pipeline.invert_batch under `model_dict.inverse_scheduler`,
+which load_sd / build_model_dict / load_synthetic attach with load_inverse_scheduler=True)."""
 import numpy as np
 import torch
 
@@ -125,6 +128,26 @@ def decode(vae, latents):
     image = (image / 2 + 0.5).clamp(0, 1)
     image = image.detach().float().cpu().permute(0, 2, 3, 1).numpy()
     return (image * 255).round().astype("uint8")
+
+
+@torch.no_grad()
+def encode(model_dict, image, generator):
+    """pipelines.py:84-114: a PIL image or a uint8 HWC array (0 .. 255), or a float tensor (B, 3, H, W) in [-1, 1] ->
+    vae.config.scaling_factor * vae.encode(image).latent_dist.sample(generator), (B, z, H/8, W/8) fp32 on the device.
+    The uint8 forms go to the device as bytes.  Square images only, as the HIP encoder is."""
+    vae = model_dict.vae
+    if hasattr(image, "size") and hasattr(image, "mode") and not isinstance(image, (np.ndarray, torch.Tensor)):   # PIL
+        w, h = image.size
+        assert w % 8 == 0 and h % 8 == 0, f"h ({h}) and w ({w}) should be a multiple of 8"
+        image = np.array(image)
+    if isinstance(image, np.ndarray):
+        assert image.dtype == np.uint8, f"Should have dtype uint8 (dtype: {image.dtype})"
+        image = torch.from_numpy(np.ascontiguousarray(image))[None, ...]              # (1, H, W, 3) bytes
+    assert isinstance(image, torch.Tensor), f"type of image: {type(image)}"
+    dist = vae.encode(image).latent_dist
+    if hasattr(dist, "moments"):                       # lgd_amd.vae.HipLatentDist: the scale rides in the sample launch
+        return dist.sample(generator, scale=vae.config.scaling_factor)
+    return vae.config.scaling_factor * dist.sample(generator)
 
 
 def gligen_enable_fuser(unet, enabled=True):
@@ -255,6 +278,29 @@ def generate_partial_frozen(model_dict, latents_all, frozen_mask, input_embeddin
                    frozen_steps=frozen_steps, frozen_mask=frozen_mask, save_all_latents=False)
     images = decode(model_dict.vae, r["latents"]) if model_dict.vae is not None else None
     return r["latents"], images
+
+
+def get_inverse_timesteps(inverse_scheduler, num_inference_steps, strength):
+    """pipelines.py:476-487 -> (timesteps, steps): the first `int(steps * strength)` entries of the inverse schedule."""
+    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = max(num_inference_steps - init_timestep, 0)
+    if t_start == 0:
+        return inverse_scheduler.timesteps, num_inference_steps
+    return inverse_scheduler.timesteps[:-t_start], num_inference_steps - t_start
+
+
+@torch.no_grad()
+def invert(model_dict, latents, input_embeddings, num_inference_steps, guidance_scale=7.5):
+    """pipelines.py:489-539 -> inverted latents of all timesteps, (T, B, C, L, L) on the CPU: [0] the noisiest,
+    [T - 1] the input.  latents: encoded from the image, without noise.  Every image of the batch is an independent job."""
+    from lgd_amd.pipeline import invert_batch
+    sm = _sampler(model_dict)
+    text_embeddings, _, _ = input_embeddings
+    n = latents.shape[0]
+    texts = [torch.stack([text_embeddings[i], text_embeddings[n + i]]) for i in range(n)]
+    out = invert_batch(sm, texts, latents.float(), num_inference_steps, guidance_scale=guidance_scale,
+                       inverse_scheduler=model_dict.inverse_scheduler)
+    return out.to(latents.dtype).cpu()
 
 
 @torch.no_grad()

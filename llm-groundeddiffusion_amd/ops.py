@@ -411,6 +411,41 @@ def nchw_to_nhwc8(x_nchw, out=None):
     return out
 
 
+_U8_TABLES = {}
+
+
+def u8_table(device) -> torch.Tensor:
+    """fp32 [256] = 2 * (u / 255) - 1, computed by the host in fp32 with true division (pipelines.py:101-104: numpy's
+    astype(float32) / 255.0, then 2.0 * x - 1.0) — the table lgd_image_u8_to_nhwc8_f16 reads."""
+    key = str(device)
+    if key not in _U8_TABLES:
+        u = torch.arange(256, dtype=F32)
+        _U8_TABLES[key] = (2.0 * (u / 255.0) - 1.0).to(device)
+    return _U8_TABLES[key]
+
+
+def image_u8_to_nhwc8(img_u8, out=None):
+    """uint8 (B, H, W, 3) on the device -> [B*H*W, 8] fp16: value, rounding remainder, zeros (lgd_hip.h)."""
+    B, H, W, C_ = img_u8.shape
+    if C_ != 3 or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
+        raise RuntimeError("image_u8_to_nhwc8 takes a contiguous uint8 (B, H, W, 3) tensor")
+    if out is None:
+        out = torch.empty((B * H * W, 8), device=img_u8.device, dtype=F16)
+    _call("lgd_image_u8_to_nhwc8_f16", _p(img_u8), _p(u8_table(img_u8.device)), _p(out), B, H * W, _stream())
+    return out
+
+
+def vae_sample(moments, noise, scale, out=None):
+    """moments fp16 [B*HW, 2z] (channels-last), noise fp32 (B, z, H, W) -> scale * (mean + std * noise), NCHW fp32."""
+    B, z, H, W = noise.shape
+    if tuple(moments.shape) != (B * H * W, 2 * z) or moments.dtype != F16 or noise.dtype != F32:
+        raise RuntimeError(f"vae_sample: moments {tuple(moments.shape)} {moments.dtype} for noise {tuple(noise.shape)}")
+    if out is None:
+        out = torch.empty_like(noise)
+    _call("lgd_vae_sample_f32", _p(moments), _p(noise), _p(out), B, z, H * W, float(scale), _stream())
+    return out
+
+
 def conv_out(x, w, bias, B, L, out=None, out_scale=1.0):
     Cin = x.shape[1]
     Cout = w.shape[0]

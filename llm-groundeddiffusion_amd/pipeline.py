@@ -19,7 +19,7 @@ from .hostprep import (align_with_bboxes, compose as compose_latents, get_center
                        input_latents_list as _input_latents_list, proportion_to_mask, seeded_noise, shift_tensor)
 from .sampler import (BOXDIFF_GUIDANCE_ATTN_KEYS, DEFAULT_GUIDANCE_ATTN_KEYS, Job, LMDSampler,
                       prepare_gligen_condition)
-from .scheduler import PNDMScheduler
+from .scheduler import DDIMInverseScheduler, PNDMScheduler
 from .weights import UNetConfig
 
 F32 = torch.float32
@@ -431,3 +431,31 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     if save_all_latents:
         return lat, images, [r["latents_all"] for r in res]
     return lat, images
+
+
+def invert_batch(sampler: LMDSampler, texts, latents, num_inference_steps=50, guidance_scale=7.5, inverse_scheduler=None):
+    """DDIM inversion (models/pipelines.py:489-539, `invert` with strength 1.0): the clean latents of real images are
+    stepped up the first T - 1 entries of the inverse schedule under classifier-free guidance, every state kept — the
+    per-timestep latents generate_partial_frozen freezes into a generation.  The loop is `denoise_batch` under a
+    scheduler.DDIMInverseScheduler (by default the one next to the sampler's scheduler), on the fused DDIM step kernel and
+    the captured graphs of every other run; independent images share UNet calls.
+
+    guidance_scale == 0: the reference evaluates the unconditional branch alone (:518-528).  Here the CFG pair runs with
+    scale 0 — eu + 0 * (ec - eu) is eu — so no one-row plan and graph exist for this case alone.
+
+    texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor (encoded, scaled,
+    no noise).  Returns fp32 (T,N,C,L,L) on the sampler's device: index 0 the noisiest state, index T - 1 the input
+    (pipelines.py:503,533-537)."""
+    sch = DDIMInverseScheduler.from_config(sampler.scheduler) if inverse_scheduler is None else inverse_scheduler
+    if not getattr(sch, "inverse", False):
+        raise TypeError("invert_batch needs a scheduler.DDIMInverseScheduler")
+    T = int(num_inference_steps)
+    starts = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
+    if len(starts) != len(texts):
+        raise ValueError(f"{len(texts)} texts for {len(starts)} latents")
+    jobs = [Job(torch.as_tensor(lat).float(), txt) for lat, txt in zip(starts, texts)]
+    # a scale <= 0 means "no guidance" to the reference (`if guidance_scale > 0.`): the unconditional prediction
+    res = sampler.denoise_batch(jobs, T, guidance_scale=max(float(guidance_scale), 0.0), scheduler=sch, n_steps=T - 1,
+                                save_all_latents=True)
+    # rows 0 .. T - 1 of each history are the ones this call wrote (the start and T - 1 steps); noisiest first
+    return torch.cat([r["latents_all"][:T] for r in res], dim=1).flip(0)

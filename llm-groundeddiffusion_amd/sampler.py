@@ -407,7 +407,8 @@ class LMDSampler:
         scheduler: this call's scheduler instead of the sampler's own — a PNDMScheduler runs the plain CFG loop of
           pipelines.py:257-273 under PLMS, whose schedule has more UNet evaluations than steps (n + 1); the state, the
           tables and the history then follow the evaluation count, and guidance, GLIGEN, frozen steps, the fast schedule
-          and first_step > 0 are refused.
+          and first_step > 0 are refused.  A DDIMInverseScheduler (pipeline.invert_batch) runs its ascending schedule on
+          the DDIM step kernel under the same refusals; with n_steps = T - 1 the history rows 0 .. T - 1 are this call's.
         Returns per job dict(latents (1,C,L,L), latents_all (T_run+1,1,C,L,L), saved {key: [T_run,Bp,H,HW,Tp]},
         guidance_iters).
         """
@@ -417,7 +418,8 @@ class LMDSampler:
         starts = [j.latents[0] if j.latents.dim() == 5 else j.latents for j in jobs]
         _, C, L, _ = starts[0].shape
         self._refuse_undefined(sch.step_kind, fast=fast_after_steps is not None, partial=int(first_step) > 0,
-                               conditioned=frozen_steps > 0 or use_gligen or any(j.guidance is not None for j in jobs))
+                               conditioned=frozen_steps > 0 or use_gligen or any(j.guidance is not None for j in jobs),
+                               inverse=getattr(sch, "inverse", False))
         st, ts, step = self._load_schedule(sch, nb, C, L, num_inference_steps, guidance_scale, fast_after_steps, fast_rate)
         Tr = len(ts)                                                          # steps actually run
         n_ground = int(gligen_scheduled_sampling_beta * Tr) if use_gligen else 0   # pipelines.py:405
@@ -466,8 +468,11 @@ class LMDSampler:
 
     # ---- the phases of _denoise_chunk, in its order
     @staticmethod
-    def _refuse_undefined(kind, *, fast, partial, conditioned):
-        """What a step kernel does not define is an error, not a fall-back."""
+    def _refuse_undefined(kind, *, fast, partial, conditioned, inverse=False):
+        """What a step kernel does not define is an error, not a fall-back.  inverse: a DDIMInverseScheduler drives it."""
+        if inverse and (fast or partial or conditioned):
+            raise RuntimeError("DDIMInverseScheduler runs the plain CFG loop only (pipelines.py:489-539): guidance, GLIGEN, "
+                               "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
         if kind == PLMS and (fast or partial or conditioned):
             raise RuntimeError("PNDMScheduler runs the plain CFG loop only (pipelines.py:257-273): guidance, GLIGEN, "
                                "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
@@ -489,7 +494,8 @@ class LMDSampler:
             ts = sch.fast_schedule(ts, int(fast_after_steps), int(fast_rate))
         step = st.step_kernel(sch.step_kind)
         step.load(sch, guidance_scale, ts)
-        st.gtab[:len(ts)].copy_(sch.guidance_step_table(self.dev, timesteps=ts))
+        if not getattr(sch, "inverse", False):                               # inversion is never guided (_refuse_undefined)
+            st.gtab[:len(ts)].copy_(sch.guidance_step_table(self.dev, timesteps=ts))
         return st, ts, step
 
     def _guidance_states(self, jobs, L, st, Tr):

@@ -130,6 +130,79 @@ class DDIMScheduler:
 
 
 
+class DDIMInverseScheduler(DDIMScheduler):
+    """[ext] diffusers 0.18.0 DDIMInverseScheduler as `DDIMInverseScheduler.from_config(scheduler.config)` makes it next to
+    the DDIM scheduler of an SD checkpoint (models/models.py:57-59): clip_sample=False, eta 0, epsilon and v_prediction —
+    the scheduler of models/pipelines.py:489-539 (`invert`).  diffusers is absent from the sandbox: restated from the
+    published class, parity unpinned at this boundary; pinned against a line-for-line stateful restatement
+    (tests/ddim_inverse_restate.py) and, step by step, against DDIMScheduler.step, which undoes it for a fixed model output.
+
+    One inversion step is the DDIM step with the noise levels taken in the other direction,
+        x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t) ;  x' = sqrt(a_next) x0 + sqrt(1 - a_next) e,   t_next = t + N_train // n,
+    so `coef_table` rows are {alpha_bar_t, alpha_bar_next, guidance_scale, v flag} and `lgd_cfg_ddim_step_f32` runs them
+    unchanged.  Final alpha: the DDIM config's set_alpha_to_one=False reaches the 0.18.0 class through its deprecated
+    keyword as set_alpha_to_zero=False, i.e. final_alpha_cumprod = alphas_cumprod[-1] (not 0) when t_next >= N_train.
+    `invert` never takes the last timestep of the schedule, so that value is unreachable from it."""
+    inverse = True                    # sampler.LMDSampler._refuse_undefined: the plain CFG loop only
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
+                 prediction_type="epsilon"):
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"DDIMInverseScheduler: prediction_type {prediction_type!r}")
+        super().__init__(num_train_timesteps, beta_start, beta_end, steps_offset, prediction_type)
+        self.config.update(set_alpha_to_zero=False)
+        self.final_alpha_cumprod = self.alphas_cumprod[-1]
+
+    @classmethod
+    def from_config(cls, scheduler):
+        """The inverse scheduler next to `scheduler` (model_dict.scheduler, or its `config`): the same betas, train step
+        count, steps_offset and prediction type."""
+        c = scheduler if isinstance(scheduler, dict) else scheduler.config
+        return cls(c.num_train_timesteps, c.beta_start, c.beta_end, steps_offset=c.steps_offset,
+                   prediction_type=c.prediction_type)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = num_inference_steps
+        ratio = self.config.num_train_timesteps // num_inference_steps
+        ts = (np.arange(0, num_inference_steps) * ratio).round().copy().astype(np.int64)
+        self.timesteps = torch.from_numpy(ts) + self.config.steps_offset
+
+    def next_timestep(self, t):
+        return int(t) + self.config.num_train_timesteps // self.num_inference_steps
+
+    def prev_timestep(self, t, index=None):
+        """The timestep `step` moves to (the class keeps DDIM's name for it): the NEXT, noisier one."""
+        return self.next_timestep(t)
+
+    def alpha_pair(self, t):
+        nxt = self.next_timestep(t)
+        a_n = float(self.alphas_cumprod[nxt]) if nxt < self.config.num_train_timesteps else float(self.final_alpha_cumprod)
+        return float(self.alphas_cumprod[int(t)]), a_n
+
+    def coef_table(self, guidance_scale: float, device, timesteps=None, step_ratios=None) -> torch.Tensor:
+        """fp32 [T][4] = {alpha_bar_t, alpha_bar_next, guidance_scale, v_pred}: lgd_cfg_ddim_step_f32's rows."""
+        if step_ratios is not None:
+            raise RuntimeError("DDIMInverseScheduler: per-step sizes belong to the fast schedule of descending DDIM runs")
+        ts = self.timesteps if timesteps is None else timesteps
+        v = 1.0 if self.config.prediction_type == "v_prediction" else 0.0
+        return torch.tensor([[*self.alpha_pair(t), guidance_scale, v] for t in ts], dtype=torch.float32, device=device)
+
+    def dynamic_step_sizes(self, timesteps):
+        """None: the step size is N_train // n at every index (utils/schedule.py only re-derives descending schedules)."""
+        return None
+
+    @staticmethod
+    def fast_schedule(timesteps, fast_after_steps, fast_rate=2):
+        raise RuntimeError("the fast schedule (utils/schedule.py) is not defined for DDIM inversion")
+
+    def add_noise(self, original, noise, timestep):
+        raise RuntimeError("DDIMInverseScheduler has no add_noise (the 0.18.0 class has none)")
+
+    def guidance_step_table(self, device, timesteps=None) -> torch.Tensor:
+        raise RuntimeError("DDIMInverseScheduler inverts with the plain CFG loop (pipelines.py:489-539): backward guidance "
+                           "is not defined under it")
+
+
 class DPMSolverMultistepScheduler(DDIMScheduler):
     """[ext] diffusers 0.18.0 DPMSolverMultistepScheduler with its defaults (algorithm_type "dpmsolver++",
     solver_order 2, solver_type "midpoint", lower_order_final, no thresholding) — what `load_sd(...,

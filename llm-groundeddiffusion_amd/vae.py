@@ -174,6 +174,11 @@ def make_hip_vae(device, seed=0):
     return HipVAEDecoder(synth_aekl_state_dict(seed=seed), device)
 
 
+def make_hip_vae_pair(device, seed=0):
+    """make_hip_vae's decoder with the encoder of the same seeded state dict behind it (HipVAE: built on first use)."""
+    return HipVAE(synth_aekl_state_dict(seed=seed), device)
+
+
 def synth_aekl_state_dict(ch=(128, 256, 512, 512), layers=2, latent_channels=4, seed=0, legacy_attention_names=False):
     """A full AutoencoderKL state dict (encoder + quant_conv + post_quant_conv + decoder, diffusers key names) with
     seeded random parameters of the SD / SDXL VAE architecture: there are no checkpoints in the sandbox."""
@@ -297,17 +302,14 @@ class HipVAEEncoder(HipVAEDecoder):
         self.conv_out = (h16(pack_conv(w_o)), f32(b_o))
 
     @torch.no_grad()
-    def encode_moments(self, image):
-        """image [B, 3, H, W] fp32 in [-1, 1] -> (mean, logvar) fp32 [B, z, H/8, W/8]; logvar clamped to [-30, 20]
-        (DiagonalGaussianDistribution)."""
+    def moments_nhwc(self, x8, B, H):
+        """The encoder from its conv_in operand x8 (fp16 [B*H*H, 8]: value, rounding remainder, zeros; what
+        lgd_nchw_to_nhwc8_f16 / lgd_image_u8_to_nhwc8_f16 write) -> fp16 moments [B*(H/8)^2, 2z], channels-last: z means,
+        then z log-variances (unclamped) per latent pixel."""
         ops = self.ops
-        x = image.to(self.dev, torch.float32).contiguous()
-        B, _, H, W = x.shape
-        if H != W:
-            raise RuntimeError("square images only (the refiner pass resizes to 1024 x 1024, sdxl_refinement.py:26)")
         c0 = self.conv_in[0].shape[0]
         h = torch.empty((B * H * H, c0), device=self.dev, dtype=torch.float16)
-        ops.gemm_launch(ops.gemm_desc(ops.nchw_to_nhwc8(x), self.conv_in[0], h, B * H * H, c0, 72, c0=8, lda0=8, taps=9,
+        ops.gemm_launch(ops.gemm_desc(x8, self.conv_in[0], h, B * H * H, c0, 72, c0=8, lda0=8, taps=9,
                                       hin=H, win=H, hout=H, wout=H, bias=self.conv_in[1], ldc=c0, splits=1))
         for blk, down in self.downs:
             for r in blk:
@@ -321,10 +323,105 @@ class HipVAEEncoder(HipVAEDecoder):
         h = self._attn(self.attn, h, B, H)
         h = self._res(self.mid[1], h, B, H)
         h = ops.groupnorm(h, B, H * H, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
-        m = ops.conv3x3(h, self.conv_out[0], B, H, H, bias=self.conv_out[1])          # [B*H*H, 2z] fp16
+        return ops.conv3x3(h, self.conv_out[0], B, H, H, bias=self.conv_out[1])       # [B*H*H, 2z] fp16
+
+    @torch.no_grad()
+    def encode_moments(self, image):
+        """image [B, 3, H, W] fp32 in [-1, 1] -> (mean, logvar) fp32 [B, z, H/8, W/8]; logvar clamped to [-30, 20]
+        (DiagonalGaussianDistribution)."""
+        x = image.to(self.dev, torch.float32).contiguous()
+        B, _, H, W = x.shape
+        if H != W:
+            raise RuntimeError("square images only (the refiner pass resizes to 1024 x 1024, sdxl_refinement.py:26)")
+        m = self.moments_nhwc(self.ops.nchw_to_nhwc8(x), B, H)
+        H = int(round((m.shape[0] // B) ** 0.5))
         m = m.view(B, H, H, self.n_moments).permute(0, 3, 1, 2).float()
         mean, logvar = m.chunk(2, dim=1)
         return mean.contiguous(), logvar.clamp(-30.0, 20.0).contiguous()
 
     def decode(self, z):
         raise RuntimeError("HipVAEEncoder encodes; use HipVAEDecoder for decode")
+
+
+class _Config(dict):
+    __getattr__ = dict.__getitem__
+
+
+class HipLatentDist:
+    """`vae.encode(image).latent_dist` as far as models/pipelines.py:110 reads it ([ext] diffusers
+    DiagonalGaussianDistribution): the encoder's fp16 moments, still on the device and channels-last; `sample` draws the
+    noise as [ext] randn_tensor does — by torch, from the caller's generator on the generator's own device, shaped like
+    the mean — and one lgd_vae_sample_f32 launch does the rest."""
+
+    def __init__(self, ops, moments, shape):
+        self.ops, self.moments, self.shape = ops, moments, tuple(shape)        # shape: (B, z, H, W) of the mean
+
+    def _nchw(self):
+        B, z, H, W = self.shape
+        return self.moments.view(B, H, W, 2 * z).permute(0, 3, 1, 2).float()
+
+    @property
+    def mean(self):
+        return self._nchw()[:, :self.shape[1]].contiguous()
+
+    @property
+    def logvar(self):
+        return self._nchw()[:, self.shape[1]:].clamp(-30.0, 20.0).contiguous()
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, generator=None, scale=1.0):
+        """mean + std * noise; `scale` (not in diffusers' signature) folds vae.config.scaling_factor into the launch."""
+        dev = self.moments.device
+        rand_dev = generator.device if generator is not None else dev
+        noise = torch.randn(self.shape, generator=generator, device=rand_dev, dtype=torch.float32)
+        return self.ops.vae_sample(self.moments, noise.to(dev).contiguous(), scale)
+
+
+class HipEncoderOutput:
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+class HipVAE(HipVAEDecoder):
+    """The VAE object of `model_dict` (models/models.py:41): HipVAEDecoder's `decode`, unchanged, plus `encode(image)
+    .latent_dist.sample(generator)` and `config.scaling_factor` as models/pipelines.py:84-114 (`encode`) reads them.  The
+    encoder is a HipVAEEncoder over the same AutoencoderKL state dict, built on first use (a generation-only run never
+    packs it)."""
+
+    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215):
+        super().__init__(source, device, groups, eps)
+        sd = source.aekl_state_dict() if hasattr(source, "aekl_state_dict") else dict(source)
+        self._encoder_sd = {k: v for k, v in sd.items() if k.startswith(("encoder.", "quant_conv."))}
+        self._encoder = None
+        self.config = _Config(scaling_factor=scaling_factor)
+
+    @property
+    def encoder(self) -> "HipVAEEncoder":
+        if self._encoder is None:
+            if "encoder.conv_in.weight" not in self._encoder_sd:
+                raise RuntimeError("this VAE was built from a state dict without encoder weights: it cannot encode")
+            self._encoder = HipVAEEncoder(self._encoder_sd, self.dev, self.groups, self.eps)
+            self._encoder_sd = None
+        return self._encoder
+
+    @torch.no_grad()
+    def encode(self, image):
+        """image: uint8 (B, H, W, 3) — the bytes go to the device as they are and lgd_image_u8_to_nhwc8_f16 writes the
+        conv_in operand — or float (B, 3, H, W) in [-1, 1] (lgd_nchw_to_nhwc8_f16, as the refiner pass does).  Square
+        images with a side that is a multiple of 8."""
+        ops, enc = self.ops, self.encoder
+        image = torch.as_tensor(image)
+        if image.dim() != 4:
+            raise RuntimeError(f"encode takes a batch of images, got shape {tuple(image.shape)}")
+        if image.dtype == torch.uint8:
+            B, H, W, _ = image.shape
+            x8 = ops.image_u8_to_nhwc8(image.to(self.dev).contiguous()) if H == W and H % 8 == 0 else None
+        else:
+            B, _, H, W = image.shape
+            x8 = ops.nchw_to_nhwc8(image.to(self.dev, torch.float32).contiguous()) if H == W and H % 8 == 0 else None
+        if x8 is None:
+            raise RuntimeError(f"square images with a side that is a multiple of 8 only (got {H} x {W})")
+        m = enc.moments_nhwc(x8, B, H)
+        return HipEncoderOutput(HipLatentDist(ops, m, (B, enc.n_moments // 2, H // 8, W // 8)))
