@@ -39,8 +39,13 @@ int lgd_abi_version(void);
  * (image, groups) slab of x and gy in registers (<= 96 KB: the 8x8 and 16x16 maps), 0 = two launches.  "ln_stream": 1 =
  * (default) the statistics-only form of lgd_layernorm_f16 (y = NULL) runs the streaming kernel (lane groups share a row),
  * 0 = the one-wave-per-row kernels.  "gn_apply_wgs" (tools): the number of workgroups per launch the GroupNorm apply passes
- * aim at, 64 .. 8192, default 1024.  Returns 0, or LGD_ERR_ARG for an unknown name. */
+ * aim at, 64 .. 8192, default 1024.  "cfg_pair": 1 = (default) launch plans of a classifier-free-guidance batch
+ * compute the ops in front of the first text / grounding-token read once per pair (LgdGemmDesc.pair, lgd_*_pair_f16),
+ * 0 = twice, as before; read by the plan builder when a plan is built (lgd_get_option), the kernels themselves always do
+ * what a call asks.  Returns 0, or LGD_ERR_ARG for an unknown name. */
 int lgd_set_option(const char* name, int value);
+/* Current value of an option the host side reads back ("cfg_pair"), or LGD_ERR_ARG (negative) for any other name. */
+int lgd_get_option(const char* name);
 
 /* ---------------------------------------------------------------------------------------------
  * GEMM / implicit-GEMM convolution on MFMA (v_mfma_f32_16x16x32_f16).
@@ -102,7 +107,18 @@ typedef struct LgdGemmDesc {
                          launch (splitk_reduce_kernel).  One counter buffer may serve every GEMM of a stream. */
   const float* rowstat; /* LGD_EPI_ROWNORM: fp32 [M][2] = (mean, rstd) of every A row (lgd_layernorm_f16 with y = NULL) */
   const float* colsum;  /* LGD_EPI_ROWNORM: fp32 [N] = row sums of the (gamma-scaled) weight matrix as stored          */
+  int32_t pair;         /* CFG pair mode, 0 = off (field appended behind the v12 layout: LGD_ABI_VERSION stays 12, callers
+                           are rebuilt against this header): rows m and m + M/2 of A (and of res / rowstat) are IDENTICAL — the
+                           classifier-free-guidance batch [uncond; cond] in front of the first op that reads text or
+                           grounding tokens (pipelines.py:436-441 duplicates the latents).  Only rows m < M/2 are computed
+                           (tile walk and grid cover M/2 rows; res, rowstat are read for row m only), with the tile the
+                           full launch would take: results are bit-identical to it.  LGD_PAIR_HALF: rows >= M/2 of C are
+                           left untouched; LGD_PAIR_DUP: every stored piece is also stored at row m + M/2.  Needs
+                           splits == 1, nb_o * nb_i == 1 and an even M (for a convolution M/2 is then a whole number
+                           of images), else LGD_ERR_ARG. */
 } LgdGemmDesc;
+#define LGD_PAIR_HALF 1
+#define LGD_PAIR_DUP 2
 
 int lgd_gemm_f16(const LgdGemmDesc* desc /* host */, void* stream);
 /* lgd_gemm_check (ABI v11): LGD_OK exactly when lgd_gemm_f16 would launch `desc`, else LGD_ERR_ARG — the same check
@@ -133,6 +149,12 @@ int lgd_conv_out_f16(const void* x, const void* w, const float* bias, float* y_n
 int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G,
                       float eps, const float* gamma, const float* beta, int silu, void* y,
                       float* part, int nchunk, float* stats, void* stream);
+/* CFG pair form (additive export: LGD_ABI_VERSION stays 12; see LgdGemmDesc.pair): images b and b + B/2 of x are identical, images b < B/2 are normalised,
+ * with the launch geometry of the full call (bit-identical).  LGD_PAIR_HALF: images >= B/2 of y are left untouched;
+ * LGD_PAIR_DUP: every stored piece is also stored for image b + B/2.  No statistics output (no-grad forward only). */
+int lgd_groupnorm_pair_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G,
+                           float eps, const float* gamma, const float* beta, int silu, void* y,
+                           float* part, int nchunk, int pair, void* stream);
 /* backward of the above w.r.t. x: gy [B][HW][C] -> gx0 (c0 channels, row stride c0) and gx1.
  * accumulate!=0 adds into gx (gradient fan-in). */
 int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void* x1, int c0, int c1, int B,
@@ -146,6 +168,11 @@ int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void* x1, int c0
 int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C, float eps,
                       const float* gamma, const float* beta, float* stats, int rows_per_batch,
                       int64_t x_bs, int64_t y_bs, void* stream);
+/* CFG pair form (additive export: LGD_ABI_VERSION stays 12): rows r and r + rows/2 are identical; the first rows/2 rows are processed by the kernel the
+ * full call would run.  pair = LGD_PAIR_HALF only (y / stats of the second half are left untouched). */
+int lgd_layernorm_pair_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C, float eps,
+                           const float* gamma, const float* beta, float* stats, int rows_per_batch,
+                           int64_t x_bs, int64_t y_bs, int pair, void* stream);
 int lgd_layernorm_bwd_f16(const void* gy, int64_t ldgy, const void* x, int64_t ldx, void* gx,
                           int64_t ldgx, int rows, int C, const float* gamma, const float* stats,
                           int rows_per_batch, int64_t gy_bs, int64_t x_bs, int64_t gx_bs,
@@ -162,6 +189,13 @@ int lgd_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k, in
                      int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs, void* o, int64_t ldo,
                      int64_t o_bs, float* lse, int B, int H, int Sq, int Sk, int d, float scale,
                      void* stream);
+/* CFG pair form (additive export: LGD_ABI_VERSION stays 12): images b and b + B/2 hold identical q / k / v (see LgdGemmDesc.pair), images b < B/2 are
+ * computed with the kernel the full launch would run (bit-identical).  pair = LGD_PAIR_HALF: o / lse of images >= B/2
+ * are left untouched; LGD_PAIR_DUP: every store is repeated for image b + B/2.  B even. */
+int lgd_attn_fwd_pair_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk,
+                          int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs, void* o, int64_t ldo,
+                          int64_t o_bs, float* lse, int B, int H, int Sq, int Sk, int d, float scale,
+                          int pair, void* stream);
 /* backward: given q,k,v,o,do,lse -> dq,dk,dv (fp16, same views). delta: fp32 ws [B][H][Sq]. */
 int lgd_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk,
                      int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs, const void* o,

@@ -40,25 +40,31 @@ class LgdGemmDesc(C.Structure):
         ("tile", C.c_int32),
         ("cnt", c_void_p),
         ("rowstat", c_void_p), ("colsum", c_void_p),
+        ("pair", C.c_int32),
     ]
 
 
 EPI_GEGLU, EPI_OUT_F32, EPI_RES_F32, EPI_ROWNORM = 1, 2, 4, 8
+PAIR_HALF, PAIR_DUP = 1, 2      # CFG pair modes (LgdGemmDesc.pair, lgd_*_pair_f16)
 
 # name -> argtypes (every function returns int; the last argument of a launching call is the hipStream_t)
 _P, _I, _L, _F = c_void_p, c_int, c_i64, c_float
 SIGNATURES = {
     "lgd_abi_version": [],
     "lgd_set_option": [C.c_char_p, _I],
+    "lgd_get_option": [C.c_char_p],
     "lgd_gemm_f16": [C.POINTER(LgdGemmDesc), _P],
     "lgd_gemm_check": [C.POINTER(LgdGemmDesc)],
     "lgd_conv_in_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgd_conv_out_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lgd_groupnorm_f16": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _P, _I, _P, _P],
+    "lgd_groupnorm_pair_f16": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _P, _I, _I, _P],
     "lgd_groupnorm_bwd_f16": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P],
     "lgd_layernorm_f16": [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _I, _L, _L, _P],
+    "lgd_layernorm_pair_f16": [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _I, _L, _L, _I, _P],
     "lgd_layernorm_bwd_f16": [_P, _L, _P, _L, _P, _L, _I, _I, _P, _P, _I, _L, _L, _L, _I, _P],
     "lgd_attn_fwd_f16": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _I, _F, _P],
+    "lgd_attn_fwd_pair_f16": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "lgd_attn_bwd_f16": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P,
                          _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P],
     "lgd_attn_bwd_keys_f16": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P,

@@ -69,6 +69,10 @@ struct AttnArgs {
   int causal;        // attn_fwd_kernel only: key j attends to query i iff j <= i (CLIP text encoder)
   int B, H, Sq, Sk, d;
   float scale_log2;  // scale * log2(e)
+  // CFG pair mode (self-attention kernels only): images b < B / 2 are computed (grid.z = B / 2; the kernel CHOICE still
+  // follows the full B, so a pair launch runs the kernel its full launch would); o_dup / lse_dup != 0: every O / lse
+  // store is repeated that many elements further on, at image b + B / 2
+  int pair; long o_dup, lse_dup;
 };
 
 // Map-capture kernel (cross-attention with a saved probability map).  Attention WITHOUT map capture
@@ -614,9 +618,15 @@ __global__ __launch_bounds__(64 * NW) void attn_self_kernel(const AttnArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (half_t)(oacc[qt][dt][r] * inv);
           *reinterpret_cast<half4_t*>(orow + dv) = o;
+          if (a.o_dup) *reinterpret_cast<half4_t*>(orow + a.o_dup + dv) = o;
         }
       }
-      if (a.lse && g == 0) a.lse[((long)b * a.H + h) * a.Sq + qrow] = m_ref[qt] + log2f(l);
+      if (a.lse && g == 0) {
+        float* lp = a.lse + ((long)b * a.H + h) * a.Sq + qrow;
+        const float lv2 = m_ref[qt] + log2f(l);
+        *lp = lv2;
+        if (a.lse_dup) lp[a.lse_dup] = lv2;
+      }
     }
   }
 }
@@ -980,18 +990,25 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_self32_kernel(const AttnArg
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (half_t)(oacc[dt][g4 * 4 + r] * inv);
           *reinterpret_cast<half4_t*>(orow + dv) = o;
+          if (a.o_dup) *reinterpret_cast<half4_t*>(orow + a.o_dup + dv) = o;
         }
       }
-    if (a.lse && hh == 0) a.lse[((long)b * a.H + h) * a.Sq + qrow] = m_ref + log2f(l);
+    if (a.lse && hh == 0) {
+      float* lp = a.lse + ((long)b * a.H + h) * a.Sq + qrow;
+      const float lv2 = m_ref + log2f(l);
+      *lp = lv2;
+      if (a.lse_dup) lp[a.lse_dup] = lv2;
+    }
   }
 }
 
 template <int DP, bool SAVE_P>
 void launch_attn_dp(const AttnArgs& a, hipStream_t st) {
   if constexpr (SAVE_P) {
-    dim3 grid((a.Sq + 63) / 64, a.H, a.B);
+    dim3 grid((a.Sq + 63) / 64, a.H, a.B);   // (no pair mode: lgd_attn_fwd_pair_f16 never captures a map)
     hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, dim3(256), 0, st, a);
   } else {
+    const int gz = a.pair ? a.B / 2 : a.B;      // thresholds below keep the full B: same kernel as the full launch
     // round-3 kernel (32x32x16 MFMA, in-wave software pipelining) for the narrow heads with a spare slot, once there
     // are enough 256-query blocks to fill the chip; LGD_ATTN32=0 keeps the 16x16x32 kernel (A/B timing, tools)
     if constexpr (DP == 64 || DP == 96) {
@@ -1009,7 +1026,7 @@ void launch_attn_dp(const AttnArgs& a, hipStream_t st) {
       if (a32 && a.d % 8 == 0 && (a32 == 2 || (dk == 96 && blocks256 >= 128))) {
         const int var = attn32_var();
         auto go = [&](auto kern, int nw) {
-          dim3 g32((a.Sq + 32 * nw - 1) / (32 * nw), a.H, a.B);
+          dim3 g32((a.Sq + 32 * nw - 1) / (32 * nw), a.H, gz);
           hipLaunchKernelGGL(kern, g32, dim3(64 * nw), 0, st, a);
         };
         if (attn32_nw() == 4 || (a32 != 2 && blocks256 < 256)) {
@@ -1030,14 +1047,14 @@ void launch_attn_dp(const AttnArgs& a, hipStream_t st) {
     }
     // two query tiles per wave once there are enough 128-query blocks to fill the chip
     const bool qt2 = (long)((a.Sq + 127) / 128) * a.H * a.B >= 1024 && DP <= 96;
-    dim3 grid(qt2 ? (a.Sq + 127) / 128 : (a.Sq + 63) / 64, a.H, a.B);
+    dim3 grid(qt2 ? (a.Sq + 127) / 128 : (a.Sq + 63) / 64, a.H, gz);
     if constexpr (DP <= 96) {
       // 8-wave workgroups (256 queries share each staged K / V^T tile) pay where the head is narrow: measured
       // +15 % at d = 40 (S = 4096), +4 % at d = 80, -15 % at d = 64 (S = 9216).  LGD_ATTN_NW=4 / 8 overrides (tools).
       static const int nw_env = [] { const char* e = getenv("LGD_ATTN_NW"); return e ? atoi(e) : 0; }();
       const bool nw8 = nw_env ? nw_env == 8 : ((DP == 64 && a.d < 48) || DP == 96);
       if (qt2 && nw8 && (long)((a.Sq + 255) / 256) * a.H * a.B >= 512) {
-        dim3 g8((a.Sq + 255) / 256, a.H, a.B);
+        dim3 g8((a.Sq + 255) / 256, a.H, gz);
         if (DP == 64 && a.d < 48) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2, DP == 64 ? 3 : DP / 16, 8>), g8, dim3(512), 0, st, a);
         else if (a.d < DP) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
         else hipLaunchKernelGGL((attn_self_kernel<DP, false, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
@@ -1060,7 +1077,7 @@ void launch_attn_dp(const AttnArgs& a, hipStream_t st) {
       // arithmetic and key order: bit-identical outputs.
       static const int wide = [] { const char* e = getenv("LGD_ATTN160"); return e ? atoi(e) : 1; }();
       if (wide && a.d == DP && a.Sq >= 256 && (long)a.H * a.B * ((a.Sq + 63) / 64) > 256) {
-        dim3 g8((a.Sq + 255) / 256, a.H, a.B);
+        dim3 g8((a.Sq + 255) / 256, a.H, gz);
         hipLaunchKernelGGL((attn_self_kernel<DP, false, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
         return;
       }
@@ -1083,6 +1100,7 @@ int launch_attn(const AttnArgs& a, hipStream_t st) {
       w.q = a.q; w.ldq = a.ldq; w.q_bs = a.q_bs; w.k = a.k; w.ldk = a.ldk; w.k_bs = a.k_bs;
       w.v = a.v; w.ldv = a.ldv; w.v_bs = a.v_bs; w.o = a.o; w.ldo = a.ldo; w.o_bs = a.o_bs; w.lse = a.lse;
       w.B = a.B; w.H = a.H; w.Sq = a.Sq; w.Sk = a.Sk; w.d = a.d; w.scale_log2 = a.scale_log2;
+      w.pair = a.pair; w.o_dup = a.o_dup; w.lse_dup = a.lse_dup;
       const long wgs = (long)((a.Sq + 255) / 256) * a.H * a.B;
       if (lgd_attn_w4_supported(w) && (w4 == 2 || (wgs >= 256 && a.Sk >= 256))) return lgd_attn_w4_launch(w, st);
     }
@@ -1106,8 +1124,19 @@ void lgd_gn_set_slab(int on);                              // norm.hip
 void lgd_ln_set_stream(int on);                            // norm.hip
 void lgd_gn_set_apply_wgs(int n);                          // norm.hip
 
+// "cfg_pair": whether launch plans built for a CFG batch use the pair modes (LgdGemmDesc.pair, lgd_*_pair_f16) for the
+// ops in front of the first one that reads text or grounding tokens.  The library only keeps the value: the kernels
+// always do what a descriptor asks; the plan builder reads it (lgd_get_option) when it builds a plan.
+static std::atomic<int> g_cfg_pair{1};
+
+extern "C" int lgd_get_option(const char* name) {
+  if (name && !strcmp(name, "cfg_pair")) return g_cfg_pair.load(std::memory_order_relaxed);
+  return LGD_ERR_ARG;
+}
+
 extern "C" int lgd_set_option(const char* name, int value) {
   if (!name) return LGD_ERR_ARG;
+  if (!strcmp(name, "cfg_pair") && (value == 0 || value == 1)) { g_cfg_pair.store(value, std::memory_order_relaxed); return LGD_OK; }
   if (!strcmp(name, "gn_fused") && value >= 0 && value <= 4096) { lgd_gn_set_fused_hw(value); return LGD_OK; }
   if (!strcmp(name, "gn_slab") && (value == 0 || value == 1)) { lgd_gn_set_slab(value); return LGD_OK; }
   if (!strcmp(name, "ln_stream") && (value == 0 || value == 1)) { lgd_ln_set_stream(value); return LGD_OK; }
@@ -1133,6 +1162,32 @@ extern "C" int lgd_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const 
   a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
   a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
   a.lse = lse; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 0;
+  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  return launch_attn<false>(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// CFG pair form of lgd_attn_fwd_f16: the two halves of the batch hold identical q / k / v, so images b < B / 2 are
+// computed only.  pair = LGD_PAIR_HALF: O (and lse) of the second half are left untouched; LGD_PAIR_DUP: every store is
+// repeated at image b + B / 2.  Kernel selection follows the full B: outputs are bit-identical to the full launch.
+extern "C" int lgd_attn_fwd_pair_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
+                                     int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
+                                     void* o, int64_t ldo, int64_t o_bs, float* lse, int B, int H, int Sq,
+                                     int Sk, int d, float scale, int pair, void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (B < 2 || (B % 2) || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
+  if (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) return LGD_ERR_ARG;
+  if (bad_view(ldq, d) || bad_view(ldk, d) || bad_view(ldv, d) || (ldo % 4) || (o_bs % 4)) return LGD_ERR_ARG;
+  AttnArgs a;
+  a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
+  a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
+  a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
+  a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
+  a.lse = lse; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 0;
+  a.pair = pair;
+  a.o_dup = pair == LGD_PAIR_DUP ? (long)(B / 2) * o_bs : 0;
+  a.lse_dup = pair == LGD_PAIR_DUP ? (long)(B / 2) * H * Sq : 0;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
   return launch_attn<false>(a, reinterpret_cast<hipStream_t>(stream));
@@ -1154,6 +1209,7 @@ extern "C" int lgd_cross_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
   a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
   a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
   a.lse = nullptr; a.probs = probs; a.tok = tok; a.cond_only = cond_only; a.causal = 0;
+  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1174,6 +1230,7 @@ extern "C" int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs,
   a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
   a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
   a.lse = nullptr; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 1;
+  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
   a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
   return launch_attn<true>(a, reinterpret_cast<hipStream_t>(stream));   // exact two-pass softmax kernel

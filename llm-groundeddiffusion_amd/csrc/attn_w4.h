@@ -11,6 +11,8 @@ struct AttnW4Args {
   float* lse;               // optional: log2-domain log-sum-exp [B][H][Sq]
   int B, H, Sq, Sk, d;
   float scale_log2;         // scale * log2(e)
+  int pair;                 // CFG pair mode: grid.z = B / 2 (see AttnArgs in attn.hip)
+  long o_dup, lse_dup;      // != 0: O / lse stores repeated that many elements further on (image b + B / 2)
 };
 
 int lgd_attn_w4_supported(const AttnW4Args& a);

@@ -555,7 +555,20 @@ __global__ __launch_bounds__(256, PIPE ? 1 : 2) void attn_w4_kernel(const AttnW4
       *reinterpret_cast<half4_t*>(orow + 16 + hh * 4) = o2;
       *reinterpret_cast<half4_t*>(orow + 24 + hh * 4) = o3;
       *reinterpret_cast<half4_t*>(orow + 32 + hh * 4) = o4;
-      if (a.lse && hh == 0) a.lse[((long)b * a.H + h) * a.Sq + qrow] = m_ref[qb] + log2f(l);
+      if (a.o_dup) {                                       // CFG pair: the same row of image b + B / 2
+        half_t* drow = orow + a.o_dup;
+        *reinterpret_cast<half4_t*>(drow + 0 + hh * 4) = o0;
+        *reinterpret_cast<half4_t*>(drow + 8 + hh * 4) = o1;
+        *reinterpret_cast<half4_t*>(drow + 16 + hh * 4) = o2;
+        *reinterpret_cast<half4_t*>(drow + 24 + hh * 4) = o3;
+        *reinterpret_cast<half4_t*>(drow + 32 + hh * 4) = o4;
+      }
+      if (a.lse && hh == 0) {
+        float* lp = a.lse + ((long)b * a.H + h) * a.Sq + qrow;
+        const float lv = m_ref[qb] + log2f(l);
+        *lp = lv;
+        if (a.lse_dup) lp[a.lse_dup] = lv;
+      }
     }
   };
   store_o(std::integral_constant<int, 0>{});
@@ -589,7 +602,7 @@ int lgd_attn_w4_supported(const AttnW4Args& a) {
 }
 
 int lgd_attn_w4_launch(const AttnW4Args& a, hipStream_t st) {
-  dim3 grid((a.Sq + 255) / 256, a.H, a.B);
+  dim3 grid((a.Sq + 255) / 256, a.H, a.pair ? a.B / 2 : a.B);
 #ifdef LGD_W4_ABLATION
   static const int abl = [] { const char* e = getenv("LGD_W4_ABL"); return e ? atoi(e) : 0; }();
   switch (abl) {

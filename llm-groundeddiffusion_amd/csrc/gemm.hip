@@ -39,6 +39,8 @@ struct GemmArgs {
   int cin;       // c0 + c1
   int k_per_split;  // multiple of BK
   int group_m;      // gemm_pipe_kernel: output tiles are walked in groups of group_m row panels (1 = rows of tiles)
+  long c_dup;       // CFG pair, dup mode (LgdGemmDesc.pair): every output store is repeated c_dup elements further on (row
+                    // m + M / 2 of the caller's matrix); 0 = single store.  In pair mode d.M is HALF the caller's M.
 #ifdef LGD_GEMM_ABLATION
   int stagger;      // tools: workgroups of the second residency slot start late by stagger x 64 x 127 cycles
 #endif
@@ -107,17 +109,19 @@ template <bool GEGLU>
 __device__ __forceinline__ void epilogue_store4(const LgdGemmDesc& d, long c_off, long r_off, int m,
                                                 int n_out, f32x4 v, f32x4 g, float4 bv, float4 bg,
                                                 bool res_ready = false,
-                                                half4_t res_pre = (half4_t){0, 0, 0, 0}) {
+                                                half4_t res_pre = (half4_t){0, 0, 0, 0}, long c_dup = 0) {
   v = epilogue_value4<GEGLU>(d, r_off, m, n_out, v, g, bv, bg, res_ready, res_pre);
   if (d.epi & LGD_EPI_OUT_F32) {
     float* cp = reinterpret_cast<float*>(d.c) + c_off + (long)m * d.ldc + n_out;
     *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
+    if (c_dup) *reinterpret_cast<float4*>(cp + c_dup) = make_float4(v[0], v[1], v[2], v[3]);
   } else {
     half_t* cp = reinterpret_cast<half_t*>(d.c) + c_off + (long)m * d.ldc + n_out;
     half4_t o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] = (half_t)v[r];
     *reinterpret_cast<half4_t*>(cp) = o;
+    if (c_dup) *reinterpret_cast<half4_t*>(cp + c_dup) = o;
   }
 }
 
@@ -211,7 +215,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& ga, f32x4 (&acc)[N
           const int m = m0 + wm * 16 * MI + mi * 16 + m_l;
           if (m < d.M)
             epilogue_store4<true>(d, c_off, r_off, m, n_out, rownorm4(d, m, n_in, acc[ni][mi]),
-                                  rownorm4(d, m, n_in + 16, acc[ni + 1][mi]), bv, bg);
+                                  rownorm4(d, m, n_in + 16, acc[ni + 1][mi]), bv, bg, false, (half4_t){0, 0, 0, 0}, ga.c_dup);
         }
       }
     }
@@ -251,7 +255,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& ga, f32x4 (&acc)[N
         const int m = m0 + wm * 16 * MI + mi * 16 + m_l;
         if (m < d.M)
           epilogue_store4<false>(d, c_off, r_off, m, n, rownorm4(d, m, n, acc[ni][mi]), acc[ni][mi], bv, bv, res16,
-                                 res16 ? rpre[nj][mi] : (half4_t){0, 0, 0, 0});
+                                 res16 ? rpre[nj][mi] : (half4_t){0, 0, 0, 0}, ga.c_dup);
       }
     }
   }
@@ -390,6 +394,7 @@ __device__ __forceinline__ void gemm_epilogue_lds_generic(const GemmArgs& ga, f3
       if (idx < RROWS * CPR && m < d.M && n < n_total_out) {
         const uint4 val = *reinterpret_cast<const uint4*>(lds + row * CROW + ch * 16);
         *reinterpret_cast<uint4*>(cbase + (long)m * d.ldc + n) = val;
+        if (ga.c_dup) *reinterpret_cast<uint4*>(cbase + ga.c_dup + (long)m * d.ldc + n) = val;
       }
     }
     // Between rounds the staging rows are rewritten; behind the LAST round of a persistent workgroup (RES_PREFETCH ==
@@ -569,6 +574,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs& ga, f32x4 (&ac
       if (idx < RROWS * CPR && m < d.M && n < n_total_out) {
         const uint4 val = *reinterpret_cast<const uint4*>(lds + row * CROW + ch * 16);
         *reinterpret_cast<uint4*>(cbase + (long)m * d.ldc + n) = val;
+        if (ga.c_dup) *reinterpret_cast<uint4*>(cbase + ga.c_dup + (long)m * d.ldc + n) = val;
       }
     }
     // Between rounds the staging rows are rewritten; behind the LAST round of a persistent workgroup (RES_PREFETCH ==
@@ -1991,6 +1997,19 @@ const GemmTile* gemm_check(const LgdGemmDesc& desc, GemmArgs& ga) {
       return nullptr;
   }
   if (d.splits > 1 && d.cnt && !(f & TILE_CNT)) return nullptr;
+  // CFG pair (LgdGemmDesc.pair): the two halves of the rows are identical, rows m < M / 2 are computed.  Everything above —
+  // the tile == 0 heuristic included — saw the caller's M, so a pair launch runs the tile its full launch would; from
+  // here on the kernels see HALF the rows (tile walk, grid and row masks follow d.M) and the dup offset.
+  ga.c_dup = 0;
+  if (d.pair) {
+    if ((d.pair != LGD_PAIR_HALF && d.pair != LGD_PAIR_DUP) || d.splits != 1 || d.nb_o * d.nb_i != 1 || (d.M & 1))
+      return nullptr;
+    d.M /= 2;
+    if (d.pair == LGD_PAIR_DUP) {
+      ga.c_dup = (long)d.M * d.ldc;
+      if ((f & TILE_LDS_EPI) && (ga.c_dup & 7)) return nullptr;     // 16-byte pieces at the second address too
+    }
+  }
   return t;
 }
 

@@ -135,7 +135,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
                                                         const float* __restrict__ beta, int silu,
                                                         half_t* __restrict__ y,
                                                         const float* __restrict__ part, int nchunk,
-                                                        float* stats, int napply) {
+                                                        float* stats, int napply, long y_dup) {
+  // y_dup != 0 (CFG pair, dup mode): every store is repeated y_dup elements further on (image b + B / 2)
   __shared__ float s_mean[64], s_rstd[64];
   const int C = c0 + c1;
   const int cpg = C / G;
@@ -216,7 +217,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
             if (silu) f = silu_f(f);
             o[e] = (half_t)f;
           }
-          *reinterpret_cast<half8_t*>(y + ((long)b * HW + pp) * C + c) = o;
+          half_t* yp = y + ((long)b * HW + pp) * C + c;
+          *reinterpret_cast<half8_t*>(yp) = o;
+          if (y_dup) *reinterpret_cast<half8_t*>(yp + y_dup) = o;
         }
       }
     }
@@ -235,7 +238,8 @@ template <int MAXP>
 __global__ __launch_bounds__(256) void gn_fused_kernel(const half_t* __restrict__ x0, const half_t* __restrict__ x1,
                                                         int c0, int c1, int HW, int G, float eps,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        int silu, half_t* __restrict__ y, float* stats, int kg) {
+                                                        int silu, half_t* __restrict__ y, float* stats, int kg,
+                                                        long y_dup) {
   __shared__ float s_part[256 * 8];
   __shared__ float s_ch[256];
   __shared__ float s_g[8][2];
@@ -319,7 +323,9 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const half_t* __restrict_
         if (silu) f = silu_f(f);
         o[e] = (half_t)f;
       }
-      *reinterpret_cast<half8_t*>(y + ((long)b * HW + pp) * C + c) = o;
+      half_t* yp = y + ((long)b * HW + pp) * C + c;
+      *reinterpret_cast<half8_t*>(yp) = o;
+      if (y_dup) *reinterpret_cast<half8_t*>(yp + y_dup) = o;
     }
   }
 }
@@ -1009,13 +1015,19 @@ void lgd_ln_set_stream(int on) { g_ln_stream = on; }        // lgd_set_option("l
 void lgd_gn_set_slab(int on) { g_gn_slab = on; }
 void lgd_gn_set_apply_wgs(int n) { g_gn_apply_wgs = n; }            // lgd_set_option("gn_slab", 0 | 1) (attn.hip)    // lgd_set_option("gn_fused", hw) (attn.hip)
 
-extern "C" int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW,
-                                 int G, float eps, const float* gamma, const float* beta, int silu,
-                                 void* y, float* part, int nchunk, float* stats, void* stream) {
+// pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every choice below —
+// one launch or two, workgroups per image — follows the full B, so each image sees the launch geometry (and the
+// summation order) of the full call.  LGD_PAIR_DUP: the apply pass stores each piece for image b + B / 2 as well.
+static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G, float eps,
+                            const float* gamma, const float* beta, int silu, void* y, float* part, int nchunk,
+                            float* stats, int pair, void* stream) {
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const int C = c0 + c1;
   if (G > 64 || C > GN_MAXC || (C % G) || (c0 % 8) || (c1 % 8) || nchunk < 1) return LGD_ERR_ARG;
   if (c1 > 0 && !x1) return LGD_ERR_ARG;
+  if (pair && ((pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) || B < 2 || (B % 2) || stats)) return LGD_ERR_ARG;
+  const int Bg = pair ? B / 2 : B;                                     // images launched
+  const long y_dup = pair == LGD_PAIR_DUP ? (long)Bg * HW * C : 0L;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   {
     // one launch when a workgroup can hold its (image, kg groups) slab in registers
@@ -1027,8 +1039,8 @@ extern "C" int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1,
       const int pl = 256 / nv, npx = (HW + pl - 1) / pl;
       if (npx <= 32) {
 #define GN_FUSED(P)                                                                                                 \
-  hipLaunchKernelGGL(gn_fused_kernel<P>, dim3(G / kg, B), dim3(256), 0, st, (const half_t*)x0, (const half_t*)x1,    \
-                     c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, stats, kg)
+  hipLaunchKernelGGL(gn_fused_kernel<P>, dim3(G / kg, Bg), dim3(256), 0, st, (const half_t*)x0, (const half_t*)x1,   \
+                     c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, stats, kg, y_dup)
         if (npx <= 4) GN_FUSED(4);
         else if (npx <= 8) GN_FUSED(8);
         else if (npx <= 16) GN_FUSED(16);
@@ -1038,13 +1050,26 @@ extern "C" int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1,
       }
     }
   }
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(256), 0, st, (const half_t*)x0,
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, Bg), dim3(256), 0, st, (const half_t*)x0,
                      (const half_t*)x1, c0, c1, HW, G, part, nchunk);
   const int napply = gn_apply_blocks(B, HW, C);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(napply, B), dim3(256), 0, st, (const half_t*)x0,
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(napply, Bg), dim3(256), 0, st, (const half_t*)x0,
                      (const half_t*)x1, c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, part,
-                     nchunk, stats, napply);
+                     nchunk, stats, napply, y_dup);
   return lgd_check_launch();
+}
+
+extern "C" int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW,
+                                 int G, float eps, const float* gamma, const float* beta, int silu,
+                                 void* y, float* part, int nchunk, float* stats, void* stream) {
+  return groupnorm_launch(x0, x1, c0, c1, B, HW, G, eps, gamma, beta, silu, y, part, nchunk, stats, 0, stream);
+}
+
+extern "C" int lgd_groupnorm_pair_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW,
+                                      int G, float eps, const float* gamma, const float* beta, int silu,
+                                      void* y, float* part, int nchunk, int pair, void* stream) {
+  if (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) return LGD_ERR_ARG;
+  return groupnorm_launch(x0, x1, c0, c1, B, HW, G, eps, gamma, beta, silu, y, part, nchunk, nullptr, pair, stream);
 }
 
 extern "C" int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void* x1, int c0, int c1,
@@ -1082,13 +1107,15 @@ extern "C" int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void*
   return lgd_check_launch();
 }
 
-extern "C" int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C,
-                                 float eps, const float* gamma, const float* beta, float* stats,
-                                 int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
+// half (CFG pair mode, lgd_layernorm_pair_f16): the kernel is CHOSEN for `rows_all` rows — what the full call would
+// run — and launched over the first `rows` = rows_all / 2 of them.
+static int layernorm_launch(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int rows_all, int C,
+                            float eps, const float* gamma, const float* beta, float* stats,
+                            int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if ((C % 8) || C > 64 * 8 * LN_MAXV || rows < 1) return LGD_ERR_ARG;
   if (!y && (!stats || C > (g_ln_stream ? 64 * 5 * 8 : 192 * 8))) return LGD_ERR_ARG;      // statistics-only form: stats required
-  if (rows_per_batch < 1) rows_per_batch = rows;
+  if (rows_per_batch < 1) rows_per_batch = rows_all;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const half_t* xp = (const half_t*)x;
   half_t* yp = (half_t*)y;
@@ -1096,7 +1123,7 @@ extern "C" int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ld
   // statistics only: the streaming kernel (lane groups per row) once the map is large enough to keep every CU streaming
   // (measured, 40 launches in one graph: 65536 x 320 16.4 -> 10.0 us, 32768 x 320 8.7 -> 4.9, 16384 x 640 7.1 -> 5.0;
   // below ~8 M elements the one-wave-per-row kernels with their 4x more workgroups win: 4096 x 1280 3.7 vs 4.8 us)
-  if (!y && g_ln_stream && ((long)rows * C >= (8L << 20) || nvec > 192)) {
+  if (!y && g_ln_stream && ((long)rows_all * C >= (8L << 20) || nvec > 192)) {
 #define LGD_LN_STATS(L, R)                                                                                         \
   hipLaunchKernelGGL((ln_stats_kernel<L, R>), dim3((rows + 4 * (64 / L) * R - 1) / (4 * (64 / L) * R)), dim3(256), 0, st, xp, \
                      (long)ldx, rows, C, eps, stats, rows_per_batch, (long)x_bs)
@@ -1120,6 +1147,22 @@ extern "C" int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ld
                        (long)y_bs);
 #undef LGD_LN_LAUNCH
   return lgd_check_launch();
+}
+
+extern "C" int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C,
+                                 float eps, const float* gamma, const float* beta, float* stats,
+                                 int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
+  return layernorm_launch(x, ldx, y, ldy, rows, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
+}
+
+extern "C" int lgd_layernorm_pair_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C,
+                                      float eps, const float* gamma, const float* beta, float* stats,
+                                      int rows_per_batch, int64_t x_bs, int64_t y_bs, int pair, void* stream) {
+  // rows of the second half are copies of the first: only HALF exists here (the consumers of a LayerNorm inside the
+  // shared prefix are pair-mode GEMMs, which read row m only)
+  if (pair != LGD_PAIR_HALF || rows < 2 || (rows % 2)) return LGD_ERR_ARG;
+  if (rows_per_batch >= 1 && ((rows / 2) % rows_per_batch)) return LGD_ERR_ARG;   // the half is a whole number of images
+  return layernorm_launch(x, ldx, y, ldy, rows / 2, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
 }
 
 extern "C" int lgd_layernorm_bwd_f16(const void* gy, int64_t ldgy, const void* x, int64_t ldx,

@@ -11,7 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import EPI_GEGLU, EPI_OUT_F32, EPI_RES_F32, EPI_ROWNORM, LgdGemmDesc
+from ._lib import EPI_GEGLU, EPI_OUT_F32, EPI_RES_F32, EPI_ROWNORM, PAIR_DUP, PAIR_HALF, LgdGemmDesc
 
 F16, F32 = torch.float16, torch.float32
 
@@ -33,6 +33,14 @@ def _call(name, *args):
 def set_option(name: str, value: int):
     """Kernel-variant switch of the library (lgd_set_option): e.g. set_option("attn32", 0 | 1 | 2)."""
     _call("lgd_set_option", name.encode(), int(value))
+
+
+def get_option(name: str) -> int:
+    """Value of an option the host side reads back (lgd_get_option): "cfg_pair"."""
+    v = _lib.load().lgd_get_option(name.encode())
+    if v < 0:
+        raise RuntimeError(f"lgd_get_option({name}) failed")
+    return v
 
 
 # ---------------------------------------------------------------------------------------------
@@ -150,6 +158,17 @@ def gemm_desc(a0, w, c, M, N, K, *, a1=None, lda0=None, lda1=0, c0=None, c1=0, t
 def gemm_accepts(d) -> bool:
     """Whether lgd_gemm_f16 would launch descriptor `d` (lgd_gemm_check: host only, needs no GPU)."""
     return _lib.load().lgd_gemm_check(C.byref(d)) == 0
+
+
+def gemm_set_pair(d, mode) -> bool:
+    """CFG pair mode of a built descriptor (LgdGemmDesc.pair: rows m and m + M/2 are identical, rows < M/2 are computed;
+    PAIR_HALF leaves the second half of C alone, PAIR_DUP stores every piece twice).  Tile, splits and shape key stay
+    those of the full launch.  False — and the descriptor unchanged — where the library refuses (split-K, batched, odd M)."""
+    prev, d.pair = d.pair, mode
+    if mode and not gemm_accepts(d):
+        d.pair = prev
+        return False
+    return True
 
 
 # profiler kernel names of the tile codes (tools/ and profiles/ key on them); which descriptors a code serves is the
@@ -340,7 +359,10 @@ def gemm_launch(desc, tag=None, flops=None):
         nb = desc.nb_o * desc.nb_i
         if flops is None:
             flops = 2.0 * desc.M * desc.N * desc.K * nb
-        nbytes = 2.0 * nb * (desc.M * desc.K / max(desc.taps, 1) + desc.N * desc.K + desc.M * desc.N)
+        if desc.pair:                                    # half the rows are computed (the shape key keeps the full M)
+            flops *= 0.5
+        m_in, m_out = (desc.M // 2 if desc.pair else desc.M), (desc.M // 2 if desc.pair == PAIR_HALF else desc.M)
+        nbytes = 2.0 * nb * (m_in * desc.K / max(desc.taps, 1) + desc.N * desc.K + m_out * desc.N)
         return PROFILER.wrap(TILE_NAMES.get(desc.tile, "gemm"), flops, nbytes,
                              lambda: _call("lgd_gemm_f16", C.byref(desc), _stream()), tag,
                              shape=f"{shape_key(desc)} splits={desc.splits}")
@@ -469,7 +491,8 @@ def gn_chunks(B, HW):
     return max(1, min(HW // 8, GN_STATS_WGS // max(B, 1), 64))
 
 
-def groupnorm(x, B, HW, G, eps, gamma, beta, silu, *, x1=None, out=None, part=None, stats=None):
+def groupnorm(x, B, HW, G, eps, gamma, beta, silu, *, x1=None, out=None, part=None, stats=None, pair=0):
+    """pair (PAIR_HALF / PAIR_DUP): images b and b + B/2 are identical, images < B/2 are normalised (lgd_groupnorm_pair_f16)."""
     c0 = x.shape[1]
     c1 = x1.shape[1] if x1 is not None else 0
     C_ = c0 + c1
@@ -478,6 +501,12 @@ def groupnorm(x, B, HW, G, eps, gamma, beta, silu, *, x1=None, out=None, part=No
         out = torch.empty((B * HW, C_), device=x.device, dtype=F16)
     if part is None:
         part = torch.empty((B, nchunk, G, 2), device=x.device, dtype=F32)
+    if pair:
+        assert stats is None, "pair mode is a no-grad forward: no statistics output"
+        _prof("groupnorm (gn_stats + gn_apply | gn_fused)", (2.0 + (2.0 if pair == PAIR_DUP else 1.0)) * B * HW * C_,
+              lambda: _call("lgd_groupnorm_pair_f16", _p(x), _p(x1), c0, c1, B, HW, G, float(eps), _p(gamma), _p(beta),
+                            1 if silu else 0, _p(out), _p(part), nchunk, int(pair), _stream()), shape=f"B{B}_HW{HW}_C{C_}")
+        return out
     # algorithmic bytes: the map read once for the statistics, once for the apply, written once
     _prof("groupnorm (gn_stats + gn_apply | gn_fused)", 6.0 * B * HW * C_,
           lambda: _call("lgd_groupnorm_f16", _p(x), _p(x1), c0, c1, B, HW, G, float(eps), _p(gamma), _p(beta),
@@ -504,25 +533,36 @@ def groupnorm_bwd(gy, x, B, HW, G, gamma, beta, silu, stats, *, x1=None, gx0=Non
 
 
 def layernorm(x, gamma, beta, eps=1e-5, *, out=None, ldy=None, stats=None, rows_per_batch=0,
-              x_bs=0, y_bs=0, rows=None, ldx=None):
+              x_bs=0, y_bs=0, rows=None, ldx=None, pair=0):
+    """pair = PAIR_HALF: rows r and r + rows/2 are identical, the first rows/2 are normalised (lgd_layernorm_pair_f16)."""
     C_ = gamma.shape[0]
     if rows is None:
         rows = x.numel() // C_
     if out is None:
         out = torch.empty((rows, C_), device=x.device, dtype=F16)
+    if pair:
+        _prof("layernorm_rows_kernel", 2.0 * rows * C_,
+              lambda: _call("lgd_layernorm_pair_f16", _p(x), ldx or C_, _p(out), ldy or C_, rows, C_, float(eps), _p(gamma),
+                            _p(beta), _p(stats), rows_per_batch, x_bs, y_bs, int(pair), _stream()), shape=f"R{rows}_C{C_}")
+        return out
     _prof("layernorm_rows_kernel", 4.0 * rows * C_,
           lambda: _call("lgd_layernorm_f16", _p(x), ldx or C_, _p(out), ldy or C_, rows, C_, float(eps), _p(gamma),
                         _p(beta), _p(stats), rows_per_batch, x_bs, y_bs, _stream()), shape=f"R{rows}_C{C_}")
     return out
 
 
-def layernorm_stats(x, C_, eps=1e-5, *, stats=None, rows=None, ldx=None):
+def layernorm_stats(x, C_, eps=1e-5, *, stats=None, rows=None, ldx=None, pair=0):
     """(mean, rstd) of every row, fp32 [rows][2]: the statistics half of LayerNorm, whose other half rides in the
-    consuming GEMM's epilogue (EPI_ROWNORM)."""
+    consuming GEMM's epilogue (EPI_ROWNORM).  pair = PAIR_HALF: the first rows/2 rows only (the halves are identical)."""
     if rows is None:
         rows = x.numel() // C_
     if stats is None:
         stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32)
+    if pair:
+        _prof("ln_stats_kernel (LayerNorm statistics only)", 1.0 * rows * C_,
+              lambda: _call("lgd_layernorm_pair_f16", _p(x), ldx or C_, _p(None), C_, rows, C_, float(eps), _p(None),
+                            _p(None), _p(stats), 0, 0, 0, int(pair), _stream()), shape=f"R{rows}_C{C_}")
+        return stats
     _prof("ln_stats_kernel (LayerNorm statistics only)", 2.0 * rows * C_,
           lambda: _call("lgd_layernorm_f16", _p(x), ldx or C_, _p(None), C_, rows, C_, float(eps), _p(None), _p(None),
                         _p(stats), 0, 0, 0, _stream()), shape=f"R{rows}_C{C_}")
@@ -547,15 +587,22 @@ def layernorm_bwd(gy, x, gamma, stats, *, gx=None, rows=None, ldgy=None, ldx=Non
 # attention.  Views are (tensor, ld, batch_stride) with head h at column offset h*d.
 # ---------------------------------------------------------------------------------------------
 def attn_fwd(q, k, v, o, B, H, Sq, Sk, d, scale, *, lse=None, q_view=None, k_view=None,
-             v_view=None, o_view=None):
+             v_view=None, o_view=None, pair=0):
+    """pair (PAIR_HALF / PAIR_DUP): images b and b + B/2 hold identical q / k / v, images < B/2 are computed
+    (lgd_attn_fwd_pair_f16: the kernel the full launch would run, over half the grid)."""
     qv = q_view or (H * d, Sq * H * d)
     kv = k_view or (H * d, Sk * H * d)
     vv = v_view or (H * d, Sk * H * d)
     ov = o_view or (H * d, Sq * H * d)
-    fn = lambda: _call("lgd_attn_fwd_f16", _p(q), qv[0], qv[1], _p(k), kv[0], kv[1], _p(v), vv[0], vv[1],
-                       _p(o), ov[0], ov[1], _p(lse), B, H, Sq, Sk, d, float(scale), _stream())
+    if pair:
+        fn = lambda: _call("lgd_attn_fwd_pair_f16", _p(q), qv[0], qv[1], _p(k), kv[0], kv[1], _p(v), vv[0], vv[1],
+                           _p(o), ov[0], ov[1], _p(lse), B, H, Sq, Sk, d, float(scale), int(pair), _stream())
+    else:
+        fn = lambda: _call("lgd_attn_fwd_f16", _p(q), qv[0], qv[1], _p(k), kv[0], kv[1], _p(v), vv[0], vv[1],
+                           _p(o), ov[0], ov[1], _p(lse), B, H, Sq, Sk, d, float(scale), _stream())
     if PROFILER is not None:
-        PROFILER.wrap(f"attn_self_kernel d={d}", 4.0 * B * H * Sq * Sk * d, 2.0 * B * H * d * (2 * Sq + 2 * Sk), fn,
+        Bc = B // 2 if pair else B                        # images computed (the shape keeps the full B)
+        PROFILER.wrap(f"attn_self_kernel d={d}", 4.0 * Bc * H * Sq * Sk * d, 2.0 * Bc * H * d * (2 * Sq + 2 * Sk), fn,
                       "attn_path", shape=f"B{B}_H{H}_Sq{Sq}_Sk{Sk}")
     else:
         fn()

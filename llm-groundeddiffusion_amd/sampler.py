@@ -225,7 +225,8 @@ class LMDSampler:
         """The launch sequence of one denoising step for nb images: CFG pair in, UNet, fused CFG + scheduler step."""
         def main_fn():
             ops.copy_(plan.latents_in[:nb], st.lat)                          # torch.cat([latents]*2)
-            ops.copy_(plan.latents_in[nb:], st.lat)
+            if not plan.latents_pair:                                        # a CFG pair plan reads the first half only
+                ops.copy_(plan.latents_in[nb:], st.lat)
             plan.forward()
             step.launch(plan.eps_out, st.lat, self.eng.dyn, frozen_ref=st.frozen_ref, mask=st.mask, hist=st.hist)
         return main_fn
@@ -328,7 +329,7 @@ class LMDSampler:
         out = []
         for f in ([True, False] if gligen else [False]):
             for nb in main_batches:
-                plan = eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys)
+                plan = eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys, pair_shared=True)
                 st = self._state(nb, eng.cfg.in_channels, L, T)
                 out.append(("main", f, nb, self._main_pass(plan, st, st.step_kernel(self.scheduler.step_kind), nb)))
             for nb in guide_batches:
@@ -532,13 +533,15 @@ class LMDSampler:
         """Plans + launch sequences (built / captured once per shape, cached on the state) per GLIGEN-fuser setting ->
         (main plans, main runners, guidance (plan, forward runner, backward runner))."""
         eng, nb = self.eng, len(jobs)
-        plans = {f: eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys) for f in fusers_main}
+        # the CFG batch is [uncond halves; cond halves] of ONE set of latents (_main_pass): pair_shared
+        plans = {f: eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys, pair_shared=True) for f in fusers_main}
         guides = {f: self._guide_runners(st, nb, L, f, gkeys) for f in fusers_guide}
         if use_gligen:                                                        # after the plans exist
             boxes, embeddings, masks = (torch.cat([j.gligen[k][0:1] for j in jobs] + [j.gligen[k][1:2] for j in jobs])
                                         for k in range(3))            # [uncond halves; cond halves], like the text
             eng.prepare_gligen(boxes=boxes, positive_embeddings=embeddings, masks=masks)
-        mains = {f: st.runner(("main", f, tuple(plan_keys), step.kind), self._main_pass(plan, st, step, nb), self.use_graphs)
+        mains = {f: st.runner(("main", f, tuple(plan_keys), step.kind, plan.pair_shared), self._main_pass(plan, st, step, nb),
+                              self.use_graphs)
                  for f, plan in plans.items()}
         return plans, mains, guides
 

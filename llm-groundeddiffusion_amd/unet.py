@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from ._lib import EPI_GEGLU
+from ._lib import EPI_GEGLU, PAIR_DUP, PAIR_HALF
 from .weights import UNetConfig, unet_blocks
 from .weightstore import WeightStore
 
@@ -37,12 +37,32 @@ N_OBJ_TOKENS = 30  # max_objs of pipelines.py:289
 
 class Act:
     """An activation buffer [rows, C] (fp16) and, in grad plans, its gradient buffer."""
-    __slots__ = ("t", "g", "rows", "C")
+    __slots__ = ("t", "g", "rows", "C", "pair")
 
     def __init__(self, t):
         self.t = t
         self.g = None
         self.rows, self.C = t.shape
+        self.pair = None            # PairMode of the producing op while only the first half of the rows is written
+
+
+class PairMode:
+    """CFG pair mode of one op of the shared prefix (Plan.pair_shared): PAIR_HALF = the op writes the first half of its
+    output only, PAIR_DUP = it stores every piece for the second half as well.  Mutable while the plan is being built:
+    an op that cannot run in pair mode (the library refuses its descriptor) turns the producers of its inputs to DUP."""
+    __slots__ = ("mode", "desc", "on_dup")
+
+    def __init__(self, mode, desc=None):
+        self.mode, self.desc, self.on_dup = mode, desc, None
+        if desc is not None:
+            desc.pair = mode
+
+    def dup(self):
+        self.mode = PAIR_DUP
+        if self.desc is not None:
+            self.desc.pair = PAIR_DUP
+        if self.on_dup is not None:          # an op without a DUP form runs in full instead: its own inputs in full too
+            self.on_dup()
 
 
 class Op:
@@ -64,8 +84,16 @@ choose_splits = ops.choose_splits
 class Plan:
     def __init__(self, eng: "UNetEngine", B: int, L: int, *, grad: bool, fuser: bool,
                  stop_key: Optional[Tuple] = None, save_keys: Sequence[Tuple] = (),
-                 text_batch_offset: int = 0, obj_batch_offset: int = 0):
+                 text_batch_offset: int = 0, obj_batch_offset: int = 0, pair_shared: bool = False):
         self.eng, self.B, self.L = eng, B, L
+        # The caller guarantees a CFG batch [uncond halves; cond halves] over ONE set of latents: rows b and b + B/2 of
+        # every activation in front of the first op that reads text or grounding tokens are identical, and the time
+        # embedding is one row per call.  Those ops then run in pair mode: computed for the first half, stored twice
+        # where a later op reads all rows (UNetEngine.plan decides; never for grad plans or per-row time embeddings).
+        self.pair_shared = bool(pair_shared)
+        self._pair = False                # building inside the shared prefix
+        self.pair_ops = 0                 # ops that run in pair mode
+        self.latents_pair = False         # conv_in reads latents_in[:B/2] only
         self.obj_off = obj_batch_offset
         self.grad, self.fuser = grad, fuser
         self.stop_key = tuple(stop_key) if stop_key else None
@@ -109,10 +137,31 @@ class Plan:
     def _ws(self, n_floats):
         return self.eng.workspace(n_floats)
 
+    # ---- CFG pair modes of the shared prefix ---------------------------------------------------
+    def _need_full(self, *acts):
+        """The op being built reads ALL rows of these inputs: a producer still in HALF mode stores both halves."""
+        for a in acts:
+            if a is not None and a.pair is not None:
+                a.pair.dup()
+                a.pair = None
+
+    def _pair_op(self, inputs, out: Optional[Act], half: bool, desc=None) -> Optional[PairMode]:
+        """Pair mode of the op being built, or None (it runs in full: outside the prefix, or the library refuses the
+        descriptor in pair mode — split-K on tiny networks).  half: only ops of the prefix read its output."""
+        if not self._pair or (desc is not None and not ops.gemm_set_pair(desc, PAIR_DUP)):
+            self._need_full(*inputs)
+            return None
+        pm = PairMode(PAIR_HALF if half else PAIR_DUP, desc)
+        if half and out is not None:
+            out.pair = pm
+        self.pair_ops += 1
+        return pm
+
     # ---- GEMM-shaped ops ------------------------------------------------------------------
     def linear(self, x: Act, name: str, *, res: Optional[Act] = None, alpha=1.0, geglu=False,
-               bias=True, out: Optional[Act] = None, rows=None, bwd=True) -> Act:
-        """y = alpha*(x @ W^T + b) + res ;  backward: gx (+)= alpha * gy @ W ; gres (+)= gy."""
+               bias=True, out: Optional[Act] = None, rows=None, bwd=True, half=False) -> Act:
+        """y = alpha*(x @ W^T + b) + res ;  backward: gx (+)= alpha * gy @ W ; gres (+)= gy.
+        half: inside the shared prefix only prefix ops read y (PairMode)."""
         W = self.eng.w.h[f"{name}.w"]
         b = self.eng.w.f[f"{name}.b"] if bias else None
         N, K = W.shape
@@ -122,6 +171,7 @@ class Plan:
         d = ops.gemm_desc(x.t, W, y.t, M, N, K, lda0=x.C, bias=b, res=res.t if res else None,
                           ldr=res.C if res else 0, alpha=alpha, epi=EPI_GEGLU if geglu else 0,
                           ldc=y.C)
+        self._pair_op([x, res], y, half, d)
         # q/k/v/out projections count towards the "attention path" of the benchmark's roofline report
         tag = "attn_path" if any(t in name for t in (".attn1.", ".attn2.", ".fuser.attn.")) else None
         fwd = lambda: ops.gemm_launch(d, tag)
@@ -151,7 +201,7 @@ class Plan:
         return y
 
     def conv(self, x: Act, name: str, H: int, *, x1: Optional[Act] = None, res: Optional[Act] = None,
-             temb_off: Optional[int] = None, stride=1, ups=False) -> Act:
+             temb_off: Optional[int] = None, stride=1, ups=False, half=False) -> Act:
         """3x3 conv (pad 1) on a channels-last map of side H (stored), optional second source."""
         B = self.B
         W = self.eng.w.h[f"{name}.w"]
@@ -166,7 +216,7 @@ class Plan:
         if temb_off is not None and eng.temb_rows > 1:
             # text_time conditioning (SDXL): the time embedding differs per image (pooled text + size / score ids), the
             # GEMM epilogue takes ONE bias2 vector per launch -> one launch per image (1024^2 refiner: 16384 rows each)
-            assert stride == 1 and not ups and res is None
+            assert stride == 1 and not ups and res is None and not self._pair
             ds = []
             for i in range(B):
                 row = eng.temb_cur[self.text_off + i]
@@ -181,6 +231,7 @@ class Plan:
                               lda1=c1, taps=9, hin=H, win=H, hout=Ho, wout=Ho, stride=stride,
                               ups=1 if ups else 0, bias=b, bias2=bias2, res=res.t if res else None,
                               ldr=res.C if res else 0, ldc=Cout)
+            self._pair_op([x, x1, res], y, half, d)
             fwd = lambda: ops.gemm_launch(d)
         if not self.grad:
             self._add(fwd)
@@ -228,6 +279,7 @@ class Plan:
         Cout, K = W.shape
         c0, c1 = x.C, (x1.C if x1 else 0)
         M = x.rows
+        self._need_full(x, x1)
         y = self._act(M, Cout)
         d = ops.gemm_desc(x.t, W, y.t, M, Cout, K, a1=x1.t if x1 else None, c0=c0, c1=c1, lda0=c0,
                           lda1=c1, bias=b, ldc=Cout)
@@ -249,7 +301,7 @@ class Plan:
         return y
 
     # ---- norms -----------------------------------------------------------------------------
-    def groupnorm(self, x: Act, x1: Optional[Act], name: str, HW: int, eps: float, silu: bool) -> Act:
+    def groupnorm(self, x: Act, x1: Optional[Act], name: str, HW: int, eps: float, silu: bool, half=False) -> Act:
         eng, B = self.eng, self.B
         G = eng.cfg.norm_num_groups
         gm, bt = eng.w.f[f"{name}.g"], eng.w.f[f"{name}.b"]
@@ -259,7 +311,11 @@ class Plan:
         part = self._alloc((B, nch, G, 2))
         stats = self._alloc((B, G, 2)) if self.grad else None
         xt1 = x1.t if x1 else None
-        fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, stats=stats)
+        pm = self._pair_op([x, x1], y, half)
+        if pm is not None:
+            fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, pair=pm.mode)
+        else:
+            fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, stats=stats)
         if not self.grad:
             self._add(fwd)
             return y
@@ -274,7 +330,7 @@ class Plan:
         self._add(fwd, make_bwd, gouts)
         return y
 
-    def layernorm(self, x: Act, name: str, *, out_t=None, ldy=None, S=None, y_bs=0) -> Act:
+    def layernorm(self, x: Act, name: str, *, out_t=None, ldy=None, S=None, y_bs=0, half=False) -> Act:
         """LayerNorm rows of x.  With out_t/ldy/S/y_bs the rows of each image are written at the
         head of a larger [S+30] buffer (GLIGEN fuser concat)."""
         eng = self.eng
@@ -284,8 +340,14 @@ class Plan:
         stats = self._alloc((x.rows, 2)) if self.grad else None
         rpb = S or 0
         x_bs = (S or 0) * C
+        # pair mode exists as HALF only (the first rows / 2 rows): for a LayerNorm whose readers are prefix ops
+        pm = self._pair_op([x], y, True) if half and out_t is None and x.rows % 2 == 0 else None
+        if pm is None:
+            self._need_full(x)
+        else:
+            pm.on_dup = lambda: self._need_full(x)
         fwd = lambda: ops.layernorm(x.t, gm, bt, out=y.t, ldy=ldy or C, stats=stats, rows=x.rows,
-                                    rows_per_batch=rpb, x_bs=x_bs, y_bs=y_bs)
+                                    rows_per_batch=rpb, x_bs=x_bs, y_bs=y_bs, pair=PAIR_HALF if y.pair is not None else 0)
         if not self.grad:
             self._add(fwd)
             return y
@@ -297,7 +359,7 @@ class Plan:
         self._add(fwd, make_bwd, [x])
         return y
 
-    def ln_linear(self, x: Act, norm: str, name: str, *, geglu=False) -> Act:
+    def ln_linear(self, x: Act, norm: str, name: str, *, geglu=False, half=False) -> Act:
         """linear(LayerNorm(x)) (attention.py:185,206,223 + the projection behind each).  No-grad plans of an engine with
         `fold_ln` read the rows RAW: one statistics pass (mean, rstd per row; no normalised copy is written or re-read)
         and the normalisation rides in the GEMM's epilogue on the gamma-folded weights (weightstore._lnlin,
@@ -307,10 +369,10 @@ class Plan:
         # the statistics-only form of lgd_layernorm_f16 (y = NULL) exists in the row kernels only: widths up to 1536
         # (every SD 1.x / 2.x / SDXL-refiner transformer); wider rows keep the two ops
         if self.grad or not eng.fold_ln or x.C > 1536:
-            y = self.layernorm(x, norm)
+            y = self.layernorm(x, norm, half=True)       # (HALF only where the linear behind it runs in pair mode)
             if geglu:
-                return self.linear(y, name, geglu=True)
-            return self.linear(y, name, bias=has_b)
+                return self.linear(y, name, geglu=True, half=half)
+            return self.linear(y, name, bias=has_b, half=half)
         W, cs, b = eng.w.h[f"{name}.wln"], eng.w.f[f"{name}.cs"], eng.w.f[f"{name}.bln"]
         N, K = W.shape
         M = x.rows
@@ -320,11 +382,13 @@ class Plan:
                           rowstat=stats, colsum=cs)
         tag = "attn_path" if any(t in name for t in (".attn1.", ".attn2.", ".fuser.attn.")) else None
         xt = x.t
-        self._add(lambda: (ops.layernorm_stats(xt, K, stats=stats, rows=M), ops.gemm_launch(d, tag)))
+        # the statistics are read by this GEMM only: in pair mode it reads those of the first M / 2 rows
+        sp = PAIR_HALF if self._pair_op([x], y, half, d) is not None else 0
+        self._add(lambda: (ops.layernorm_stats(xt, K, stats=stats, rows=M, pair=sp), ops.gemm_launch(d, tag)))
         return y
 
     # ---- attention -------------------------------------------------------------------------
-    def self_attn(self, qkv: Act, heads: int, S: int, Sk: Optional[int] = None) -> Act:
+    def self_attn(self, qkv: Act, heads: int, S: int, Sk: Optional[int] = None, half=False) -> Act:
         """Flash attention over a fused [B*(Sk), 3C] projection; queries are the first S rows of each
         image (Sk = S+30 for the GLIGEN fuser, attention.py:50)."""
         B = self.B
@@ -336,8 +400,9 @@ class Plan:
         lse = self._alloc((B, heads, S)) if self.grad else None
         scale = d ** -0.5
         qt, kt, vt = qkv.t, qkv.t[:, C:], qkv.t[:, 2 * C:]
+        pm = self._pair_op([qkv], o, half)
         fwd = lambda: ops.attn_fwd(qt, kt, vt, o.t, B, heads, S, Sk, d, scale, lse=lse,
-                                   q_view=view, k_view=view, v_view=view)
+                                   q_view=view, k_view=view, v_view=view, pair=pm.mode if pm is not None else 0)
         if not self.grad:
             self._add(fwd)
             return o
@@ -384,6 +449,7 @@ class Plan:
             if self.grad:
                 self.gmaps[key] = self._alloc((B, heads, S, T))   # zeroed by the energy launch (EnergyTables.run)
         kt, vt = kv_t, kv_t[:, :, C:]
+        self._need_full(q)
 
         def fwd():
             ops.cross_attn_fwd(q.t, kt, vt, o.t, B, heads, S, T, d, scale, probs=probs,
@@ -419,9 +485,10 @@ class Plan:
         eng = self.eng
         eps = eng.cfg.norm_eps
         HW = H * H
-        h = self.groupnorm(x, skip, f"{r.prefix}.norm1", HW, eps, True)
-        h = self.conv(h, f"{r.prefix}.conv1", H, temb_off=eng.w.temb_offsets[r.prefix])
-        h = self.groupnorm(h, None, f"{r.prefix}.norm2", HW, eps, True)
+        # (half: inside the shared prefix of a CFG pair plan these three feed the next op of the resnet only)
+        h = self.groupnorm(x, skip, f"{r.prefix}.norm1", HW, eps, True, half=True)
+        h = self.conv(h, f"{r.prefix}.conv1", H, temb_off=eng.w.temb_offsets[r.prefix], half=True)
+        h = self.groupnorm(h, None, f"{r.prefix}.norm2", HW, eps, True, half=True)
         if r.shortcut:
             sc = self.shortcut(x, skip, f"{r.prefix}.conv_shortcut")
         else:
@@ -435,18 +502,21 @@ class Plan:
         eng, B = self.eng, self.B
         S = H * H
         C, heads = a.channels, a.heads
-        n = self.groupnorm(x, None, f"{a.prefix}.norm", S, 1e-6, False)          # transformer_2d.py:283
-        h = self.linear(n, f"{a.prefix}.proj_in")
+        # Shared prefix of a CFG pair plan (self._pair): everything up to attn1.to_out — with the GLIGEN fuser off up to
+        # attn2.to_q — of the first block sees neither text nor grounding tokens.  The residual stream leaves it whole.
+        n = self.groupnorm(x, None, f"{a.prefix}.norm", S, 1e-6, False, half=True)          # transformer_2d.py:283
+        h = self.linear(n, f"{a.prefix}.proj_in", half=True)
         for dpt in range(a.depth):                                               # transformer_2d.py:293-302
             t = f"{a.prefix}.transformer_blocks.{dpt}"
             key = tuple(a.key[:3]) + (dpt,)
             # 1. self-attention (attention.py:185-195)
-            qkv = self.ln_linear(h, f"{t}.norm1", f"{t}.attn1.qkv")
-            h = self.linear(self.self_attn(qkv, heads, S), f"{t}.attn1.to_out.0", res=h)
+            qkv = self.ln_linear(h, f"{t}.norm1", f"{t}.attn1.qkv", half=True)
+            h = self.linear(self.self_attn(qkv, heads, S, half=True), f"{t}.attn1.to_out.0", res=h)
             if dpt == 0:
                 self.dbg[f"{a.prefix}.after_attn1"] = h
             # 1.5 GLIGEN gated self-attention (attention.py:43-53, 198-200)
             if self.fuser:
+                self._pair = False                       # the fuser's keys hold the grounding tokens
                 f = f"{t}.fuser"
                 Sk = S + N_OBJ_TOKENS
                 cat = eng.fuser_cat(eng.kv_name(a.prefix, dpt), B, S, self.obj_off)   # [B*(S+30), C], tail rows preset
@@ -461,6 +531,7 @@ class Plan:
                 self.dbg[f"{a.prefix}.after_fuser"] = h
             # 2. cross-attention (attention.py:204-220) — the hook of attention_processor.py:377-483
             q = self.ln_linear(h, f"{t}.norm2", f"{t}.attn2.to_q")
+            self._pair = False                           # cross-attention reads the text
             last = self.stop_key is not None and key == self.stop_key
             o = self.cross_attn(q, key, eng.kv_name(a.prefix, dpt), heads, S, last)
             if last:
@@ -489,6 +560,12 @@ class Plan:
         d_in = ops.gemm_desc(lat8, w.h["conv_in.w8"], x0.t, B * L * L, c0, 72, c0=8, lda0=8, taps=9, hin=L, win=L, hout=L,
                              wout=L, bias=w.f["conv_in.b"], ldc=c0, splits=1)
         f_in = 2.0 * B * L * L * c0 * 9 * cfg.in_channels                   # algorithmic: the filter has 9 x 4 taps, not 72
+        self._pair = self.pair_shared
+        if self._pair_op([], None, False, d_in) is not None:
+            # the second half of latents_in is never read: the caller need not fill it (LMDSampler._main_pass)
+            self.latents_pair = True
+            lat = lat[:B // 2]
+            f_in *= 0.5
         self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8), ops.gemm_launch(d_in, None, f_in)))
         skips = [(x, L)]
         H = L
@@ -504,6 +581,8 @@ class Plan:
                         if x is None:            # the last saved / guidance key is a down-level one: the plan ends here
                             done = True
                             break
+                    self._pair = False           # the shared prefix ends inside the first resnet / transformer pair
+                    self._need_full(x)
                     skips.append((x, H))
                 if done:
                     break
@@ -787,17 +866,22 @@ class UNetEngine:
 
     # ---- plans ---------------------------------------------------------------------------------
     def plan(self, B: int, L: int, *, grad=False, fuser=False, stop_key=None, save_keys=(),
-             text_batch_offset=0, obj_batch_offset=0) -> Plan:
+             text_batch_offset=0, obj_batch_offset=0, pair_shared=False) -> Plan:
+        """pair_shared: the caller feeds a CFG batch — rows b and b + B/2 share their latents (and the call its
+        timestep); the ops in front of the first text / grounding-token read are then computed once per pair
+        (Plan.pair_shared).  Ignored for grad plans, odd batches, per-row time embeddings (text_time) and with the
+        library option "cfg_pair" at 0."""
         mode = self.tuning_mode or ops.current_tuning_mode()
+        pair_shared = bool(pair_shared and not grad and B % 2 == 0 and self.temb_rows == 1 and ops.get_option("cfg_pair"))
         key = (B, L, grad, fuser, tuple(stop_key) if stop_key else None, tuple(map(tuple, save_keys)),
-               text_batch_offset, obj_batch_offset, mode, self.fold_ln)
+               text_batch_offset, obj_batch_offset, mode, self.fold_ln, pair_shared)
         if B + text_batch_offset > self.max_text_batch:
             raise RuntimeError(f"plan batch {B} (+{text_batch_offset}) exceeds max_text_batch={self.max_text_batch}")
         if key not in self._plans:
             with ops.tuning(mode):                        # descriptors are tuned when they are built
                 self._plans[key] = Plan(self, B, L, grad=grad, fuser=fuser, stop_key=stop_key,
                                         save_keys=save_keys, text_batch_offset=text_batch_offset,
-                                        obj_batch_offset=obj_batch_offset)
+                                        obj_batch_offset=obj_batch_offset, pair_shared=pair_shared)
             while len(self._plans) > self.MAX_PLANS:
                 self._plans.popitem(last=False)       # a dropped plan's graphs stay valid: the arena never moves
         self._plans.move_to_end(key)
