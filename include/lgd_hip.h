@@ -341,6 +341,34 @@ int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float* latent, co
                                 const float* noise, const int32_t* picks, const float* coef_table, const int32_t* dyn,
                                 float* hist, int P, int Pp, int C, int HW, int n_steps, int n_boot, int prep,
                                 void* stream);
+/* MultiDiffusion over overlapping views (additive export: LGD_ABI_VERSION stays 12) — MultiDiffusion.generate of the
+ * reference (generation/multidiffusion.py:210-280): a latent panorama [C][Hp][Wp] seen through V = nbh*nbw windows of
+ * 64x64 at stride 8, view v starting at ((v / nbw)*8, (v % nbw)*8) with nbh = (Hp-64)/8+1, nbw = (Wp-64)/8+1
+ * (get_views).  The UNet batch holds a chunk of whole views [v0, v0+nv) in a buffer with room for nvc views: view j of
+ * the chunk owns rows j*Pp + k of the uncond half and (nvc + j)*Pp + k of the cond half, k < Pp (P prompts padded to Pp).
+ * Two launches bracket the UNet call of every chunk of step i = dyn[0]:
+ *   prep = 1: x_in rows of the chunk's views, both halves:  x_k = latent[view], and for 1 <= k < P while i < n_boot
+ *     b = (masks[k][view] >= 0.5),  x_k = x_k*b + (sqrt(a)*bg[picks[i][v][k-1]] + sqrt(1-a)*noise[view])*(1-b),
+ *     a = coef_table[i][0]  (DDIMScheduler.add_noise at t_i).  eps, value, count and hist are not read.
+ *   prep = 0: for every panorama element, over the chunk's views that cover it in ascending view order
+ *     value += sum_k masks[k] * DDIM(x_k, cfg_k)   (the sum over k first, in prompt order),
+ *     count += sum_k masks[k]                       (normalization only),
+ *     cfg_k = eu_k + gs*(ec_k - eu_k) with indep_uncond, else gs*(ec_k - eu_k) + eu_0 (the view's prompt-0 uncond row).
+ *     The chunk with v0 == 0 starts from zero instead of reading value / count (no memset launch); the chunk with
+ *     v0 + nv == V finishes: latent = normalization ? (count > 0 ? value / count : value) : value, hist[i+1] = latent
+ *     when hist != NULL (it does not store value / count).  Without normalization overlapping views sum, as in the
+ *     reference; elements no view covers come out 0.  One thread owns four consecutive elements and gathers: no atomics,
+ *     and the result does not depend on how the V views are split into chunks.
+ * eps, x_in: fp32 [2*nvc*Pp][C][64*64]; latent, value, count, noise: fp32 [C][Hp][Wp]; masks: fp32 [>= P][Hp][Wp];
+ * bg: fp32 [n_boot][C][64*64]; picks: device int32 [n_steps][V][P-1] (indices clamped to [0, n_boot)); hist: fp32
+ * [n_steps+1][C][Hp][Wp] or NULL; coef_table, dyn: as lgd_multidiffusion_step_f32.  value / count may be NULL when one
+ * chunk holds all views (count also without normalization).  Hp, Wp >= 64, Wp % 4 == 0, P <= Pp, the view range inside
+ * V = nbh*nbw, nv <= nvc, 16-byte aligned buffers, bg / noise / picks present when bootstrapping: else LGD_ERR_ARG. */
+int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float* latent, float* value, float* count,
+                                 const float* masks, const float* bg, const float* noise, const int32_t* picks,
+                                 const float* coef_table, const int32_t* dyn, float* hist, int P, int Pp, int C, int Hp,
+                                 int Wp, int V, int v0, int nv, int nvc, int n_steps, int n_boot, int indep_uncond,
+                                 int normalization, int prep, void* stream);
 /* Model-input scaling of sigma-space samplers — [ext] diffusers EulerDiscreteScheduler.scale_model_input, which the
  * SDXL-refiner pass applies before every UNet call (generation/sdxl_refinement.py:29 -> StableDiffusionXLImg2ImgPipeline):
  *   out[r][i] = x[i] * table[dyn[0] * row_stride + col]   for r < reps   (reps = 2: the CFG pair reads one latent).

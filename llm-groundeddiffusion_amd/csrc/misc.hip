@@ -391,9 +391,7 @@ __global__ __launch_bounds__(256) void cfg_plms_kernel(
 // over 64 CUs.  A thread reads x_k (the UNet input rows it wrote one step earlier) and the CFG pair of every prompt in
 // prompt order and owns its output elements: no atomics, deterministic.  The DDIM arithmetic is cfg_ddim_kernel's,
 // lane by lane, so that one prompt with mask 1 reproduces the plain CFG + DDIM step bit for bit.
-__device__ __forceinline__ float md_ddim(float eu, float ec, float xv, float gs, bool vpred, float sa, float sb,
-                                         float pa, float pb) {
-  float m = eu + gs * (ec - eu);
+__device__ __forceinline__ float md_ddim_of(float m, float xv, bool vpred, float sa, float sb, float pa, float pb) {
   float x0, e;
   if (vpred) {
     x0 = sa * xv - sb * m;
@@ -403,6 +401,11 @@ __device__ __forceinline__ float md_ddim(float eu, float ec, float xv, float gs,
     x0 = (xv - sb * e) / sa;
   }
   return pa * x0 + pb * e;
+}
+
+__device__ __forceinline__ float md_ddim(float eu, float ec, float xv, float gs, bool vpred, float sa, float sb,
+                                         float pa, float pb) {
+  return md_ddim_of(eu + gs * (ec - eu), xv, vpred, sa, sb, pa, pb);
 }
 
 __global__ __launch_bounds__(64) void multidiffusion_step_kernel(
@@ -470,6 +473,141 @@ __global__ __launch_bounds__(64) void multidiffusion_step_kernel(
     reinterpret_cast<f32x4*>(x_in + (long)k * n)[v] = x;
     reinterpret_cast<f32x4*>(x_in + (long)(Pp + k) * n)[v] = x;
   }
+}
+
+// MultiDiffusion over V overlapping 64x64 views of a latent panorama [C][Hp][Wp] (MultiDiffusion.generate of the
+// reference, generation/multidiffusion.py:210-280; window 64, stride 8): see lgd_hip.h.  The UNet batch holds a chunk of
+// whole views [v0, v0 + nv): view j of the chunk owns rows j*Pp + k (uncond half) and nvc*Pp + j*Pp + k (cond half).
+//
+// prep: one thread = four consecutive fp32 lanes of one plane of one view of the chunk; it writes the UNet input rows of
+// step dyn[0] (the bootstrapping blend is multidiffusion_step_kernel's expression, with panorama-sized noise and masks).
+constexpr int MD_WIN = 64, MD_STRIDE = 8, MD_WHW = MD_WIN * MD_WIN;
+
+__global__ __launch_bounds__(64) void multidiffusion_views_prep_kernel(
+    float* __restrict__ x_in, const float* __restrict__ latent, const float* __restrict__ masks,
+    const float* __restrict__ bg, const float* __restrict__ noise, const int32_t* __restrict__ picks,
+    const float* __restrict__ coef_table, const int32_t* __restrict__ dyn, int P, int Pp, int C, int Hp, int Wp,
+    int nbw, int V, int v0, int nv, int nvc, int n_steps, int n_boot) {
+  const int step = dyn[0];
+  if (step < 0 || step >= n_steps) return;
+  const long t = blockIdx.x * 64L + threadIdx.x;
+  const long per_view = (long)C * (MD_WHW / 4);
+  if (t >= nv * per_view) return;
+  const int j = (int)(t / per_view);
+  const int r = (int)(t - j * per_view);
+  const int c = r / (MD_WHW / 4);
+  const int p = (r - c * (MD_WHW / 4)) << 2;                 // first of four lanes inside the 64x64 window
+  const int v = v0 + j;
+  const int y = (v / nbw) * MD_STRIDE + p / MD_WIN, x = (v % nbw) * MD_STRIDE + p % MD_WIN;
+  const long plane = (long)Hp * Wp;
+  const long q = (long)y * Wp + x;                           // panorama position of the four lanes (one row: x % 4 == 0)
+  const f32x4 acc = *reinterpret_cast<const f32x4*>(latent + c * plane + q);
+  const bool boot = step < n_boot && P > 1;
+  float sa = 0.f, sb = 0.f;
+  f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+  if (boot) {
+    const float a_n = coef_table[step * 4];
+    sa = sqrtf(a_n);
+    sb = sqrtf(1.f - a_n);
+    nz = *reinterpret_cast<const f32x4*>(noise + c * plane + q);
+  }
+  const long row = (long)C * MD_WHW;
+  const long in_row = (long)c * MD_WHW + p;
+  for (int k = 0; k < Pp; ++k) {
+    f32x4 xk = acc;
+    if (boot && k >= 1 && k < P) {
+      int pk = picks[((long)step * V + v) * (P - 1) + (k - 1)];
+      pk = pk < 0 ? 0 : (pk >= n_boot ? n_boot - 1 : pk);
+      const f32x4 g = *reinterpret_cast<const f32x4*>(bg + pk * row + in_row);
+      const f32x4 mk = *reinterpret_cast<const f32x4*>(masks + k * plane + q);
+      f32x4 b;
+      b.x = mk.x >= 0.5f ? 1.f : 0.f;
+      b.y = mk.y >= 0.5f ? 1.f : 0.f;
+      b.z = mk.z >= 0.5f ? 1.f : 0.f;
+      b.w = mk.w >= 0.5f ? 1.f : 0.f;
+      const f32x4 noisy = sa * g + sb * nz;                   // DDIMScheduler.add_noise(bg, noise[view], t)
+      xk = acc * b + noisy * (1.f - b);
+    }
+    *reinterpret_cast<f32x4*>(x_in + ((long)j * Pp + k) * row + in_row) = xk;
+    *reinterpret_cast<f32x4*>(x_in + ((long)(nvc + j) * Pp + k) * row + in_row) = xk;
+  }
+}
+
+// accumulate: one thread = four consecutive fp32 lanes of the panorama (view starts are multiples of 8, so the four lanes
+// lie inside or outside a view together).  It gathers from the chunk's views that cover it in ascending view order and
+// owns its value / count / latent elements: no atomics, and the add order does not depend on how the views are chunked.
+__global__ __launch_bounds__(64) void multidiffusion_views_accum_kernel(
+    const float* __restrict__ eps, const float* __restrict__ x_in, float* __restrict__ latent, float* __restrict__ value,
+    float* __restrict__ count, const float* __restrict__ masks, const float* __restrict__ coef_table,
+    const int32_t* __restrict__ dyn, float* __restrict__ hist, int P, int Pp, int C, int Hp, int Wp, int nbw, int V,
+    int v0, int nv, int nvc, int n_steps, int indep_uncond, int normalization) {
+  const int step = dyn[0];
+  if (step < 0 || step >= n_steps) return;
+  const long plane = (long)Hp * Wp;
+  const long n = C * plane;
+  const long e = (blockIdx.x * 64L + threadIdx.x) << 2;
+  if (e >= n) return;
+  const int c = (int)(e / plane);
+  const long q = e - c * plane;
+  const int y = (int)(q / Wp), x = (int)(q - (long)y * Wp);
+  const float* ct = coef_table + step * 4;
+  const float a_t = ct[0], a_p = ct[1], gs = ct[2];
+  const bool vpred = ct[3] != 0.f;
+  const float sa = sqrtf(a_t), sb = sqrtf(1.f - a_t), pa = sqrtf(a_p), pb = sqrtf(1.f - a_p);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 val = zero, cnt = zero;
+  if (v0 > 0) {
+    val = *reinterpret_cast<const f32x4*>(value + e);
+    if (normalization) cnt = *reinterpret_cast<const f32x4*>(count + e);
+  }
+  const long row = (long)C * MD_WHW;
+  for (int j = 0; j < nv; ++j) {
+    const int v = v0 + j;
+    const int hs = (v / nbw) * MD_STRIDE, ws = (v % nbw) * MD_STRIDE;
+    if (y < hs || y >= hs + MD_WIN || x < ws || x >= ws + MD_WIN) continue;
+    const long in_row = (long)c * MD_WHW + (y - hs) * MD_WIN + (x - ws);
+    const float* eu_row = eps + (long)j * Pp * row + in_row;
+    const float* ec_row = eps + (long)(nvc + j) * Pp * row + in_row;
+    const float* x_row = x_in + (long)j * Pp * row + in_row;
+    const f32x4 eu0 = *reinterpret_cast<const f32x4*>(eu_row);
+    f32x4 vs = zero, cs = zero;
+    for (int k = 0; k < P; ++k) {
+      const f32x4 eu = *reinterpret_cast<const f32x4*>(eu_row + k * row);
+      const f32x4 ec = *reinterpret_cast<const f32x4*>(ec_row + k * row);
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x_row + k * row);
+      const f32x4 mk = *reinterpret_cast<const f32x4*>(masks + k * plane + q);
+      f32x4 d;
+      if (indep_uncond) {
+        d.x = md_ddim(eu.x, ec.x, xv.x, gs, vpred, sa, sb, pa, pb);
+        d.y = md_ddim(eu.y, ec.y, xv.y, gs, vpred, sa, sb, pa, pb);
+        d.z = md_ddim(eu.z, ec.z, xv.z, gs, vpred, sa, sb, pa, pb);
+        d.w = md_ddim(eu.w, ec.w, xv.w, gs, vpred, sa, sb, pa, pb);
+      } else {                                               // one unconditional row per view, the directions differ
+        const f32x4 m = gs * (ec - eu) + eu0;
+        d.x = md_ddim_of(m.x, xv.x, vpred, sa, sb, pa, pb);
+        d.y = md_ddim_of(m.y, xv.y, vpred, sa, sb, pa, pb);
+        d.z = md_ddim_of(m.z, xv.z, vpred, sa, sb, pa, pb);
+        d.w = md_ddim_of(m.w, xv.w, vpred, sa, sb, pa, pb);
+      }
+      vs = k == 0 ? mk * d : vs + mk * d;                     // the sum over prompts first, then into the panorama
+      cs = k == 0 ? mk : cs + mk;
+    }
+    val += vs;
+    cnt += cs;
+  }
+  if (v0 + nv < V) {
+    *reinterpret_cast<f32x4*>(value + e) = val;
+    if (normalization) *reinterpret_cast<f32x4*>(count + e) = cnt;
+    return;
+  }
+  if (normalization) {                                        // torch.where(count > 0, value / count, value)
+    val.x = cnt.x > 0.f ? val.x / cnt.x : val.x;
+    val.y = cnt.y > 0.f ? val.y / cnt.y : val.y;
+    val.z = cnt.z > 0.f ? val.z / cnt.z : val.z;
+    val.w = cnt.w > 0.f ? val.w / cnt.w : val.w;
+  }
+  *reinterpret_cast<f32x4*>(latent + e) = val;
+  if (hist) *reinterpret_cast<f32x4*>(hist + (long)(step + 1) * n + e) = val;
 }
 
 // uint8 HWC images [npix][3] -> the 8-channel fp16 operand of the VAE encoder's conv_in (lgd_hip.h): channels 0..2 =
@@ -761,6 +899,40 @@ extern "C" int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float*
   hipLaunchKernelGGL(multidiffusion_step_kernel, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0,
                      reinterpret_cast<hipStream_t>(stream), eps, x_in, latent, masks, bg, noise, picks, coef_table,
                      dyn, hist, P, Pp, HW, n, n_steps, n_boot, prep);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float* latent, float* value, float* count,
+                                            const float* masks, const float* bg, const float* noise,
+                                            const int32_t* picks, const float* coef_table, const int32_t* dyn,
+                                            float* hist, int P, int Pp, int C, int Hp, int Wp, int V, int v0, int nv,
+                                            int nvc, int n_steps, int n_boot, int indep_uncond, int normalization,
+                                            int prep, void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (!x_in || !latent || !masks || !coef_table || !dyn || P < 1 || Pp < P || C < 1 || n_steps < 1 || n_boot < 0 ||
+      (prep != 0 && prep != 1) || (!prep && !eps))
+    return LGD_ERR_ARG;
+  if (Hp < MD_WIN || Wp < MD_WIN || (Wp & 3) || Hp > 4096 || Wp > 4096 || C > 64) return LGD_ERR_ARG;
+  const int nbh = (Hp - MD_WIN) / MD_STRIDE + 1, nbw = (Wp - MD_WIN) / MD_STRIDE + 1;   // get_views
+  if (V != nbh * nbw || v0 < 0 || nv < 1 || v0 + nv > V || nvc < nv || (long)nvc * Pp > (1 << 20)) return LGD_ERR_ARG;
+  const bool single = v0 == 0 && nv == V;
+  if (!prep && !single && (!value || (normalization && !count))) return LGD_ERR_ARG;
+  if (prep && n_boot > 0 && P > 1 && (!bg || !noise || !picks)) return LGD_ERR_ARG;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (misaligned(eps) || misaligned(x_in) || misaligned(latent) || misaligned(value) || misaligned(count) ||
+      misaligned(masks) || misaligned(bg) || misaligned(noise) || misaligned(hist))
+    return LGD_ERR_ARG;  // 16-byte vectors: every plane, window row and mask row starts on a vector boundary
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (prep) {
+    const long nt = (long)nv * C * (MD_WHW / 4);
+    hipLaunchKernelGGL(multidiffusion_views_prep_kernel, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, x_in, latent,
+                       masks, bg, noise, picks, coef_table, dyn, P, Pp, C, Hp, Wp, nbw, V, v0, nv, nvc, n_steps, n_boot);
+  } else {
+    const long nt = (long)C * Hp * Wp / 4;
+    hipLaunchKernelGGL(multidiffusion_views_accum_kernel, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, eps, x_in,
+                       latent, value, count, masks, coef_table, dyn, hist, P, Pp, C, Hp, Wp, nbw, V, v0, nv, nvc,
+                       n_steps, indep_uncond ? 1 : 0, normalization ? 1 : 0);
+  }
   return lgd_check_launch();
 }
 

@@ -6,8 +6,13 @@ own networks from `models.sd_key` at import.  Here `init()` builds them from the
 needs diffusers and the checkpoint), `init_synthetic()` builds seeded random networks of the same architecture, and
 `run()` calls `init()` the first time when neither was called.
 
-Only what run() can reach is served: one 512 x 512 view, indep_uncond, no normalization, DDIM.  The image is converted
-like the reference's T.ToPILImage (truncating), not rounded like the other plugins'."""
+run() reaches one 512 x 512 view with indep_uncond and no normalization; `sd.generate`, the public method of the
+reference's MultiDiffusion class, serves panoramas (64 x 64 latent windows at stride 8, get_views) with its defaults
+indep_uncond=False and normalization=True.  DDIM.  The image is converted like the reference's T.ToPILImage
+(truncating), not rounded like the other plugins'.
+
+One deviation in sd.generate: the background colours come from a device generator seeded with `seed`, which is what
+run()'s seed_everything(seed) amounts to; the reference's bare generate() leaves them to the global RNG state."""
 from PIL import Image
 
 import models
@@ -22,7 +27,38 @@ fg_negative_prompt = "artifacts, blurry, smooth texture, bad quality, distortion
 
 sd_kw = dict(H=512, W=512)
 
-sd = None          # EasyDict(sampler, encoder, tokenizer, text_encoder, device) once init() / init_synthetic() ran
+get_views = md_core.get_views
+
+
+class MultiDiffusion(EasyDict):
+    """`sd`: EasyDict(sampler, encoder, tokenizer, text_encoder, device) with the reference class's generate()."""
+
+    def generate(self, masks, prompts, negative_prompts="", height=512, width=2048, num_inference_steps=50,
+                 guidance_scale=7.5, bootstrapping=20, indep_uncond=False, normalization=True, seed=None):
+        """generation/multidiffusion.py:161-285 -> PIL image (width x height).  masks: (P, 1, height/8, width/8) float,
+        row 0 the background; prompts: P strings; negative_prompts: P strings, or one string for all of them.  seed is
+        required (the reference's torch.manual_seed(None) fails too)."""
+        if seed is None:
+            raise TypeError("seed is required: the reference seeds the start latent with torch.manual_seed(seed)")
+        if self.tokenizer is None or self.text_encoder is None:
+            raise RuntimeError("no tokenizer / text encoder: init_synthetic() needs stand-ins for them")
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        P = len(prompts)
+        negs = [negative_prompts] * P if isinstance(negative_prompts, str) else list(negative_prompts)
+        print(f"With bootstrapping ({bootstrapping} steps)" if bootstrapping else "No bootstrapping")
+        print(prompts)
+        draws = md_core.draw_randomness(self.encoder, self.device, seed, bootstrapping, P, num_inference_steps,
+                                        in_channels=self.sampler.eng.cfg.in_channels, size=(height, width),
+                                        n_views=len(get_views(height, width)), bg_size=md_core.SIZE)
+        texts = md_core.encode_texts(self.tokenizer, self.text_encoder, prompts, negs, self.device)
+        out = md_core.multidiffusion_generate(self.sampler, texts, masks, draws["start_latent"], draws["bg_latents"],
+                                              draws["picks"], steps=num_inference_steps, guidance_scale=guidance_scale,
+                                              n_boot=bootstrapping, indep_uncond=indep_uncond,
+                                              normalization=normalization)
+        return Image.fromarray(out["image"])
+
+
+sd = None          # MultiDiffusion(sampler, encoder, tokenizer, text_encoder, device) once init() / init_synthetic() ran
 
 
 def init(device="cuda"):
@@ -39,8 +75,8 @@ def init(device="cuda"):
     from lgd_amd.vae import HipVAEEncoder
     md = models.load_sd(models.sd_key)
     vae = AutoencoderKL.from_pretrained(models.sd_key, subfolder="vae")
-    sd = EasyDict(sampler=md.sampler, encoder=HipVAEEncoder(vae.state_dict(), device), tokenizer=md.tokenizer,
-                  text_encoder=md.text_encoder, device=device)
+    sd = MultiDiffusion(sampler=md.sampler, encoder=HipVAEEncoder(vae.state_dict(), device), tokenizer=md.tokenizer,
+                        text_encoder=md.text_encoder, device=device)
     return sd
 
 
@@ -52,8 +88,8 @@ def init_synthetic(name="sd15", seed=0, device="cuda", tokenizer=None, text_enco
     md = models.load_synthetic(name, seed=seed, device=device, with_vae=False)
     state = _vae.synth_aekl_state_dict(seed=seed)
     md.sampler.vae = _vae.HipVAEDecoder(state, device)
-    sd = EasyDict(sampler=md.sampler, encoder=_vae.HipVAEEncoder(state, device), tokenizer=tokenizer,
-                  text_encoder=text_encoder, device=device)
+    sd = MultiDiffusion(sampler=md.sampler, encoder=_vae.HipVAEEncoder(state, device), tokenizer=tokenizer,
+                        text_encoder=text_encoder, device=device)
     return sd
 
 

@@ -1,8 +1,8 @@
 """MultiDiffusion, the region-prompt baseline of the reference (generation/multidiffusion.py, `generate.py --run-model
 multidiffusion`), on the HIP engine.
 
-What the reference's `run()` can reach, and nothing else: one 512 x 512 view (get_views(512, 512) yields one window),
-indep_uncond=True, normalization=False, DDIM (eta 0) from the checkpoint's scheduler config.  Per step i:
+What the reference's `run()` reaches: one 512 x 512 view (get_views(512, 512) yields one window), indep_uncond=True,
+normalization=False, DDIM (eta 0) from the checkpoint's scheduler config.  Per step i:
     x_k = latent for every prompt k; while i < bootstrapping, for k >= 1 outside the region of prompt k the latent is
           replaced by add_noise(bg[pick], start latent, t_i) (a randomly picked constant-colour background);
     the UNet runs on [x_0 .. x_{P-1}] * 2 with text [uncond_k; cond_k];
@@ -10,6 +10,15 @@ indep_uncond=True, normalization=False, DDIM (eta 0) from the checkpoint's sched
 Host prep (boxes -> disjoint masks and prompts) is restated below from utils/parse.py and generation/multidiffusion.py,
 which do not exist where this runs.  The device side is one launch of lgd_multidiffusion_step_f32 per step after the
 UNet (plus one to write step 0's input rows), and the UNet plan and that launch are captured as one hipGraph.
+
+What `MultiDiffusion.generate` itself offers beyond that, panoramas: V = len(get_views(H, W)) overlapping 64 x 64 latent
+windows at stride 8, each denoised per prompt as above, then
+    latent <- value / count where count > 0,  value = sum over views and prompts of mask_k * DDIM(x_k, cfg_k) placed at
+              the view, count = the same sum of mask_k (normalization; without it count = 1 and overlapping views sum),
+    cfg_k = eps_uncond_0 + gs * (eps_cond_k - eps_uncond_k) unless indep_uncond.
+That path (_generate_views) is taken for any other latent size or flag value and leaves the single-view path as it was:
+chunks of views per UNet call, lgd_multidiffusion_views_f32 before (input rows) and after (gather into value / count, and
+behind the last chunk the latent) each call, one step one hipGraph.
 
 Precision: UNet in fp16 with fp32 accumulation, CFG and the step in fp32, the HIP VAE in fp16 (the reference runs the
 VAE in fp32 and the UNet and CFG in fp16 under autocast).
@@ -25,6 +34,7 @@ from .scheduler import DDIMScheduler
 F32 = torch.float32
 SIZE = (512, 512)                 # utils/parse.py:21-24: box_scale (h, w)
 LATENT_SCALE = 0.18215            # generation/multidiffusion.py:157,163
+WINDOW = 64                       # get_views: the latent window of a view (stride 8)
 
 
 # ---- host prep --------------------------------------------------------------------------------------------------------
@@ -140,27 +150,44 @@ def prepare(gen_boxes, bg_prompt, bg_negative, fg_negative_prompt, extra_neg_pro
                 boxes=gen_boxes)
 
 
+def get_views(panorama_height, panorama_width, window_size=64, stride=8):
+    """generation/multidiffusion.py:30-43: the (h_start, h_end, w_start, w_end) latent windows of a panorama given in
+    pixels, row-major; a size that is no window + whole strides leaves a right / bottom margin no view covers."""
+    # true division and float floor division, as there: 516 pixels are 64.5 latent rows and still one window
+    rows = int((panorama_height / 8 - window_size) // stride + 1)
+    cols = int((panorama_width / 8 - window_size) // stride + 1)
+    starts = [(r * stride, c * stride) for r in range(rows) for c in range(cols)] if rows > 0 and cols > 0 else []
+    return [(hs, hs + window_size, ws, ws + window_size) for hs, ws in starts]
+
+
 # ---- the random draws of one run --------------------------------------------------------------------------------------
-def draw_randomness(encoder, device, seed, n_boot, n_prompts, steps, in_channels=4, size=SIZE, chunk=4):
+def draw_randomness(encoder, device, seed, n_boot, n_prompts, steps, in_channels=4, size=SIZE, chunk=4, n_views=1,
+                    bg_size=None):
     """The reference's draws, call for call (generation/multidiffusion.py:170-197,205-214,236 with run():443-447):
       seed_everything(seed); torch.rand(n_boot, 3, device) -> background colours;
       per background in order: constant image, 2*img-1, VAE posterior sample (one device randn) * 0.18215;
       torch.manual_seed(seed); start latent randn (1, C, H/8, W/8) on the CPU;
-      per step i < n_boot: torch.randint(0, n_boot, (P-1,)) on the CPU (nothing else draws inside the loop).
+      per step i < n_boot and per view in order: torch.randint(0, n_boot, (P-1,)) on the CPU (nothing else draws inside
+      the loop).
     Explicit generators seeded like the global ones give the same numbers without touching process state.
     encoder: .encode_moments(image [B,3,H,W] in [-1,1]) -> (mean, logvar clamped to [-30, 20]) (HipVAEEncoder); the
     moments may be computed in batches, the posterior draws follow the reference's order.
-    Returns dict(colours (n_boot,3), bg_latents (n_boot,C,h,w) on `device`, start_latent (1,C,h,w) CPU,
-    picks int64 (min(n_boot, steps), P-1) CPU)."""
+    size: pixels of the start latent (the panorama); bg_size: pixels of the background images, `size` when None (a
+    panorama passes 512 x 512, what get_random_background always encodes, line 113-118); n_views: len(get_views(*size)).
+    Returns dict(colours (n_boot,3), bg_latents (n_boot,C,bh/8,bw/8) on `device`, start_latent (1,C,h/8,w/8) CPU,
+    picks int64 CPU: (min(n_boot, steps), P-1) for n_views == 1 (one view draws what it always drew), else
+    (min(n_boot, steps), n_views, P-1))."""
     device = torch.device(device)
     h, w = size
+    bh, bw = size if bg_size is None else bg_size
+    n_views = int(n_views)
     colours = bg_lat = None
     if n_boot:
         gd = torch.Generator(device).manual_seed(int(seed))
         colours = torch.rand(n_boot, 3, generator=gd, device=device)
         moments = []
         for c0 in range(0, n_boot, chunk):
-            img = colours[c0:c0 + chunk, :, None, None].repeat(1, 1, h, w)
+            img = colours[c0:c0 + chunk, :, None, None].repeat(1, 1, bh, bw)
             moments.append(encoder.encode_moments(2 * img - 1))
         mean = torch.cat([m for m, _ in moments]).to(device, F32)
         std = torch.exp(0.5 * torch.cat([lv for _, lv in moments]).to(device, F32))
@@ -171,8 +198,11 @@ def draw_randomness(encoder, device, seed, n_boot, n_prompts, steps, in_channels
         bg_lat = torch.cat(rows)
     g = torch.Generator().manual_seed(int(seed))
     start = torch.randn((1, in_channels, h // 8, w // 8), generator=g, dtype=F32)
-    picks = torch.stack([torch.randint(0, n_boot, (n_prompts - 1,), generator=g) for _ in range(min(n_boot, steps))]) \
-        if n_boot and steps else torch.zeros((0, n_prompts - 1), dtype=torch.int64)
+    n_pick = min(n_boot, steps) if n_boot and steps else 0
+    picks = torch.stack([torch.randint(0, n_boot, (n_prompts - 1,), generator=g) for _ in range(n_pick * n_views)]) \
+        if n_pick and n_views else torch.zeros((0, n_prompts - 1), dtype=torch.int64)
+    if n_views != 1:                                                      # step-major, view-minor: lines 210-223
+        picks = picks.reshape(n_pick, n_views, n_prompts - 1)
     return dict(colours=colours, bg_latents=bg_lat, start_latent=start, picks=picks)
 
 
@@ -203,6 +233,23 @@ class _MDState(LoopState):
         self.hist = torch.zeros((T + 1, C, L, L), device=dev, dtype=F32)
 
 
+class _MDViewsState(LoopState):
+    """_MDState for a panorama seen through V views: the panorama-sized latent, frozen noise, masks and the value / count
+    accumulators of lgd_multidiffusion_views_f32, view-sized backgrounds, and one pick per step, view and foreground
+    prompt."""
+
+    def __init__(self, dev, P, C, Hp, Wp, V, T, n_boot):
+        super().__init__(torch.zeros((C, Hp, Wp), device=dev, dtype=F32), T)
+        self.noise = torch.zeros((C, Hp, Wp), device=dev, dtype=F32)
+        self.value = torch.zeros((C, Hp, Wp), device=dev, dtype=F32)
+        self.count = torch.zeros((C, Hp, Wp), device=dev, dtype=F32)
+        self.masks = torch.zeros((P, Hp * Wp), device=dev, dtype=F32)
+        self.bg = torch.zeros((max(n_boot, 1), C, WINDOW, WINDOW), device=dev, dtype=F32)
+        self.picks = torch.zeros((T, V, max(P - 1, 1)), device=dev, dtype=torch.int32)
+        self.ctab = torch.zeros((T, 4), device=dev, dtype=F32)
+        self.hist = torch.zeros((T + 1, C, Hp, Wp), device=dev, dtype=F32)
+
+
 def _ddim_of(sampler):
     """The DDIM scheduler of the checkpoint (models/models.py:49; generation/multidiffusion.py:86)."""
     s = sampler.scheduler
@@ -226,8 +273,8 @@ def padded_rows(sampler, P):
 @torch.no_grad()
 def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, picks, steps=50, guidance_scale=10.0,
                             n_boot=20, decode=True, save_all_latents=False, first_step=0, n_steps=None, noise=None,
-                            record_inputs=False):
-    """MultiDiffusion.generate (generation/multidiffusion.py:167-282) as run() calls it.
+                            record_inputs=False, indep_uncond=True, normalization=False, views_per_call=None):
+    """MultiDiffusion.generate (generation/multidiffusion.py:167-282); with the defaults, as run() calls it.
 
     texts: (2P, 77, Cx) = [uncond_0 .. uncond_{P-1}; cond_0 .. cond_{P-1}];  masks: (P, 1, L, L) or (P, L, L), row 0 the
     background;  start_latent: (1, C, L, L);  bg_latents: (n_boot, C, L, L) encoded backgrounds;  picks: int
@@ -236,10 +283,20 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
     first_step / n_steps: run only those steps, from `start_latent` as the state before step first_step; the frozen
     bootstrapping noise is then `noise` (by default the start latent, as in the reference).
     Returns dict(latent (1,C,L,L), image uint8 (H,W,3) truncated like ToPILImage or None, latents_all (T+1,1,C,L,L)
-    with save_all_latents, inputs: per step run the (P,C,L,L) UNet input rows with record_inputs)."""
+    with save_all_latents, inputs: per step run the (P,C,L,L) UNet input rows with record_inputs).
+
+    A start latent (1, C, Hp, Wp) other than 64 x 64 (with masks (P, 1, Hp, Wp)), indep_uncond=False (prompt 0's
+    unconditional prediction for every prompt of a view) or normalization=True (value / count over the overlaps) take
+    the path over the V = len(get_views(8 Hp, 8 Wp)) views: see _generate_views.  bg_latents stay (n_boot, C, 64, 64),
+    picks become (>= min(n_boot, steps), V, P-1), `inputs` per step (V, P, C, 64, 64), and views_per_call caps the views
+    per UNet call below what the engine's text buffers hold."""
     eng, dev = sampler.eng, sampler.dev
     P = int(masks.shape[0])
     n_boot = int(n_boot)
+    if tuple(start_latent.shape[2:]) != (WINDOW, WINDOW) or not indep_uncond or normalization:
+        return _generate_views(sampler, texts, masks, start_latent, bg_latents, picks, steps, guidance_scale, n_boot,
+                               decode, save_all_latents, first_step, n_steps, noise, record_inputs, bool(indep_uncond),
+                               bool(normalization), views_per_call)
     _, C, L, _ = start_latent.shape
     if tuple(texts.shape[:1]) != (2 * P,):
         raise ValueError(f"texts {tuple(texts.shape)} for {P} prompts: want (2P, 77, Cx) = [uncond; cond]")
@@ -302,6 +359,108 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
     lat = st.lat.reshape(1, C, L, L).clone()
     image = decode_truncating(sampler.vae, lat)[0] if decode else None
     return dict(latent=lat, image=image, inputs=inputs,
+                latents_all=st.hist[:T + 1].clone().unsqueeze(1) if save_all_latents else None)
+
+
+@torch.no_grad()
+def _generate_views(sampler, texts, masks, start_latent, bg_latents, picks, steps, guidance_scale, n_boot, decode,
+                    save_all_latents, first_step, n_steps, noise, record_inputs, indep_uncond, normalization,
+                    views_per_call):
+    """The loop of generation/multidiffusion.py:210-280 over the V views of a panorama.  The engine's text buffers hold
+    max_text_batch rows, so the views go through the UNet in chunks of max_text_batch // (2 Pp) whole views; the text
+    rows are repeated per view of a chunk.  Per chunk: lgd_multidiffusion_views_f32 (prep) writes the chunk's input
+    rows, the plan runs, lgd_multidiffusion_views_f32 adds the chunk's share to value / count, and behind the last
+    chunk writes the blended latent.  All chunks use one plan: a last, shorter chunk leaves the rows behind its views
+    as they are (finite: an earlier chunk's), the UNet computes them and nobody reads the result.  One step, all its
+    chunks, is one captured hipGraph."""
+    eng, dev = sampler.eng, sampler.dev
+    P = int(masks.shape[0])
+    _, C, Hp, Wp = start_latent.shape
+    if Hp < WINDOW or Wp < WINDOW or Wp % 4:
+        raise ValueError(f"panorama latent {Hp} x {Wp}: want at least {WINDOW} x {WINDOW} and a width divisible by 4")
+    if tuple(texts.shape[:1]) != (2 * P,):
+        raise ValueError(f"texts {tuple(texts.shape)} for {P} prompts: want (2P, 77, Cx) = [uncond; cond]")
+    if int(masks.numel()) != P * Hp * Wp:
+        raise ValueError(f"masks {tuple(masks.shape)} for a {Hp} x {Wp} latent: want (P, 1, Hp, Wp)")
+    if n_boot < 0:
+        raise ValueError("bootstrapping must be >= 0")
+    views = get_views(8 * Hp, 8 * Wp)
+    V = len(views)                                           # >= 1: the latent holds at least one window
+    sch = _ddim_of(sampler)
+    sch.set_timesteps(int(steps))
+    ts = sch.timesteps
+    T = len(ts)
+    n_pick = min(n_boot, T)
+    boot = n_boot > 0 and P > 1
+    if boot:
+        picks = torch.as_tensor(picks)
+        if picks.numel() < n_pick * V * (P - 1) or bg_latents is None or \
+                tuple(bg_latents.shape) != (n_boot, C, WINDOW, WINDOW):
+            raise ValueError(f"bootstrapping needs bg_latents (n_boot, C, {WINDOW}, {WINDOW}) and picks "
+                             "(min(n_boot, steps), V, P-1)")
+        picks = picks.reshape(-1, V, P - 1)
+        if n_pick and (int(picks[:n_pick].min()) < 0 or int(picks[:n_pick].max()) >= n_boot):
+            raise ValueError("picks index the n_boot backgrounds")
+    Pp = padded_rows(sampler, P)
+    nvc = min(V, eng.max_text_batch // (2 * Pp))
+    if views_per_call is not None:
+        nvc = min(nvc, int(views_per_call))
+    if nvc < 1:
+        raise ValueError("views_per_call must be >= 1")
+
+    st = sampler.md_states.get(("views", P, Pp, C, Hp, Wp, T, n_boot, indep_uncond, normalization, nvc),
+                               lambda: _MDViewsState(dev, P, C, Hp, Wp, V, T, n_boot))
+
+    # ---- per-run constants (before graph capture so that the capture's warm-up launch sees valid inputs)
+    st.ctab.copy_(sch.coef_table(guidance_scale, dev, timesteps=ts))
+    unc, cond = texts[:P].to(dev, F32), texts[P:].to(dev, F32)
+    pad = lambda t: torch.cat([t, t[:1].expand(Pp - P, *t.shape[1:])]) if Pp > P else t
+    eng.prepare_timesteps([int(t) for t in ts])
+    eng.prepare_text(torch.cat([pad(unc).repeat(nvc, 1, 1), pad(cond).repeat(nvc, 1, 1)]))
+    eng.set_step(0)
+    plan = eng.plan(2 * Pp * nvc, WINDOW)
+    st.picks.zero_()
+    kw = dict(n_prompts=P, rows_per_view=Pp, n_views=V, n_steps=T, indep_uncond=indep_uncond,
+              normalization=normalization, bg=st.bg, noise=st.noise, picks=st.picks, n_boot=n_boot)
+    chunks = [(v0, min(nvc, V - v0)) for v0 in range(0, V, nvc)]
+
+    def prep(v0, nv):
+        ops.multidiffusion_views(None, plan.latents_in, st.lat, st.value, st.count, st.masks, st.ctab, eng.dyn, v0=v0,
+                                 nv=nv, prep=True, **kw)
+
+    def step_fn():
+        for v0, nv in chunks:
+            prep(v0, nv)
+            plan.forward()
+            ops.multidiffusion_views(plan.eps_out, plan.latents_in, st.lat, st.value, st.count, st.masks, st.ctab,
+                                     eng.dyn, v0=v0, nv=nv, hist=st.hist, **kw)
+    plan.latents_in.zero_()                                  # rows behind a short last chunk: finite from the start
+    runner = st.runner("step", step_fn, sampler.use_graphs)
+
+    # ---- state of this call
+    st.masks.copy_(masks.reshape(P, Hp * Wp).to(dev, F32))
+    st.lat.copy_(start_latent.reshape(C, Hp, Wp).to(dev, F32))
+    st.noise.copy_((start_latent if noise is None else noise).reshape(C, Hp, Wp).to(dev, F32))
+    if boot:
+        st.bg.copy_(bg_latents.to(dev, F32))
+        if n_pick:
+            st.picks[:n_pick].copy_(picks[:n_pick].to(dev, torch.int32))
+    first_step, last_step = clamp_steps(first_step, n_steps, T)
+    st.hist[first_step].copy_(st.lat)
+    inputs = []
+
+    def one_step(index):
+        if record_inputs:                                    # the rows the step's own prep launches write again
+            rows = []
+            for v0, nv in chunks:
+                prep(v0, nv)
+                rows.append(plan.latents_in[:nv * Pp].reshape(nv, Pp, C, WINDOW, WINDOW)[:, :P].clone())
+            inputs.append(torch.cat(rows))
+        runner()
+    run_steps(eng, first_step, last_step, one_step)
+    lat = st.lat.reshape(1, C, Hp, Wp).clone()
+    image = decode_truncating(sampler.vae, lat)[0] if decode else None
+    return dict(latent=lat, image=image, inputs=inputs, views=views,
                 latents_all=st.hist[:T + 1].clone().unsqueeze(1) if save_all_latents else None)
 
 

@@ -794,6 +794,27 @@ def multidiffusion_step(eps, x_in, latent, masks, coef_table, dyn, *, n_prompts,
     return latent
 
 
+def multidiffusion_views(eps, x_in, latent, value, count, masks, coef_table, dyn, *, n_prompts, rows_per_view, n_views,
+                         v0, nv, n_steps, indep_uncond=True, normalization=False, bg=None, noise=None, picks=None,
+                         n_boot=0, hist=None, prep=False):
+    """MultiDiffusion over overlapping 64x64 views of the panorama `latent` (C, Hp, Wp) for the chunk of views
+    [v0, v0 + nv): with prep=True the chunk's UNet input rows of step dyn[0], else the chunk's share of value / count
+    and, behind the last view, the blended latent; x_in / eps fp32 (2 * nvc * rows_per_view, C, 64, 64), see lgd_hip.h."""
+    rows, C_, L, _ = x_in.shape
+    P, Pp = int(n_prompts), int(rows_per_view)
+    _, Hp, Wp = latent.shape
+    if L != 64 or rows % (2 * Pp) or tuple(x_in.shape[2:]) != (64, 64) or (eps is not None and eps.shape != x_in.shape):
+        raise RuntimeError(f"multidiffusion_views: x_in {tuple(x_in.shape)} is not (2 * views * {Pp}, C, 64, 64)")
+    nvc = rows // (2 * Pp)
+    nbytes = 4.0 * C_ * 4096 * nv * (1 + 2 * Pp) if prep else 4.0 * (C_ * 4096 * nv * 3 * P + latent.numel() * 6)
+    _prof("multidiffusion_views_prep_kernel" if prep else "multidiffusion_views_accum_kernel", nbytes,
+          lambda: _call("lgd_multidiffusion_views_f32", _p(None if prep else eps), _p(x_in), _p(latent), _p(value),
+                        _p(count), _p(masks), _p(bg), _p(noise), _p(picks), _p(coef_table), _p(dyn), _p(hist), P, Pp,
+                        C_, Hp, Wp, int(n_views), int(v0), int(nv), nvc, int(n_steps), int(n_boot),
+                        1 if indep_uncond else 0, 1 if normalization else 0, 1 if prep else 0, _stream()))
+    return latent
+
+
 def axpy(g, x, coef_table, step_idx, col, active=None):
     per = x.numel() // x.shape[0] if active is not None else 0
     _prof("axpy_kernel", 12.0 * x.numel(),

@@ -96,36 +96,38 @@ class HipVAEDecoder:
         """`AutoencoderKL.state_dict()` (models/models.py:41) -> decoder on the HIP kernels."""
         return cls(state_dict, device, **kw)
 
-    def _bias_map(self, B, L):
+    def _bias_map(self, B, H, W):
         """conv_in bias + what post_quant_conv's bias contributes through the taps that lie inside the image:
-        fp16 [B*L*L, C] (residual operand of the conv_in GEMM)."""
-        key = (B, L)
+        fp16 [B*H*W, C] (residual operand of the conv_in GEMM)."""
+        key = (B, H, W)
         if key not in self._bias_maps:
-            v = torch.ones(3, L)
-            v[0, 0] = 0          # tap row ky = 0 reads y - 1: outside at y = 0
-            v[2, L - 1] = 0
-            m = torch.einsum("okl,ky,lx->yxo", self._tap_bias, v, v) + self._b_in            # [L, L, C]
-            self._bias_maps = {key: m.reshape(1, L * L, -1).expand(B, -1, -1).reshape(B * L * L, -1)
+            vy, vx = torch.ones(3, H), torch.ones(3, W)
+            vy[0, 0] = vx[0, 0] = 0          # tap row ky = 0 reads y - 1: outside at y = 0
+            vy[2, H - 1] = vx[2, W - 1] = 0
+            m = torch.einsum("okl,ky,lx->yxo", self._tap_bias, vy, vx) + self._b_in          # [H, W, C]
+            self._bias_maps = {key: m.reshape(1, H * W, -1).expand(B, -1, -1).reshape(B * H * W, -1)
                                .to(self.dev, torch.float16).contiguous()}
         return self._bias_maps[key]
 
-    def _res(self, p, x, B, H):
+    def _res(self, p, x, B, H, W=None):
+        """W=None: a square H x H map (the encoder's)."""
         ops = self.ops
-        HW = H * H
+        W = H if W is None else W
+        HW = H * W
         h = ops.groupnorm(x, B, HW, self.groups, self.eps, p["n1"][0], p["n1"][1], True)
-        h = ops.conv3x3(h, p["c1"][0], B, H, H, bias=p["c1"][1])
+        h = ops.conv3x3(h, p["c1"][0], B, H, W, bias=p["c1"][1])
         h = ops.groupnorm(h, B, HW, self.groups, self.eps, p["n2"][0], p["n2"][1], True)
         sc = x if p["sc"] is None else ops.linear(x, p["sc"][0], p["sc"][1])
-        return ops.conv3x3(h, p["c2"][0], B, H, H, bias=p["c2"][1], res=sc)
+        return ops.conv3x3(h, p["c2"][0], B, H, W, bias=p["c2"][1], res=sc)
 
-    def _attn(self, p, x, B, H):
-        """Single-head attention over the H*H positions at width C (512): the head is wider than the flash kernels'
+    def _attn(self, p, x, B, H, W=None):
+        """Single-head attention over the H*W positions at width C (512): the head is wider than the flash kernels'
         160, so the batch runs as three BATCHED GEMM launches + one row softmax:
             scores[b] = q[b] k[b]^T      ->  P = softmax(scores)      (q, k carry C^-1/4 each)
             vt[b]     = Wv n[b]^T        (V^T directly from the projection: no transpose pass)
             out[b]    = P[b] vt[b]^T + bv   (rows of P sum to 1, so V's bias is added once, behind the product)"""
         ops = self.ops
-        S = H * H
+        S = H * (H if W is None else W)
         C = x.shape[1]
         F16 = torch.float16
         n = ops.groupnorm(x, B, S, self.groups, self.eps, p["n"][0], p["n"][1], False)
@@ -144,29 +146,32 @@ class HipVAEDecoder:
 
     @torch.no_grad()
     def decode(self, z):
+        """z (B, C, Hl, Wl) -> (B, 3, 8 Hl, 8 Wl); Hl and Wl need not be equal (a MultiDiffusion panorama).  The mid-block
+        attention runs over all Hl*Wl positions with a materialised fp16 score matrix of (Hl*Wl)^2 elements per image:
+        32 MB at 64 x 64, 512 MB at the 64 x 256 latent of a 512 x 2048 panorama.  That is accepted: it is one call per
+        image."""
         ops = self.ops
         z = z.to(self.dev, torch.float32).contiguous()
-        B, _, L, _ = z.shape
+        B, _, H, W = z.shape
         lat8 = ops.nchw_to_nhwc8(z)
-        h = torch.empty((B * L * L, self.c_mid), device=self.dev, dtype=torch.float16)
-        ops.gemm_launch(ops.gemm_desc(lat8, self.conv_in_w8, h, B * L * L, self.c_mid, 72, c0=8, lda0=8, taps=9, hin=L,
-                                      win=L, hout=L, wout=L, res=self._bias_map(B, L), ldr=self.c_mid, ldc=self.c_mid,
-                                      splits=1))
-        H = L
-        h = self._res(self.mid[0], h, B, H)
-        h = self._attn(self.attn, h, B, H)
-        h = self._res(self.mid[1], h, B, H)
+        h = torch.empty((B * H * W, self.c_mid), device=self.dev, dtype=torch.float16)
+        ops.gemm_launch(ops.gemm_desc(lat8, self.conv_in_w8, h, B * H * W, self.c_mid, 72, c0=8, lda0=8, taps=9, hin=H,
+                                      win=W, hout=H, wout=W, res=self._bias_map(B, H, W), ldr=self.c_mid,
+                                      ldc=self.c_mid, splits=1))
+        h = self._res(self.mid[0], h, B, H, W)
+        h = self._attn(self.attn, h, B, H, W)
+        h = self._res(self.mid[1], h, B, H, W)
         for blk, up in self.ups:
             for r in blk:
-                h = self._res(r, h, B, H)
+                h = self._res(r, h, B, H, W)
             if up is not None:
-                h = ops.conv3x3(h, up[0], B, H, H, bias=up[1], ups=1)
-                H *= 2
-        h = ops.groupnorm(h, B, H * H, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
+                h = ops.conv3x3(h, up[0], B, H, W, bias=up[1], ups=1)
+                H, W = 2 * H, 2 * W
+        h = ops.groupnorm(h, B, H * W, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
         # conv_out (128 -> 3, padded to 4 channels) on the matrix cores as well: at 512 x 512 the one-wave-per-pixel
         # kernel took 1.7 ms per image, the implicit GEMM (N = 4 inside a 64-wide tile) a few tens of microseconds
-        y = ops.conv3x3(h, self.conv_out[0], B, H, H, bias=self.conv_out[1])            # [B*H*H, 4] fp16
-        return y.view(B, H, H, 4)[..., :3].permute(0, 3, 1, 2).float()
+        y = ops.conv3x3(h, self.conv_out[0], B, H, W, bias=self.conv_out[1])            # [B*H*W, 4] fp16
+        return y.view(B, H, W, 4)[..., :3].permute(0, 3, 1, 2).float()
 
 
 def make_hip_vae(device, seed=0):
