@@ -1,0 +1,83 @@
+"""The GEMM launch contract, checked where there is no GPU: the pinned acceptance table of
+tests/gemm_conformance_cases.py equals what lgd_gemm_check answers, the tile codes are exactly ops.TILE_NAMES, and the
+"exact" data of every form really is exact — which is what entitles tests/test_gemm_conformance_gpu.py to compare
+with zero tolerance."""
+import os
+import sys
+
+import pytest
+import torch
+
+import lgd_amd  # noqa: F401
+from lgd_amd import ops
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gemm_conformance_cases as gcc  # noqa: E402
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _library():
+    """The acceptance matrix is the library's answer (lgd_gemm_check): host code, no GPU."""
+    import __graft_entry__ as ge
+    ge.build()
+
+
+def test_pinned_acceptance_table_is_what_the_library_answers():
+    pinned = gcc.pinned()
+    assert list(pinned) == list(gcc.FORMS), "the pinned table has one row per form, in order"
+    diff = []
+    for name, form in gcc.FORMS.items():
+        assert sorted(pinned[name]) == gcc.TILES, name
+        for tile, cell in zip(gcc.TILES, gcc.acceptance_row(form)):
+            if pinned[name][tile] != cell:
+                diff.append((name, tile, pinned[name][tile], cell))
+    assert not diff, f"(form, code, pinned, library): {diff}"
+
+
+def test_tile_codes_are_exactly_tile_names():
+    """The codes the library accepts on a plain contiguous descriptor, among 1..79, are the ones ops.TILE_NAMES names."""
+    p = gcc.P
+    accepted = [t for t in range(1, 80) if ops.gemm_accepts(ops.gemm_desc(p, p, p, 512, 640, 640, splits=1, tile=t))]
+    assert accepted == sorted(ops.TILE_NAMES)
+    assert ops.gemm_accepts(ops.gemm_desc(p, p, p, 512, 640, 640, splits=1, tile=0))          # 0 = the library's heuristic
+
+
+def test_acceptance_floors():
+    """No code and no form may drop out of the matrix unnoticed: the minima of the pinned table."""
+    pinned = gcc.pinned()
+    per_code = {t: sum(pinned[n][t] != "." for n in pinned) for t in gcc.TILES}
+    per_form = {n: sum(c != "." for c in pinned[n].values()) for n in pinned}
+    assert min(per_code.values()) == gcc.MIN_FORMS_PER_CODE, per_code
+    assert min(per_form.values()) == gcc.MIN_CODES_PER_FORM, per_form
+    assert gcc.MIN_FORMS_PER_CODE >= 9 and gcc.MIN_CODES_PER_FORM >= 14
+    # every form of the issue's list is there, with the pair modes on five of them
+    for name in ("plain_k64", "plain_k192", "plain_k448", "plain_k72", "plain_n4", "tiny_m", "strided", "inplace", "res_f32",
+                 "out_f32_bias2", "geglu", "geglu_res", "rownorm", "rownorm_geglu", "two_src", "two_src_small", "conv_same",
+                 "conv_s2", "conv_ups1", "conv_ups2", "conv_two_src", "conv_c8", "conv_split", "batched", "batched_split",
+                 "split2", "split4of5", "split_geglu", "split_out_f32"):
+        assert name in pinned
+    for base in ("plain_k192", "strided", "conv_same", "geglu", "rownorm"):
+        assert "half:" + base in pinned and "dup:" + base in pinned
+
+
+@pytest.mark.parametrize("name", [n for n, f in gcc.FORMS.items() if f.exact])
+def test_exact_forms_are_exact(name):
+    """Integer / half-integer data: the fp64 reference IS a value of the output type, and the sum of the magnitudes
+    of every term of an element stays below 2^24 (with multiples of 0.5: below 2^23 in units of the spacing), so every
+    partial sum in any order is an exact fp32 number.  A correct kernel therefore returns the reference bit for bit."""
+    c = gcc.FORMS[name].case("exact")
+    assert torch.equal(c.rounded_ref(), c.ref)
+    assert torch.equal(c.ref * 2, (c.ref * 2).round())                       # multiples of 0.5
+    assert 2 * c.s_max < 2 ** 24
+    assert float(c.ref.abs().max()) <= 1024                                  # half-integers are exact in fp16 up to 1024
+
+
+def test_geglu_forms_have_no_exact_mode():
+    assert [n for n, f in gcc.FORMS.items() if not f.exact] == [n for n in gcc.FORMS if "geglu" in n]
+
+
+def test_split4of5_drops_its_empty_trailing_split():
+    """Five K tiles over four splits are two tiles each: three splits carry work.  The descriptor keeps what the caller
+    asked for; the library normalises its own copy (the workspace is sized for four)."""
+    f = gcc.FORMS["split4of5"]
+    assert f.K // 64 == 5 and f.splits == 4 and all(f.accepts(t)[0] == (t != 44) for t in gcc.TILES)

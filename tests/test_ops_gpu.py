@@ -205,6 +205,7 @@ def test_conv3x3_phase_tiles(dev, tile, B, H, C, Cout, splits):
 @pytest.mark.parametrize("M,N,K,tile", [
     (66017, 1000, 320, 34), (66017, 1000, 640, 33), (40000, 968, 192, 37), (70001, 320, 320, 38), (33000, 2560, 320, 35),
     (131072, 320, 64, 39), (20000, 1920, 576, 40),
+    (20000, 1000, 192, 41), (20000, 1000, 192, 42),        # 64-row tiles of more than 96 KB of LDS: one workgroup per CU, thousands of tiles
 ])
 def test_gemm_persistent_tile_loop_ragged(dev, M, N, K, tile):
     """More output tiles than resident workgroups and K <= 640: the 8-wave tiles run their persistent loop (one
