@@ -244,6 +244,27 @@ int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void
                             const void* v, int64_t ldv, int64_t v_bs, void* o, int64_t ldo, int64_t o_bs, int B,
                             int H, int S, int d, float scale, void* stream);
 
+/* lgd_attn_plan (additive export: LGD_ABI_VERSION stays 12): the variant code of the kernel instantiation a call with these arguments runs under the
+ * current option state ("attn32", "attn32_nw", "attn32_var", "attn_w4", "attn_w4_pipe") — answered by the function the
+ * launches themselves switch on; host only, nothing is launched.  code = family * 100000 + DP * 100 + sub (DP: the padded
+ * head dim of the instantiation); the Python binding names every code (ops.ATTN_VARIANTS).
+ *   op = LGD_ATTN_OP_FWD:       lgd_attn_fwd_f16 / lgd_attn_fwd_pair_f16 (pair != 0) / lgd_cross_attn_fwd_f16 (probs != 0:
+ *                               a map is captured) / lgd_attn_causal_fwd_f16 (causal != 0).  `aligned` is ignored: every
+ *                               view the entry points accept suits every forward kernel.
+ *   op = LGD_ATTN_OP_BWD:       lgd_attn_bwd_f16 / lgd_attn_bwd_keys_f16 (Sk_grad <= Sk).
+ *   op = LGD_ATTN_OP_CROSS_BWD: lgd_cross_attn_bwd_f16.  aligned: q / go as 16-byte and gq as 8-byte vectors (ld, per-image
+ *                               stride, base pointer); 0 selects the one-wave-per-row kernel.
+ * Sk_grad is only read by LGD_ATTN_OP_BWD.  Negative: LGD_ERR_ARG / LGD_ERR_UNSUPPORTED as the launch would answer.
+ * Preconditions of every attention entry point (else LGD_ERR_ARG, before anything touches the device): d % 8 == 0; ld and
+ * per-image stride of every fp16 input view multiples of 8 and its base 16-byte aligned; of every fp16 output view
+ * multiples of 4 and 8-byte aligned (lgd_cross_attn_bwd_f16 also serves q / go / gq views that are not, element by
+ * element). */
+#define LGD_ATTN_OP_FWD 0
+#define LGD_ATTN_OP_BWD 1
+#define LGD_ATTN_OP_CROSS_BWD 2
+int lgd_attn_plan(int op, int B, int H, int Sq, int Sk, int Sk_grad, int d, int probs, int causal, int pair,
+                  int aligned);
+
 /* ---------------------------------------------------------------------------------------------
  * Elementwise pieces.
  * ------------------------------------------------------------------------------------------- */

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "../../include/lgd_hip.h"
 #include "attn_w4.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -1002,120 +1003,157 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_self32_kernel(const AttnArg
   }
 }
 
-template <int DP, bool SAVE_P>
-void launch_attn_dp(const AttnArgs& a, hipStream_t st) {
-  if constexpr (SAVE_P) {
-    dim3 grid((a.Sq + 63) / 64, a.H, a.B);   // (no pair mode: lgd_attn_fwd_pair_f16 never captures a map)
-    hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, dim3(256), 0, st, a);
-  } else {
-    const int gz = a.pair ? a.B / 2 : a.B;      // thresholds below keep the full B: same kernel as the full launch
-    // round-3 kernel (32x32x16 MFMA, in-wave software pipelining) for the narrow heads with a spare slot, once there
-    // are enough 256-query blocks to fill the chip; LGD_ATTN32=0 keeps the 16x16x32 kernel (A/B timing, tools)
-    if constexpr (DP == 64 || DP == 96) {
-      // g_attn32 (lgd_set_option("attn32", v); initial value from LGD_ATTN32 in the environment): 0 = never (the
-      // 16x16x32 kernel: A/B timing), 1 = default, 2 = for every problem size (tests)
-      const int a32 = attn32_mode();
-      const int dk = ((a.d + 2 + 15) / 16) * 16;
-      // measured (tools/attn_quick.py, B = 16): d = 80 (DK = 96) 97 -> 80 us; d = 40 (DK = 48) 570 -> 630 us — at two
-      // waves per SIMD (170 VGPRs) its stalls are not covered the way the 16x16x32 kernel's four waves cover theirs —
-      // so by default only the DK = 96 heads take this kernel
-      // round 6: the threshold was 512 blocks of 256 queries ("fill the chip twice"); measured (tools/attn80_ab.py) the
-      // 8-image calls (256 blocks) run 70.3 -> 42.0 us on this kernel (305 -> 512 TF/s; with the fuser's 1054 keys 73.7 ->
-      // 45.9) and the 4-image calls (128 blocks) 34.7 -> 33.2 us with 128-query workgroups
-      const long blocks256 = (long)((a.Sq + 255) / 256) * a.H * a.B;
-      if (a32 && a.d % 8 == 0 && (a32 == 2 || (dk == 96 && blocks256 >= 128))) {
-        const int var = attn32_var();
-        auto go = [&](auto kern, int nw) {
-          dim3 g32((a.Sq + 32 * nw - 1) / (32 * nw), a.H, gz);
-          hipLaunchKernelGGL(kern, g32, dim3(64 * nw), 0, st, a);
-        };
-        if (attn32_nw() == 4 || (a32 != 2 && blocks256 < 256)) {
-          if (dk == 48) { go(&attn_self32_kernel<48, 2, 4>, 4); return; }
-          if (dk == 96) { go(&attn_self32_kernel<96, 3, 4>, 4); return; }
-        } else if (var == 1) {
-          if (dk == 48) { go(&attn_self32_kernel<48, 2, 8, 4, true>, 8); return; }
-          if (dk == 96) { go(&attn_self32_kernel<96, 3, 8, 4, true>, 8); return; }
-        } else if (var == 2) {
-          // (the <= 128-VGPR, two-workgroups-per-CU build of the dk = 48 kernel spilled 76 registers and is gone)
-          if (dk == 48) { go(&attn_self32_kernel<48, 2, 8, 2, false>, 8); return; }
-          if (dk == 96) { go(&attn_self32_kernel<96, 3, 8, 2, false>, 8); return; }
-        } else {
-          if (dk == 48) { go(&attn_self32_kernel<48, 2, 8>, 8); return; }
-          if (dk == 96) { go(&attn_self32_kernel<96, 3, 8>, 8); return; }
-        }
-      }
-    }
-    // two query tiles per wave once there are enough 128-query blocks to fill the chip
-    const bool qt2 = (long)((a.Sq + 127) / 128) * a.H * a.B >= 1024 && DP <= 96;
-    dim3 grid(qt2 ? (a.Sq + 127) / 128 : (a.Sq + 63) / 64, a.H, gz);
-    if constexpr (DP <= 96) {
-      // 8-wave workgroups (256 queries share each staged K / V^T tile) pay where the head is narrow: measured
-      // +15 % at d = 40 (S = 4096), +4 % at d = 80, -15 % at d = 64 (S = 9216).  LGD_ATTN_NW=4 / 8 overrides (tools).
-      static const int nw_env = [] { const char* e = getenv("LGD_ATTN_NW"); return e ? atoi(e) : 0; }();
-      const bool nw8 = nw_env ? nw_env == 8 : ((DP == 64 && a.d < 48) || DP == 96);
-      if (qt2 && nw8 && (long)((a.Sq + 255) / 256) * a.H * a.B >= 512) {
-        dim3 g8((a.Sq + 255) / 256, a.H, gz);
-        if (DP == 64 && a.d < 48) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2, DP == 64 ? 3 : DP / 16, 8>), g8, dim3(512), 0, st, a);
-        else if (a.d < DP) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((attn_self_kernel<DP, false, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
-        return;
-      }
-      if (qt2) {
-        if (DP == 64 && a.d < 48) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2, DP == 64 ? 3 : DP / 16>), grid, dim3(256), 0, st, a);
-        else if (a.d < DP) hipLaunchKernelGGL((attn_self_kernel<DP, true, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((attn_self_kernel<DP, false, 2>), grid, dim3(256), 0, st, a);
-        return;
-      }
-    }
-    if constexpr (DP == 160) {
-      // round 6: the 16x16 level (S = 256, d = 160): ONE workgroup per (image, head) — eight waves x two query tiles = all
-      // 256 queries share each staged K / V^T tile, which the 64-query workgroups stage four times over.  A workgroup of
-      // either form is a chain of four or five load -> stage -> barrier round trips of ~4.5 us (not MFMA work), so the wide
-      // form wins only where the narrow one needs two rounds of workgroups: measured (tools/attn160_ab.py, 40 launches in
-      // one graph) B = 16: 33.6 -> 23.8 us (160 -> 226 TF/s), with the fuser's 286 keys 38.0 -> 26.8; B = 8: 18.4 -> 21.8,
-      // B = 4: 14.5 -> 20.7 — hence the (image, head) count in the condition.  LGD_ATTN160=0: old form.  Same per-row
-      // arithmetic and key order: bit-identical outputs.
-      static const int wide = [] { const char* e = getenv("LGD_ATTN160"); return e ? atoi(e) : 1; }();
-      if (wide && a.d == DP && a.Sq >= 256 && (long)a.H * a.B * ((a.Sq + 63) / 64) > 256) {
-        dim3 g8((a.Sq + 255) / 256, a.H, gz);
-        hipLaunchKernelGGL((attn_self_kernel<DP, false, 2, DP / 16, 8>), g8, dim3(512), 0, st, a);
-        return;
-      }
-    }
-    if (DP == 64 && a.d < 48) hipLaunchKernelGGL((attn_self_kernel<DP, true, 1, DP == 64 ? 3 : DP / 16>), grid, dim3(256), 0, st, a);
-    else if (a.d < DP) hipLaunchKernelGGL((attn_self_kernel<DP, true, 1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_self_kernel<DP, false, 1>), grid, dim3(256), 0, st, a);
-  }
+// ---------------------------------------------------------------------------------------------
+// Dispatch: plan_fwd CHOOSES the variant code (attn_plan.h) from the arguments and the option state; launch_attn switches
+// on that code.  lgd_attn_plan answers from the same function.
+// ---------------------------------------------------------------------------------------------
+int attn_nw_env() {   // LGD_ATTN_NW=4 / 8 overrides the waves-per-workgroup choice of attn_self_kernel (tools)
+  static const int nw_env = [] { const char* e = getenv("LGD_ATTN_NW"); return e ? atoi(e) : 0; }();
+  return nw_env;
+}
+int attn160_wide_env() {   // LGD_ATTN160=0: the 64-query workgroups at d = 160 (tools)
+  static const int wide = [] { const char* e = getenv("LGD_ATTN160"); return e ? atoi(e) : 1; }();
+  return wide;
 }
 
-template <bool SAVE_P>
-int launch_attn(const AttnArgs& a, hipStream_t st) {
-  const int d = a.d;
-  if constexpr (!SAVE_P) {
-    // d = 40 (SD1.x 64x64 level): the one-wave-per-SIMD kernel of attn_w4.hip once a launch has enough 256-query
-    // workgroups to occupy the chip (it holds ONE workgroup per CU); smaller problems keep the 4-waves-per-SIMD kernel
-    const int w4 = attn_w4_mode();
-    if (w4 && d == 40) {
-      AttnW4Args w;
-      w.q = a.q; w.ldq = a.ldq; w.q_bs = a.q_bs; w.k = a.k; w.ldk = a.ldk; w.k_bs = a.k_bs;
-      w.v = a.v; w.ldv = a.ldv; w.v_bs = a.v_bs; w.o = a.o; w.ldo = a.ldo; w.o_bs = a.o_bs; w.lse = a.lse;
-      w.B = a.B; w.H = a.H; w.Sq = a.Sq; w.Sk = a.Sk; w.d = a.d; w.scale_log2 = a.scale_log2;
-      w.pair = a.pair; w.o_dup = a.o_dup; w.lse_dup = a.lse_dup;
-      const long wgs = (long)((a.Sq + 255) / 256) * a.H * a.B;
-      if (lgd_attn_w4_supported(w) && (w4 == 2 || (wgs >= 256 && a.Sk >= 256))) return lgd_attn_w4_launch(w, st);
+int attn_dp_of(int d) { return d <= 32 ? 32 : d <= 64 ? 64 : d <= 96 ? 96 : d <= 128 ? 128 : d <= 160 ? 160 : d <= 192 ? 192 : 0; }
+
+// two_pass: the exact two-pass softmax kernel (map capture, causal).  The thresholds keep the full B in pair mode: a pair
+// launch runs the kernel its full launch would.  (Every view the entry points accept suits every kernel here, the d = 40
+// kernel of attn_w4.hip included: bad_view / bad_out below are the one alignment predicate.)
+int plan_fwd(int B, int H, int Sq, int Sk, int d, bool two_pass) {
+  const int DP = attn_dp_of(d);        // 192: SAM global attention, 64 + 2 x 64 bias columns
+  if (!DP) return LGD_ERR_UNSUPPORTED;
+  if (two_pass) return attn_code(ATTN_FAM_TWOPASS, DP, 0);
+  const long blocks256 = (long)((Sq + 255) / 256) * H * B;
+  // d = 40 (SD1.x 64x64 level): the one-wave-per-SIMD kernel of attn_w4.hip once a launch has enough 256-query
+  // workgroups to occupy the chip (it holds ONE workgroup per CU); smaller problems keep the 4-waves-per-SIMD kernel
+  const int w4 = attn_w4_mode();
+  if (w4 && d == 40 && (w4 == 2 || (blocks256 >= 256 && Sk >= 256)))
+    return attn_code(ATTN_FAM_W4, 64, lgd_attn_w4_pipe() ? 1 : 0);
+  // round-3 kernel (32x32x16 MFMA, in-wave software pipelining) for the narrow heads with a spare slot, once there
+  // are enough 256-query blocks to fill the chip; LGD_ATTN32=0 keeps the 16x16x32 kernel (A/B timing, tools)
+  if (DP == 64 || DP == 96) {
+    // g_attn32 (lgd_set_option("attn32", v); initial value from LGD_ATTN32 in the environment): 0 = never (the
+    // 16x16x32 kernel: A/B timing), 1 = default, 2 = for every problem size (tests)
+    const int a32 = attn32_mode();
+    const int dk = ((d + 2 + 15) / 16) * 16;
+    // measured (tools/attn_quick.py, B = 16): d = 80 (DK = 96) 97 -> 80 us; d = 40 (DK = 48) 570 -> 630 us — at two
+    // waves per SIMD (170 VGPRs) its stalls are not covered the way the 16x16x32 kernel's four waves cover theirs —
+    // so by default only the DK = 96 heads take this kernel
+    // round 6: the threshold was 512 blocks of 256 queries ("fill the chip twice"); measured (tools/attn80_ab.py) the
+    // 8-image calls (256 blocks) run 70.3 -> 42.0 us on this kernel (305 -> 512 TF/s; with the fuser's 1054 keys 73.7 ->
+    // 45.9) and the 4-image calls (128 blocks) 34.7 -> 33.2 us with 128-query workgroups
+    if (a32 && d % 8 == 0 && (a32 == 2 || (dk == 96 && blocks256 >= 128)) && (dk == 48 || dk == 96)) {
+      const int var = attn32_var();
+      // (the <= 128-VGPR, two-workgroups-per-CU build of the dk = 48 kernel spilled 76 registers and is gone)
+      const int sub = (attn32_nw() == 4 || (a32 != 2 && blocks256 < 256)) ? ATTN32_NW4
+                      : var == 1 ? ATTN32_NW8_PF4 : var == 2 ? ATTN32_NW8_FREE : ATTN32_NW8;
+      return attn_code(ATTN_FAM_SELF32, dk, sub);
     }
   }
-  if (d <= 32) launch_attn_dp<32, SAVE_P>(a, st);
-  else if (d <= 64) launch_attn_dp<64, SAVE_P>(a, st);
-  else if (d <= 96) launch_attn_dp<96, SAVE_P>(a, st);
-  else if (d <= 128) launch_attn_dp<128, SAVE_P>(a, st);
-  else if (d <= 160) launch_attn_dp<160, SAVE_P>(a, st);
-  else if (d <= 192) launch_attn_dp<192, SAVE_P>(a, st);  // SAM global attention: 64 + 2 x 64 bias columns
-  else return LGD_ERR_UNSUPPORTED;
+  const int mode = (DP == 64 && d < 48) ? SELF_ONES3 : d < DP ? SELF_ONES : SELF_PLAIN;
+  // two query tiles per wave once there are enough 128-query blocks to fill the chip
+  const bool qt2 = (long)((Sq + 127) / 128) * H * B >= 1024 && DP <= 96;
+  if (qt2) {
+    // 8-wave workgroups (256 queries share each staged K / V^T tile) pay where the head is narrow: measured
+    // +15 % at d = 40 (S = 4096), +4 % at d = 80, -15 % at d = 64 (S = 9216).  LGD_ATTN_NW=4 / 8 overrides (tools).
+    const int nw_env = attn_nw_env();
+    const bool nw8 = nw_env ? nw_env == 8 : ((DP == 64 && d < 48) || DP == 96);
+    return attn_code(ATTN_FAM_SELF, DP, 10 * mode + (nw8 && blocks256 >= 512 ? SELF_QT2_NW8 : SELF_QT2));
+  }
+  // round 6: the 16x16 level (S = 256, d = 160): ONE workgroup per (image, head) — eight waves x two query tiles = all
+  // 256 queries share each staged K / V^T tile, which the 64-query workgroups stage four times over.  A workgroup of
+  // either form is a chain of four or five load -> stage -> barrier round trips of ~4.5 us (not MFMA work), so the wide
+  // form wins only where the narrow one needs two rounds of workgroups: measured (tools/attn160_ab.py, 40 launches in
+  // one graph) B = 16: 33.6 -> 23.8 us (160 -> 226 TF/s), with the fuser's 286 keys 38.0 -> 26.8; B = 8: 18.4 -> 21.8,
+  // B = 4: 14.5 -> 20.7 — hence the (image, head) count in the condition.  LGD_ATTN160=0: old form.  Same per-row
+  // arithmetic and key order: bit-identical outputs.
+  if (DP == 160 && attn160_wide_env() && d == DP && Sq >= 256 && (long)H * B * ((Sq + 63) / 64) > 256)
+    return attn_code(ATTN_FAM_SELF, DP, 10 * SELF_PLAIN + SELF_QT2_NW8);
+  return attn_code(ATTN_FAM_SELF, DP, 10 * mode + SELF_QT1);
+}
+
+// attn_self_kernel<DP, ONES, QT, NDT, NW> for one (DP, mode): the three workgroup shapes
+template <int DP, bool ONES, int NDT>
+void launch_self_shape(int shape, const AttnArgs& a, hipStream_t st) {
+  const int gz = a.pair ? a.B / 2 : a.B;
+  if constexpr (DP <= 96 || (DP == 160 && !ONES)) {
+    if (shape == SELF_QT2_NW8) {
+      hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 2, NDT, 8>), dim3((a.Sq + 255) / 256, a.H, gz), dim3(512), 0, st, a);
+      return;
+    }
+  }
+  if constexpr (DP <= 96) {
+    if (shape == SELF_QT2) {
+      hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 2, NDT>), dim3((a.Sq + 127) / 128, a.H, gz), dim3(256), 0, st, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 1, NDT>), dim3((a.Sq + 63) / 64, a.H, gz), dim3(256), 0, st, a);
+}
+
+template <int DP>
+void launch_fwd_code(int code, const AttnArgs& a, hipStream_t st) {
+  const int fam = attn_code_fam(code), sub = attn_code_sub(code);
+  if (fam == ATTN_FAM_TWOPASS) {
+    dim3 grid((a.Sq + 63) / 64, a.H, a.B);   // (no pair mode: lgd_attn_fwd_pair_f16 never captures a map)
+    hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, dim3(256), 0, st, a);
+    return;
+  }
+  if constexpr (DP == 64 || DP == 96) {
+    if (fam == ATTN_FAM_SELF32) {
+      constexpr int DK = DP == 64 ? 48 : 96, NDT = DP == 64 ? 2 : 3;
+      const int gz = a.pair ? a.B / 2 : a.B;
+      auto go = [&](auto kern, int nw) {
+        dim3 g32((a.Sq + 32 * nw - 1) / (32 * nw), a.H, gz);
+        hipLaunchKernelGGL(kern, g32, dim3(64 * nw), 0, st, a);
+      };
+      switch (sub) {
+        case ATTN32_NW4: go(&attn_self32_kernel<DK, NDT, 4>, 4); return;
+        case ATTN32_NW8_PF4: go(&attn_self32_kernel<DK, NDT, 8, 4, true>, 8); return;
+        case ATTN32_NW8_FREE: go(&attn_self32_kernel<DK, NDT, 8, 2, false>, 8); return;
+        default: go(&attn_self32_kernel<DK, NDT, 8>, 8); return;
+      }
+    }
+  }
+  const int mode = sub / 10, shape = sub % 10;
+  if constexpr (DP == 64) {
+    // d = 40 with the ones row needs three 16-row tiles of V^T / O^T, not DP / 16 = 4
+    if (mode == SELF_ONES3) return launch_self_shape<DP, true, 3>(shape, a, st);
+  }
+  if (mode == SELF_PLAIN) launch_self_shape<DP, false, DP / 16>(shape, a, st);
+  else launch_self_shape<DP, true, DP / 16>(shape, a, st);
+}
+
+int launch_attn(const AttnArgs& a, hipStream_t st, bool two_pass) {
+  AttnW4Args w;
+  w.q = a.q; w.ldq = a.ldq; w.q_bs = a.q_bs; w.k = a.k; w.ldk = a.ldk; w.k_bs = a.k_bs;
+  w.v = a.v; w.ldv = a.ldv; w.v_bs = a.v_bs; w.o = a.o; w.ldo = a.ldo; w.o_bs = a.o_bs; w.lse = a.lse;
+  w.B = a.B; w.H = a.H; w.Sq = a.Sq; w.Sk = a.Sk; w.d = a.d; w.scale_log2 = a.scale_log2;
+  w.pair = a.pair; w.o_dup = a.o_dup; w.lse_dup = a.lse_dup;
+  const int code = plan_fwd(a.B, a.H, a.Sq, a.Sk, a.d, two_pass);
+  if (code < 0) return code;
+  if (attn_code_fam(code) == ATTN_FAM_W4) return lgd_attn_w4_launch(w, st, attn_code_sub(code));
+  switch (attn_dp_of(a.d)) {
+    case 32: launch_fwd_code<32>(code, a, st); break;
+    case 64: launch_fwd_code<64>(code, a, st); break;
+    case 96: launch_fwd_code<96>(code, a, st); break;
+    case 128: launch_fwd_code<128>(code, a, st); break;
+    case 160: launch_fwd_code<160>(code, a, st); break;
+    default: launch_fwd_code<192>(code, a, st); break;
+  }
   return lgd_check_launch();
 }
 
-bool bad_view(int64_t ld, int d) { return (ld % 8) != 0 || (d % 8) != 0; }
+// Every kernel reads Q / K / V rows as 16-byte vectors and writes O as 8-byte vectors: the leading dimensions, the head
+// dim, the BASE pointers and the per-image strides all have to keep that alignment (no kernel here serves less).
+bool bad_view(const void* p, int64_t ld, int64_t bs, int d) {
+  return (ld % 8) != 0 || (d % 8) != 0 || (bs % 8) != 0 || (reinterpret_cast<uintptr_t>(p) & 15) != 0;
+}
+bool bad_out(const void* p, int64_t ld, int64_t bs) {
+  return (ld % 4) != 0 || (bs % 4) != 0 || (reinterpret_cast<uintptr_t>(p) & 7) != 0;
+}
 
 }  // namespace
 
@@ -1153,9 +1191,10 @@ extern "C" int lgd_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const 
                                 int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
                                 void* o, int64_t ldo, int64_t o_bs, float* lse, int B, int H, int Sq,
                                 int Sk, int d, float scale, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
-  if (bad_view(ldq, d) || bad_view(ldk, d) || bad_view(ldv, d) || (ldo % 4)) return LGD_ERR_ARG;
+  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
+  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   AttnArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -1165,7 +1204,7 @@ extern "C" int lgd_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const 
   a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
-  return launch_attn<false>(a, reinterpret_cast<hipStream_t>(stream));
+  return launch_attn(a, reinterpret_cast<hipStream_t>(stream), false);
 }
 
 // CFG pair form of lgd_attn_fwd_f16: the two halves of the batch hold identical q / k / v, so images b < B / 2 are
@@ -1175,10 +1214,11 @@ extern "C" int lgd_attn_fwd_pair_f16(const void* q, int64_t ldq, int64_t q_bs, c
                                      int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
                                      void* o, int64_t ldo, int64_t o_bs, float* lse, int B, int H, int Sq,
                                      int Sk, int d, float scale, int pair, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 2 || (B % 2) || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
   if (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) return LGD_ERR_ARG;
-  if (bad_view(ldq, d) || bad_view(ldk, d) || bad_view(ldv, d) || (ldo % 4) || (o_bs % 4)) return LGD_ERR_ARG;
+  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
+  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   AttnArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -1190,7 +1230,7 @@ extern "C" int lgd_attn_fwd_pair_f16(const void* q, int64_t ldq, int64_t q_bs, c
   a.lse_dup = pair == LGD_PAIR_DUP ? (long)(B / 2) * H * Sq : 0;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
-  return launch_attn<false>(a, reinterpret_cast<hipStream_t>(stream));
+  return launch_attn(a, reinterpret_cast<hipStream_t>(stream), false);
 }
 
 extern "C" int lgd_cross_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
@@ -1198,11 +1238,12 @@ extern "C" int lgd_cross_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
                                       int64_t v_bs, void* o, int64_t ldo, int64_t o_bs, float* probs,
                                       int tok, int cond_only, int B, int H, int Sq, int Sk, int d,
                                       float scale, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
-  if (bad_view(ldq, d) || bad_view(ldk, d) || bad_view(ldv, d) || (ldo % 4)) return LGD_ERR_ARG;
+  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
+  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
   if (cond_only && (B % 2)) return LGD_ERR_ARG;  // attention_processor.py:475
   if (tok >= Sk) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   AttnArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -1213,17 +1254,17 @@ extern "C" int lgd_cross_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (probs) return launch_attn<true>(a, st);
-  return launch_attn<false>(a, st);
+  return launch_attn(a, st, probs != nullptr);
 }
 
 extern "C" int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk,
                                        int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs, void* o,
                                        int64_t ldo, int64_t o_bs, int B, int H, int S, int d, float scale,
                                        void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 1 || H < 1 || S < 1 || d < 8) return LGD_ERR_ARG;
-  if (bad_view(ldq, d) || bad_view(ldk, d) || bad_view(ldv, d) || (ldo % 4)) return LGD_ERR_ARG;
+  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
+  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   AttnArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -1233,5 +1274,27 @@ extern "C" int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs,
   a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
   a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.d = d;
   a.scale_log2 = scale * 1.4426950408889634f;
-  return launch_attn<true>(a, reinterpret_cast<hipStream_t>(stream));   // exact two-pass softmax kernel
+  return launch_attn(a, reinterpret_cast<hipStream_t>(stream), true);   // exact two-pass softmax kernel
+}
+
+// The variant code (attn_plan.h; named in ops.ATTN_VARIANTS) the call with these arguments would run under the current
+// option state: answered by the functions the launches switch on.  Host only, touches no device.
+extern "C" int lgd_attn_plan(int op, int B, int H, int Sq, int Sk, int Sk_grad, int d, int probs, int causal, int pair,
+                             int aligned) {
+  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8 || (d % 8)) return LGD_ERR_ARG;
+  if (pair && (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP)) return LGD_ERR_ARG;
+  switch (op) {
+    case LGD_ATTN_OP_FWD:
+      if (causal && Sq != Sk) return LGD_ERR_ARG;
+      if (pair && ((B % 2) || probs || causal)) return LGD_ERR_ARG;
+      return plan_fwd(B, H, Sq, Sk, d, probs || causal);
+    case LGD_ATTN_OP_BWD:
+      if (Sk_grad < 1 || Sk_grad > Sk || probs || causal || pair) return LGD_ERR_ARG;
+      return lgd_attn_bwd_plan(B, H, Sq, Sk, d);
+    case LGD_ATTN_OP_CROSS_BWD:
+      if (causal || pair) return LGD_ERR_ARG;
+      return lgd_cross_attn_bwd_plan(Sk, d, aligned);
+    default:
+      return LGD_ERR_ARG;
+  }
 }

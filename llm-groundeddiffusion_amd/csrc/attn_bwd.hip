@@ -16,6 +16,7 @@
 // row) remains as the fallback for 96 < Sk <= 128.
 #include "common.h"
 #include "../../include/lgd_hip.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -749,38 +750,70 @@ int launch_bwd_nt(const AttnBwdArgs& a, hipStream_t st) {
   return lgd_check_launch();
 }
 
-template <int DP>
-int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {
-  // two 16-row tiles per wave once there are enough 128-row workgroups to fill the chip
-  const long wgs = (long)((a.Sq < a.Sk ? a.Sq : a.Sk) / 128) * a.H * a.B;
+int attn_bwd_env() {
   // LGD_ATTN_BWD (tools, A/B): 0 = single-buffered 4-wave kernels of round 1, 1 = double-buffered, 2 = double-buffered 8 waves.
   // Measured (tools/attn_bwd_quick.py, same box): d = 40, S = 4096: 607 -> 587 (1) -> 547 us (2); with the fuser's
   // 4126 keys 679 -> 653 -> 655; d = 80 and d = 160 unchanged; d = 64 at S = 9216 (SD2.1): 1067 -> 1199 us with two stages
   // (79 KB of LDS per workgroup halves the resident workgroups) — so only the narrow-head case takes the new variants.
   static const int env = [] { const char* e = getenv("LGD_ATTN_BWD"); return e ? atoi(e) : -2; }();
+  return env;
+}
+
+int bwd_dp_of(int d) { return d <= 32 ? 32 : d <= 64 ? 64 : d <= 96 ? 96 : d <= 128 ? 128 : d <= 160 ? 160 : 0; }
+
+// the variant code (attn_plan.h) of a self-attention backward: launch_bwd switches on it, lgd_attn_plan reports it
+int plan_bwd(int B, int H, int Sq, int Sk, int d) {
+  const int DP = bwd_dp_of(d);
+  if (!DP) return LGD_ERR_UNSUPPORTED;
+  // two 16-row tiles per wave once there are enough 128-row workgroups to fill the chip
+  const long wgs = (long)((Sq < Sk ? Sq : Sk) / 128) * H * B;
+  const int env = attn_bwd_env();
   const bool narrow = env == -2;           // default: new variants for d <= 48 only
   const int mode = narrow ? 0 : env;
+  if (DP == 64 && d <= 48) {  // d = 40: the fourth 16-row tile of dQ / dK / dV would be all padding
+    if (wgs < 512) return attn_code(ATTN_FAM_BWD, DP, 10 + BWD_T1);
+    if ((narrow || mode == 2) && wgs >= 1024) return attn_code(ATTN_FAM_BWD, DP, 10 + BWD_T2_DB_NW8);
+    if (narrow || mode >= 1) return attn_code(ATTN_FAM_BWD, DP, 10 + BWD_T2_DB);
+    return attn_code(ATTN_FAM_BWD, DP, 10 + BWD_T2);
+  }
+  if (DP <= 96 && wgs >= 512) {
+    // (8-wave double-buffered kernels exist for DP = 64 only: at DP = 96 the dK/dV kernel spilled 92 registers)
+    if (DP == 64 && mode == 2 && wgs >= 1024) return attn_code(ATTN_FAM_BWD, DP, BWD_T2_DB_NW8);
+    if (mode >= 1) return attn_code(ATTN_FAM_BWD, DP, BWD_T2_DB);
+    return attn_code(ATTN_FAM_BWD, DP, BWD_T2);
+  }
+  return attn_code(ATTN_FAM_BWD, DP, BWD_T1);
+}
+
+template <int DP>
+int launch_bwd(int code, const AttnBwdArgs& a, hipStream_t st) {
+  const int sub = attn_code_sub(code);
   if constexpr (DP == 64) {
-    if (a.d <= 48) {  // d = 40: the fourth 16-row tile of dQ / dK / dV would be all padding
-      if (wgs >= 512) {
-        if ((narrow || mode == 2) && wgs >= 1024) return launch_bwd_nt<DP, 2, 2, 3, 8, true>(a, st);
-        if (narrow || mode >= 1) return launch_bwd_nt<DP, 2, 2, 3, 4, true>(a, st);
-        return launch_bwd_nt<DP, 2, 2, 3>(a, st);
-      }
-      return launch_bwd_nt<DP, 1, 1, 3>(a, st);
+    switch (sub) {
+      case 10 + BWD_T1: return launch_bwd_nt<DP, 1, 1, 3>(a, st);
+      case 10 + BWD_T2: return launch_bwd_nt<DP, 2, 2, 3>(a, st);
+      case 10 + BWD_T2_DB: return launch_bwd_nt<DP, 2, 2, 3, 4, true>(a, st);
+      case 10 + BWD_T2_DB_NW8: return launch_bwd_nt<DP, 2, 2, 3, 8, true>(a, st);
+      case BWD_T2_DB_NW8: return launch_bwd_nt<DP, 2, 2, DP / 16, 8, true>(a, st);
+      default: break;
     }
   }
   if constexpr (DP <= 96) {
-    if (wgs >= 512) {
-      // (8-wave double-buffered kernels exist for DP = 64 only: at DP = 96 the dK/dV kernel spilled 92 registers)
-      if constexpr (DP == 64)
-        if (mode == 2 && wgs >= 1024) return launch_bwd_nt<DP, 2, 2, DP / 16, 8, true>(a, st);
-      if (mode >= 1) return launch_bwd_nt<DP, 2, 2, DP / 16, 4, true>(a, st);
-      return launch_bwd_nt<DP, 2, 2, DP / 16>(a, st);
-    }
+    if (sub == BWD_T2_DB) return launch_bwd_nt<DP, 2, 2, DP / 16, 4, true>(a, st);
+    if (sub == BWD_T2) return launch_bwd_nt<DP, 2, 2, DP / 16>(a, st);
   }
   return launch_bwd_nt<DP, 1, 1, DP / 16>(a, st);
 }
+
+// the MFMA kernel holds all (<= 96) keys of a query in registers and moves q / go / gq as vectors (`aligned`); the
+// one-wave-per-row kernel serves up to 128 keys and element-wise q / go / gq views
+int plan_cross_bwd(int Sk, int d, bool aligned) {
+  if (Sk < 1 || Sk > XB_MAXSK || d > XB_MAXD) return LGD_ERR_ARG;
+  if (Sk <= XM_KEYS && d <= 160 && aligned) return attn_code(ATTN_FAM_XBWD_MFMA, bwd_dp_of(d), 0);
+  return attn_code(ATTN_FAM_XBWD_ROWS, 0, 0);
+}
+
+bool misaligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
 
 }  // namespace
 
@@ -810,11 +843,18 @@ extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, c
                                      int64_t ldgq, int64_t gq_bs, void* gk, int64_t ldgk, int64_t gk_bs,
                                      void* gv, int64_t ldgv, int64_t gv_bs, int B, int H, int Sq, int Sk,
                                      int Sk_grad, int d, float scale, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || Sk_grad < 1 || Sk_grad > Sk || d < 8 || (d % 8)) return LGD_ERR_ARG;
   if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || (ldgo % 8) || (ldgq % 4) || (ldgk % 4) ||
       (ldgv % 4) || !lse || !delta)
     return LGD_ERR_ARG;
+  // rows are read as 16-byte and written as 8-byte vectors: base pointers and per-image strides keep that alignment
+  if ((q_bs % 8) || (k_bs % 8) || (v_bs % 8) || (o_bs % 8) || (go_bs % 8) || (gq_bs % 4) || (gk_bs % 4) || (gv_bs % 4) ||
+      misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(o, 16) || misaligned(go, 16) ||
+      misaligned(gq, 8) || misaligned(gk, 8) || misaligned(gv, 8))
+    return LGD_ERR_ARG;
+  const int code = plan_bwd(B, H, Sq, Sk, d);
+  if (code < 0) return code;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   AttnBwdArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -830,23 +870,32 @@ extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, c
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d <= 32) return launch_bwd<32>(a, st);
-  if (d <= 64) return launch_bwd<64>(a, st);
-  if (d <= 96) return launch_bwd<96>(a, st);
-  if (d <= 128) return launch_bwd<128>(a, st);
-  if (d <= 160) return launch_bwd<160>(a, st);
-  return LGD_ERR_UNSUPPORTED;
+  switch (attn_code_dp(code)) {
+    case 32: return launch_bwd<32>(code, a, st);
+    case 64: return launch_bwd<64>(code, a, st);
+    case 96: return launch_bwd<96>(code, a, st);
+    case 128: return launch_bwd<128>(code, a, st);
+    default: return launch_bwd<160>(code, a, st);
+  }
 }
+
+int lgd_attn_bwd_plan(int B, int H, int Sq, int Sk, int d) { return plan_bwd(B, H, Sq, Sk, d); }
+int lgd_cross_attn_bwd_plan(int Sk, int d, int aligned) { return plan_cross_bwd(Sk, d, aligned != 0); }
 
 extern "C" int lgd_cross_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
                                       int64_t ldk, int64_t k_bs, const void* v, int64_t ldv,
                                       int64_t v_bs, const void* go, int64_t ldgo, int64_t go_bs,
                                       const float* gp, void* gq, int64_t ldgq, int64_t gq_bs, int B,
                                       int H, int Sq, int Sk, int d, float scale, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || Sk > XB_MAXSK || d < 8 || (d % 8) || d > XB_MAXD ||
-      (ldq % 1) || (ldk % 8) || (ldv % 8))
+      (ldk % 8) || (ldv % 8) || (k_bs % 8) || (v_bs % 8) || misaligned(k, 16) || misaligned(v, 16) || !gq)
     return LGD_ERR_ARG;
+  // q / go / gq as 16- and 8-byte vectors (MFMA kernel) or element by element (row kernel)
+  const bool aligned = (ldq % 8) == 0 && (q_bs % 8) == 0 && !misaligned(q, 16) && (ldgq % 4) == 0 && (gq_bs % 4) == 0 &&
+                       !misaligned(gq, 8) && (ldgo % 8) == 0 && (!go || ((go_bs % 8) == 0 && !misaligned(go, 16)));
+  const int code = plan_cross_bwd(Sk, d, aligned);
+  if (code < 0) return code;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   CrossBwdArgs a;
   a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
   a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
@@ -856,12 +905,14 @@ extern "C" int lgd_cross_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
   a.gq = (half_t*)gq; a.ldgq = ldgq; a.gq_bs = gq_bs;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d; a.scale = scale;
   hipStream_t st_ = reinterpret_cast<hipStream_t>(stream);
-  if (Sk <= XM_KEYS && d <= 160 && (ldq % 8) == 0 && (ldgo % 8) == 0 && (ldgq % 4) == 0) {
-    if (d <= 32) return launch_cross_bwd_mfma<32>(a, st_);
-    if (d <= 64) return launch_cross_bwd_mfma<64>(a, st_);
-    if (d <= 96) return launch_cross_bwd_mfma<96>(a, st_);
-    if (d <= 128) return launch_cross_bwd_mfma<128>(a, st_);
-    return launch_cross_bwd_mfma<160>(a, st_);
+  if (attn_code_fam(code) == ATTN_FAM_XBWD_MFMA) {
+    switch (attn_code_dp(code)) {
+      case 32: return launch_cross_bwd_mfma<32>(a, st_);
+      case 64: return launch_cross_bwd_mfma<64>(a, st_);
+      case 96: return launch_cross_bwd_mfma<96>(a, st_);
+      case 128: return launch_cross_bwd_mfma<128>(a, st_);
+      default: return launch_cross_bwd_mfma<160>(a, st_);
+    }
   }
   const int ld = d + 2;
   size_t smem = (size_t)(2 * Sk * ld + 2) * 2 + (size_t)4 * 2 * XB_MAXD * 4 + (size_t)4 * XB_MAXSK * 4;

@@ -654,6 +654,57 @@ def attn_causal_fwd(q, k, v, o, B, H, S, d, scale, *, view=None):
     return o
 
 
+# Variant codes of the attention dispatch (lgd_attn_plan): family * 100000 + DP * 100 + sub, DP = the padded head dim of the
+# kernel instantiation.  Every code the library can answer is named here; ATTN_VARIANTS_ENV_ONLY are the ones only the
+# process-wide A/B switches of the environment (LGD_ATTN_NW, LGD_ATTN_BWD) select.
+ATTN_OP_FWD, ATTN_OP_BWD, ATTN_OP_CROSS_BWD = 0, 1, 2
+
+
+def _attn_variant_names():
+    names = {}
+    shapes = {0: "4 waves x 1 query tile", 1: "4 waves x 2 query tiles", 2: "8 waves x 2 query tiles"}
+    for dp in (32, 64, 96, 128, 160, 192):
+        modes = {0: f"d = {dp}", 1: f"d < {dp}, row of ones"}
+        if dp == 64:
+            modes[2] = "d < 48, row of ones, 3 dv tiles"
+        for m, mname in modes.items():
+            for s, sname in shapes.items():
+                if s == 0 or dp <= 96 or (dp == 160 and m == 0 and s == 2):
+                    names[100000 + dp * 100 + 10 * m + s] = f"attn_self_kernel DP={dp} ({mname}) {sname}"
+        names[400000 + dp * 100] = f"attn_fwd_kernel DP={dp} (two-pass softmax: map capture, causal)"
+    for dk in (48, 96):
+        for s, sname in {0: "4 waves", 1: "8 waves", 2: "8 waves, prefetch 4 ahead", 3: "8 waves, compiler's slot order"}.items():
+            names[200000 + dk * 100 + s] = f"attn_self32_kernel DK={dk} {sname}"
+    names[306400] = "attn_w4_kernel d=40, two waves per SIMD"
+    names[306401] = "attn_w4_kernel d=40, one wave per SIMD (in-wave pipeline)"
+    bshapes = {0: "1 tile per wave", 1: "2 tiles per wave", 2: "2 tiles per wave, double-buffered",
+               3: "2 tiles per wave, double-buffered, 8 waves"}
+    for dp in (32, 64, 96, 128, 160):
+        for s, sname in bshapes.items():
+            if s == 0 or (dp <= 96 and s < 3) or dp == 64:
+                names[500000 + dp * 100 + s] = f"attn_bwd_dq/dkv_kernel DP={dp} {sname}"
+                if dp == 64:
+                    names[500000 + dp * 100 + 10 + s] = f"attn_bwd_dq/dkv_kernel DP=64 (d <= 48, 3 tiles of d) {sname}"
+        names[600000 + dp * 100] = f"cross_attn_bwd_mfma_kernel DP={dp}"
+    names[700000] = "cross_attn_bwd_kernel (one wave per query row)"
+    return names
+
+
+ATTN_VARIANTS = _attn_variant_names()
+ATTN_VARIANTS_ENV_ONLY = frozenset({103202, 103212, 106402, 106412, 106421, 109601, 109611,
+                                    503202, 506402, 506403, 506411, 509602})
+
+
+def attn_plan(op, B, H, Sq, Sk, d, *, sk_grad=None, probs=False, causal=False, pair=0, aligned=True) -> int:
+    """The variant code (a key of ATTN_VARIANTS) the attention call with these arguments runs under the current option
+    state; host only.  Raises for arguments the library refuses.  aligned: read for ATTN_OP_CROSS_BWD only (q / go / gq move as
+    vectors: the MFMA kernel; else the one-wave-per-row kernel)."""
+    code = _lib.load().lgd_attn_plan(int(op), B, H, Sq, Sk, Sk if sk_grad is None else int(sk_grad), d,
+                                     1 if probs else 0, 1 if causal else 0, int(pair), 1 if aligned else 0)
+    _lib.check(min(code, 0), "lgd_attn_plan")
+    return code
+
+
 def quick_gelu(x, out=None):
     if out is None:
         out = torch.empty_like(x)
