@@ -25,6 +25,12 @@
 extern "C" {
 #endif
 
+/* Return codes of every call. */
+#define LGD_OK 0
+#define LGD_ERR_ARG (-1)
+#define LGD_ERR_LAUNCH (-2)
+#define LGD_ERR_UNSUPPORTED (-3)
+
 #define LGD_ABI_VERSION 12
 int lgd_abi_version(void);
 /* Kernel-variant switches of the library (A/B timing and tests; the defaults are what the benchmark runs).  No
@@ -42,9 +48,14 @@ int lgd_abi_version(void);
  * aim at, 64 .. 8192, default 1024.  "cfg_pair": 1 = (default) launch plans of a classifier-free-guidance batch
  * compute the ops in front of the first text / grounding-token read once per pair (LgdGemmDesc.pair, lgd_*_pair_f16),
  * 0 = twice, as before; read by the plan builder when a plan is built (lgd_get_option), the kernels themselves always do
- * what a call asks.  Returns 0, or LGD_ERR_ARG for an unknown name. */
+ * what a call asks.  "attn32_nw": waves per workgroup of the 32x32x16 kernel, 8 (default) or 4; "attn32_var" (tools): its
+ * fragment prefetch, 0 = (default) 2 slots ahead in pinned order, 1 = 4 ahead, 2 = the compiler's order.
+ * Every option has a range and a value outside it is refused, "attn32" (0 .. 2) included.  The initial values of
+ * "attn32", "attn32_nw", "attn_w4" and "attn_w4_pipe" come from LGD_ATTN32, LGD_ATTN32_NW, LGD_ATTN_W4 and LGD_W4_PIPE in
+ * the environment, read once; a value outside the option's range there leaves the default.  The options are atomics: any
+ * thread may set one while others launch.  Returns 0, or LGD_ERR_ARG for an unknown name or a value out of range. */
 int lgd_set_option(const char* name, int value);
-/* Current value of an option the host side reads back ("cfg_pair"), or LGD_ERR_ARG (negative) for any other name. */
+/* Current value (>= 0) of any option lgd_set_option knows, or LGD_ERR_ARG (negative) for any other name. */
 int lgd_get_option(const char* name);
 
 /* ---------------------------------------------------------------------------------------------
@@ -246,8 +257,8 @@ int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void
 
 /* lgd_attn_plan (additive export: LGD_ABI_VERSION stays 12): the variant code of the kernel instantiation a call with these arguments runs under the
  * current option state ("attn32", "attn32_nw", "attn32_var", "attn_w4", "attn_w4_pipe") — answered by the function the
- * launches themselves switch on; host only, nothing is launched.  code = family * 100000 + DP * 100 + sub (DP: the padded
- * head dim of the instantiation); the Python binding names every code (ops.ATTN_VARIANTS).
+ * launches themselves choose their kernel with; host only, nothing is launched.  code = family * 100000 + DP * 100 + sub (DP: the padded
+ * head dim of the instantiation); lgd_attn_variant below names every code (the Python binding: ops.ATTN_VARIANTS).
  *   op = LGD_ATTN_OP_FWD:       lgd_attn_fwd_f16 / lgd_attn_fwd_pair_f16 (pair != 0) / lgd_cross_attn_fwd_f16 (probs != 0:
  *                               a map is captured) / lgd_attn_causal_fwd_f16 (causal != 0).  `aligned` is ignored: every
  *                               view the entry points accept suits every forward kernel.
@@ -264,6 +275,13 @@ int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void
 #define LGD_ATTN_OP_CROSS_BWD 2
 int lgd_attn_plan(int op, int B, int H, int Sq, int Sk, int Sk_grad, int d, int probs, int causal, int pair,
                   int aligned);
+/* lgd_attn_variant (additive export: LGD_ABI_VERSION stays 12): row `index` (0, 1, ..) of the library's table of
+ * attention kernel variants — the table the launches themselves look a code up in, so it holds exactly the codes
+ * lgd_attn_plan can answer.  *code: the variant code; *env_only: 1 when only the A/B switches of the environment
+ * (LGD_ATTN_NW, LGD_ATTN_BWD) select it, which no option state reaches; name (host buffer of name_cap bytes): the
+ * instantiation's name, NUL-terminated and cut to name_cap - 1 characters (the longest has fewer than 100).  Any of the
+ * three may be NULL.  Host only.  Returns 0, or LGD_ERR_ARG for an index past the end. */
+int lgd_attn_variant(int index, int* code, int* env_only, char* name, int name_cap);
 
 /* ---------------------------------------------------------------------------------------------
  * Elementwise pieces.

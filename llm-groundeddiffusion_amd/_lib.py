@@ -89,6 +89,7 @@ SIGNATURES = {
     "lgd_scale_rows_f32": [_P, _P, _P, _P, _I, _I, _L, _I, _P],
     "lgd_attn_causal_fwd_f16": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _P],
     "lgd_attn_plan": [_I] * 11,
+    "lgd_attn_variant": [_I, _P, _P, _P, _I],
     "lgd_quick_gelu_f16": [_P, _P, _L, _P],
     "lgd_act_f16": [_P, _P, _L, _I, _P],
     "lgd_nchw_to_nhwc8_f16": [_P, _P, _I, _I, _I, _P],

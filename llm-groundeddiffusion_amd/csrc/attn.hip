@@ -16,42 +16,14 @@
 //
 // Map capture (attention_processor.py:440-480): two passes over the keys — pass 1 row max / row sum,
 // pass 2 normalised probabilities, which are written to the fp32 map and fed to the PV product.
-#include <atomic>
 #include "common.h"
 #include "../../include/lgd_hip.h"
 #include "attn_w4.h"
 #include "attn_plan.h"
+#include "options.h"
 #include <stdlib.h>
-#include <string.h>
 
 namespace {
-
-int g_attn32_nw = -1;     // waves per workgroup of the 32x32x16 kernel: 8 (256 queries per workgroup) or 4
-int attn32_nw() {
-  if (g_attn32_nw < 0) { const char* e = getenv("LGD_ATTN32_NW"); g_attn32_nw = e ? atoi(e) : 8; }
-  return g_attn32_nw;
-}
-int g_attn32_var = 0;      // tools: 0 = fragment prefetch 2 slots ahead, pinned slot order; 1 = 4 ahead; 2 = compiler's order
-int attn32_var() { return g_attn32_var; }
-int g_attn32 = -1;
-int attn32_mode() {
-  if (g_attn32 < 0) { const char* e = getenv("LGD_ATTN32"); g_attn32 = e ? atoi(e) : 1; }
-  return g_attn32;
-}
-
-// round-4 kernel for d = 40 (attn_w4.hip): 1 = default, 0 = never (A/B timing), 2 = for every size (tests).  Read by
-// every lane thread at launch time: an atomic whose first reader takes LGD_ATTN_W4 once (no torn lazy initialisation)
-std::atomic<int> g_attn_w4{-1};
-int attn_w4_mode() {
-  int v = g_attn_w4.load(std::memory_order_relaxed);
-  if (v < 0) {
-    static const int env = [] { const char* e = getenv("LGD_ATTN_W4"); return e ? atoi(e) : 1; }();
-    int expect = -1;
-    g_attn_w4.compare_exchange_strong(expect, env, std::memory_order_relaxed);
-    v = g_attn_w4.load(std::memory_order_relaxed);
-  }
-  return v;
-}
 
 constexpr int KV_T = 64;         // keys per tile
 constexpr int VT_LD = KV_T + 8;  // halfs per row of the transposed V tile (ds_read_b64: conflict-free)
@@ -1004,8 +976,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_self32_kernel(const AttnArg
 }
 
 // ---------------------------------------------------------------------------------------------
-// Dispatch: plan_fwd CHOOSES the variant code (attn_plan.h) from the arguments and the option state; launch_attn switches
-// on that code.  lgd_attn_plan answers from the same function.
+// Dispatch: plan_fwd CHOOSES the variant code (attn_plan.h) from the arguments and the option state; launch_attn looks the
+// code's row up in FWD_VARIANTS and calls its launcher.  lgd_attn_plan answers from the same function.
 // ---------------------------------------------------------------------------------------------
 int attn_nw_env() {   // LGD_ATTN_NW=4 / 8 overrides the waves-per-workgroup choice of attn_self_kernel (tools)
   static const int nw_env = [] { const char* e = getenv("LGD_ATTN_NW"); return e ? atoi(e) : 0; }();
@@ -1020,7 +992,7 @@ int attn_dp_of(int d) { return d <= 32 ? 32 : d <= 64 ? 64 : d <= 96 ? 96 : d <=
 
 // two_pass: the exact two-pass softmax kernel (map capture, causal).  The thresholds keep the full B in pair mode: a pair
 // launch runs the kernel its full launch would.  (Every view the entry points accept suits every kernel here, the d = 40
-// kernel of attn_w4.hip included: bad_view / bad_out below are the one alignment predicate.)
+// kernel of attn_w4.hip included: AttnView of attn_plan.h is the one alignment predicate.)
 int plan_fwd(int B, int H, int Sq, int Sk, int d, bool two_pass) {
   const int DP = attn_dp_of(d);        // 192: SAM global attention, 64 + 2 x 64 bias columns
   if (!DP) return LGD_ERR_UNSUPPORTED;
@@ -1028,15 +1000,13 @@ int plan_fwd(int B, int H, int Sq, int Sk, int d, bool two_pass) {
   const long blocks256 = (long)((Sq + 255) / 256) * H * B;
   // d = 40 (SD1.x 64x64 level): the one-wave-per-SIMD kernel of attn_w4.hip once a launch has enough 256-query
   // workgroups to occupy the chip (it holds ONE workgroup per CU); smaller problems keep the 4-waves-per-SIMD kernel
-  const int w4 = attn_w4_mode();
+  const int w4 = lgd_option(OPT_ATTN_W4);
   if (w4 && d == 40 && (w4 == 2 || (blocks256 >= 256 && Sk >= 256)))
-    return attn_code(ATTN_FAM_W4, 64, lgd_attn_w4_pipe() ? 1 : 0);
+    return attn_code(ATTN_FAM_W4, 64, lgd_option(OPT_ATTN_W4_PIPE));
   // round-3 kernel (32x32x16 MFMA, in-wave software pipelining) for the narrow heads with a spare slot, once there
-  // are enough 256-query blocks to fill the chip; LGD_ATTN32=0 keeps the 16x16x32 kernel (A/B timing, tools)
+  // are enough 256-query blocks to fill the chip; "attn32" = 0 keeps the 16x16x32 kernel (A/B timing, tools)
   if (DP == 64 || DP == 96) {
-    // g_attn32 (lgd_set_option("attn32", v); initial value from LGD_ATTN32 in the environment): 0 = never (the
-    // 16x16x32 kernel: A/B timing), 1 = default, 2 = for every problem size (tests)
-    const int a32 = attn32_mode();
+    const int a32 = lgd_option(OPT_ATTN32);      // 0 = never, 1 = default, 2 = for every problem size (tests)
     const int dk = ((d + 2 + 15) / 16) * 16;
     // measured (tools/attn_quick.py, B = 16): d = 80 (DK = 96) 97 -> 80 us; d = 40 (DK = 48) 570 -> 630 us — at two
     // waves per SIMD (170 VGPRs) its stalls are not covered the way the 16x16x32 kernel's four waves cover theirs —
@@ -1045,9 +1015,9 @@ int plan_fwd(int B, int H, int Sq, int Sk, int d, bool two_pass) {
     // 8-image calls (256 blocks) run 70.3 -> 42.0 us on this kernel (305 -> 512 TF/s; with the fuser's 1054 keys 73.7 ->
     // 45.9) and the 4-image calls (128 blocks) 34.7 -> 33.2 us with 128-query workgroups
     if (a32 && d % 8 == 0 && (a32 == 2 || (dk == 96 && blocks256 >= 128)) && (dk == 48 || dk == 96)) {
-      const int var = attn32_var();
+      const int var = lgd_option(OPT_ATTN32_VAR);
       // (the <= 128-VGPR, two-workgroups-per-CU build of the dk = 48 kernel spilled 76 registers and is gone)
-      const int sub = (attn32_nw() == 4 || (a32 != 2 && blocks256 < 256)) ? ATTN32_NW4
+      const int sub = (lgd_option(OPT_ATTN32_NW) == 4 || (a32 != 2 && blocks256 < 256)) ? ATTN32_NW4
                       : var == 1 ? ATTN32_NW8_PF4 : var == 2 ? ATTN32_NW8_FREE : ATTN32_NW8;
       return attn_code(ATTN_FAM_SELF32, dk, sub);
     }
@@ -1074,136 +1044,132 @@ int plan_fwd(int B, int H, int Sq, int Sk, int d, bool two_pass) {
   return attn_code(ATTN_FAM_SELF, DP, 10 * mode + SELF_QT1);
 }
 
-// attn_self_kernel<DP, ONES, QT, NDT, NW> for one (DP, mode): the three workgroup shapes
-template <int DP, bool ONES, int NDT>
-void launch_self_shape(int shape, const AttnArgs& a, hipStream_t st) {
-  const int gz = a.pair ? a.B / 2 : a.B;
-  if constexpr (DP <= 96 || (DP == 160 && !ONES)) {
-    if (shape == SELF_QT2_NW8) {
-      hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 2, NDT, 8>), dim3((a.Sq + 255) / 256, a.H, gz), dim3(512), 0, st, a);
-      return;
-    }
-  }
-  if constexpr (DP <= 96) {
-    if (shape == SELF_QT2) {
-      hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 2, NDT>), dim3((a.Sq + 127) / 128, a.H, gz), dim3(256), 0, st, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((attn_self_kernel<DP, ONES, 1, NDT>), dim3((a.Sq + 63) / 64, a.H, gz), dim3(256), 0, st, a);
+// ---------------------------------------------------------------------------------------------
+// The launchers: each takes what its table row is written with and derives the kernel's template arguments from it.
+// ---------------------------------------------------------------------------------------------
+template <int DP, int MODE, int SHAPE>
+int launch_self(const AttnArgs& a, hipStream_t st) {
+  static_assert(MODE != SELF_ONES3 || DP == 64, "the three-tile form is the d = 40 head at DP = 64");
+  constexpr bool ONES = MODE != SELF_PLAIN;
+  constexpr int NDT = MODE == SELF_ONES3 ? 3 : DP / 16;   // d = 40 with the ones row: three 16-row tiles of V^T / O^T, not four
+  constexpr int QT = SHAPE == SELF_QT1 ? 1 : 2, NW = SHAPE == SELF_QT2_NW8 ? 8 : 4;
+  const dim3 grid((a.Sq + 16 * QT * NW - 1) / (16 * QT * NW), a.H, a.pair ? a.B / 2 : a.B);
+  hipLaunchKernelGGL((attn_self_kernel<DP, ONES, QT, NDT, NW>), grid, dim3(64 * NW), 0, st, a);
+  return lgd_check_launch();
 }
 
-template <int DP>
-void launch_fwd_code(int code, const AttnArgs& a, hipStream_t st) {
-  const int fam = attn_code_fam(code), sub = attn_code_sub(code);
-  if (fam == ATTN_FAM_TWOPASS) {
-    dim3 grid((a.Sq + 63) / 64, a.H, a.B);   // (no pair mode: lgd_attn_fwd_pair_f16 never captures a map)
-    hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, dim3(256), 0, st, a);
-    return;
-  }
-  if constexpr (DP == 64 || DP == 96) {
-    if (fam == ATTN_FAM_SELF32) {
-      constexpr int DK = DP == 64 ? 48 : 96, NDT = DP == 64 ? 2 : 3;
-      const int gz = a.pair ? a.B / 2 : a.B;
-      auto go = [&](auto kern, int nw) {
-        dim3 g32((a.Sq + 32 * nw - 1) / (32 * nw), a.H, gz);
-        hipLaunchKernelGGL(kern, g32, dim3(64 * nw), 0, st, a);
-      };
-      switch (sub) {
-        case ATTN32_NW4: go(&attn_self32_kernel<DK, NDT, 4>, 4); return;
-        case ATTN32_NW8_PF4: go(&attn_self32_kernel<DK, NDT, 8, 4, true>, 8); return;
-        case ATTN32_NW8_FREE: go(&attn_self32_kernel<DK, NDT, 8, 2, false>, 8); return;
-        default: go(&attn_self32_kernel<DK, NDT, 8>, 8); return;
-      }
-    }
-  }
-  const int mode = sub / 10, shape = sub % 10;
-  if constexpr (DP == 64) {
-    // d = 40 with the ones row needs three 16-row tiles of V^T / O^T, not DP / 16 = 4
-    if (mode == SELF_ONES3) return launch_self_shape<DP, true, 3>(shape, a, st);
-  }
-  if (mode == SELF_PLAIN) launch_self_shape<DP, false, DP / 16>(shape, a, st);
-  else launch_self_shape<DP, true, DP / 16>(shape, a, st);
+template <int DK, int SUB>
+int launch_self32(const AttnArgs& a, hipStream_t st) {
+  constexpr int NDT = DK == 48 ? 2 : 3, NW = SUB == ATTN32_NW4 ? 4 : 8, PF = SUB == ATTN32_NW8_PF4 ? 4 : 2;
+  constexpr bool PIN = SUB != ATTN32_NW8_FREE;
+  const dim3 grid((a.Sq + 32 * NW - 1) / (32 * NW), a.H, a.pair ? a.B / 2 : a.B);
+  hipLaunchKernelGGL((attn_self32_kernel<DK, NDT, NW, PF, PIN>), grid, dim3(64 * NW), 0, st, a);
+  return lgd_check_launch();
 }
 
-int launch_attn(const AttnArgs& a, hipStream_t st, bool two_pass) {
+template <int PIPE>
+int launch_w4(const AttnArgs& a, hipStream_t st) {
   AttnW4Args w;
   w.q = a.q; w.ldq = a.ldq; w.q_bs = a.q_bs; w.k = a.k; w.ldk = a.ldk; w.k_bs = a.k_bs;
   w.v = a.v; w.ldv = a.ldv; w.v_bs = a.v_bs; w.o = a.o; w.ldo = a.ldo; w.o_bs = a.o_bs; w.lse = a.lse;
   w.B = a.B; w.H = a.H; w.Sq = a.Sq; w.Sk = a.Sk; w.d = a.d; w.scale_log2 = a.scale_log2;
   w.pair = a.pair; w.o_dup = a.o_dup; w.lse_dup = a.lse_dup;
-  const int code = plan_fwd(a.B, a.H, a.Sq, a.Sk, a.d, two_pass);
-  if (code < 0) return code;
-  if (attn_code_fam(code) == ATTN_FAM_W4) return lgd_attn_w4_launch(w, st, attn_code_sub(code));
-  switch (attn_dp_of(a.d)) {
-    case 32: launch_fwd_code<32>(code, a, st); break;
-    case 64: launch_fwd_code<64>(code, a, st); break;
-    case 96: launch_fwd_code<96>(code, a, st); break;
-    case 128: launch_fwd_code<128>(code, a, st); break;
-    case 160: launch_fwd_code<160>(code, a, st); break;
-    default: launch_fwd_code<192>(code, a, st); break;
-  }
+  return lgd_attn_w4_launch(w, st, PIPE);
+}
+
+template <int DP>
+int launch_twopass(const AttnArgs& a, hipStream_t st) {
+  const dim3 grid((a.Sq + 63) / 64, a.H, a.B);   // (no pair mode: lgd_attn_fwd_pair_f16 never captures a map)
+  hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, dim3(256), 0, st, a);
   return lgd_check_launch();
 }
 
-// Every kernel reads Q / K / V rows as 16-byte vectors and writes O as 8-byte vectors: the leading dimensions, the head
-// dim, the BASE pointers and the per-image strides all have to keep that alignment (no kernel here serves less).
-bool bad_view(const void* p, int64_t ld, int64_t bs, int d) {
-  return (ld % 8) != 0 || (d % 8) != 0 || (bs % 8) != 0 || (reinterpret_cast<uintptr_t>(p) & 15) != 0;
+// ---------------------------------------------------------------------------------------------
+// The variant table of the forward (families 1-4).  The row macros turn ONE argument set into the code, the name and the
+// launcher's template arguments.  ENV = 1: only LGD_ATTN_NW selects the code (plan_fwd never answers it by default).
+// ---------------------------------------------------------------------------------------------
+#define SELF_NAME_PLAIN(DP) "d = " #DP
+#define SELF_NAME_ONES(DP) "d < " #DP ", row of ones"
+#define SELF_NAME_ONES3(DP) "d < 48, row of ones, 3 dv tiles"
+#define SELF_NAME_QT1 "4 waves x 1 query tile"
+#define SELF_NAME_QT2 "4 waves x 2 query tiles"
+#define SELF_NAME_QT2_NW8 "8 waves x 2 query tiles"
+#define SELF_ROW(DP, MODE, SHAPE, ENV)                                                                              \
+  {{attn_code(ATTN_FAM_SELF, DP, 10 * SELF_##MODE + SELF_##SHAPE), ENV,                                             \
+    "attn_self_kernel DP=" #DP " (" SELF_NAME_##MODE(DP) ") " SELF_NAME_##SHAPE},                                   \
+   launch_self<DP, SELF_##MODE, SELF_##SHAPE>}
+#define SELF32_NAME_NW4 "4 waves"
+#define SELF32_NAME_NW8 "8 waves"
+#define SELF32_NAME_NW8_PF4 "8 waves, prefetch 4 ahead"
+#define SELF32_NAME_NW8_FREE "8 waves, compiler's slot order"
+#define SELF32_ROW(DK, SUB)                                                                                         \
+  {{attn_code(ATTN_FAM_SELF32, DK, ATTN32_##SUB), 0, "attn_self32_kernel DK=" #DK " " SELF32_NAME_##SUB},           \
+   launch_self32<DK, ATTN32_##SUB>}
+#define W4_ROW(PIPE, WHAT) {{attn_code(ATTN_FAM_W4, 64, PIPE), 0, "attn_w4_kernel d=40, " WHAT}, launch_w4<PIPE>}
+#define TWOPASS_ROW(DP)                                                                                             \
+  {{attn_code(ATTN_FAM_TWOPASS, DP, 0), 0, "attn_fwd_kernel DP=" #DP " (two-pass softmax: map capture, causal)"},  \
+   launch_twopass<DP>}
+
+const AttnVariant<AttnArgs> FWD_VARIANTS[] = {
+    // attn_self_kernel: two query tiles per wave up to DP = 96; eight waves there and for the full d = 160 head
+    SELF_ROW(32, PLAIN, QT1, 0), SELF_ROW(32, PLAIN, QT2, 0), SELF_ROW(32, PLAIN, QT2_NW8, 1),
+    SELF_ROW(32, ONES, QT1, 0), SELF_ROW(32, ONES, QT2, 0), SELF_ROW(32, ONES, QT2_NW8, 1),
+    SELF_ROW(64, PLAIN, QT1, 0), SELF_ROW(64, PLAIN, QT2, 0), SELF_ROW(64, PLAIN, QT2_NW8, 1),
+    SELF_ROW(64, ONES, QT1, 0), SELF_ROW(64, ONES, QT2, 0), SELF_ROW(64, ONES, QT2_NW8, 1),
+    SELF_ROW(64, ONES3, QT1, 0), SELF_ROW(64, ONES3, QT2, 1), SELF_ROW(64, ONES3, QT2_NW8, 0),
+    SELF_ROW(96, PLAIN, QT1, 0), SELF_ROW(96, PLAIN, QT2, 1), SELF_ROW(96, PLAIN, QT2_NW8, 0),
+    SELF_ROW(96, ONES, QT1, 0), SELF_ROW(96, ONES, QT2, 1), SELF_ROW(96, ONES, QT2_NW8, 0),
+    SELF_ROW(128, PLAIN, QT1, 0), SELF_ROW(128, ONES, QT1, 0),
+    SELF_ROW(160, PLAIN, QT1, 0), SELF_ROW(160, PLAIN, QT2_NW8, 0), SELF_ROW(160, ONES, QT1, 0),
+    SELF_ROW(192, PLAIN, QT1, 0), SELF_ROW(192, ONES, QT1, 0),
+    SELF32_ROW(48, NW4), SELF32_ROW(48, NW8), SELF32_ROW(48, NW8_PF4), SELF32_ROW(48, NW8_FREE),
+    SELF32_ROW(96, NW4), SELF32_ROW(96, NW8), SELF32_ROW(96, NW8_PF4), SELF32_ROW(96, NW8_FREE),
+    W4_ROW(0, "two waves per SIMD"), W4_ROW(1, "one wave per SIMD (in-wave pipeline)"),
+    TWOPASS_ROW(32), TWOPASS_ROW(64), TWOPASS_ROW(96), TWOPASS_ROW(128), TWOPASS_ROW(160), TWOPASS_ROW(192),
+};
+constexpr int N_FWD_VARIANTS = sizeof(FWD_VARIANTS) / sizeof(FWD_VARIANTS[0]);
+static_assert(N_FWD_VARIANTS == 28 + 8 + 2 + 6, "a kernel instantiation was added or dropped");
+
+int launch_attn(const AttnArgs& a, hipStream_t st, bool two_pass) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  const int code = plan_fwd(a.B, a.H, a.Sq, a.Sk, a.d, two_pass);
+  if (code < 0) return code;
+  return attn_launch_code(FWD_VARIANTS, code, a, st);
 }
-bool bad_out(const void* p, int64_t ld, int64_t bs) {
-  return (ld % 4) != 0 || (bs % 4) != 0 || (reinterpret_cast<uintptr_t>(p) & 7) != 0;
+
+// what every forward entry point refuses, in this order: sizes (LGD_ERR_ARG), a head dim no kernel serves
+// (LGD_ERR_UNSUPPORTED), rows that do not move as whole vectors (LGD_ERR_ARG)
+int check_fwd(const AttnView& q, const AttnView& k, const AttnView& v, const AttnView& o, int B, int H, int Sq, int Sk, int d) {
+  if (int e = check_problem(B, H, Sq, Sk, d)) return e;
+  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
+  return attn_vectors_ok(d, {q, k, v}, {o}) ? LGD_OK : LGD_ERR_ARG;
+}
+
+// plain attention over the views: no lse, no map capture, not causal, no pair mode
+AttnArgs attn_args(const AttnView& q, const AttnView& k, const AttnView& v, const AttnView& o, int B, int H, int Sq, int Sk,
+                   int d, float scale) {
+  AttnArgs a;
+  a.q = (const half_t*)q.p; a.ldq = q.ld; a.q_bs = q.bs;
+  a.k = (const half_t*)k.p; a.ldk = k.ld; a.k_bs = k.bs;
+  a.v = (const half_t*)v.p; a.ldv = v.ld; a.v_bs = v.bs;
+  a.o = (half_t*)o.p; a.ldo = o.ld; a.o_bs = o.bs;
+  a.lse = nullptr; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 0;
+  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  return a;
 }
 
 }  // namespace
-
-void lgd_gn_set_fused_hw(int hw);                          // norm.hip
-void lgd_gn_set_slab(int on);                              // norm.hip
-void lgd_ln_set_stream(int on);                            // norm.hip
-void lgd_gn_set_apply_wgs(int n);                          // norm.hip
-
-// "cfg_pair": whether launch plans built for a CFG batch use the pair modes (LgdGemmDesc.pair, lgd_*_pair_f16) for the
-// ops in front of the first one that reads text or grounding tokens.  The library only keeps the value: the kernels
-// always do what a descriptor asks; the plan builder reads it (lgd_get_option) when it builds a plan.
-static std::atomic<int> g_cfg_pair{1};
-
-extern "C" int lgd_get_option(const char* name) {
-  if (name && !strcmp(name, "cfg_pair")) return g_cfg_pair.load(std::memory_order_relaxed);
-  return LGD_ERR_ARG;
-}
-
-extern "C" int lgd_set_option(const char* name, int value) {
-  if (!name) return LGD_ERR_ARG;
-  if (!strcmp(name, "cfg_pair") && (value == 0 || value == 1)) { g_cfg_pair.store(value, std::memory_order_relaxed); return LGD_OK; }
-  if (!strcmp(name, "gn_fused") && value >= 0 && value <= 4096) { lgd_gn_set_fused_hw(value); return LGD_OK; }
-  if (!strcmp(name, "gn_slab") && (value == 0 || value == 1)) { lgd_gn_set_slab(value); return LGD_OK; }
-  if (!strcmp(name, "ln_stream") && (value == 0 || value == 1)) { lgd_ln_set_stream(value); return LGD_OK; }
-  if (!strcmp(name, "gn_apply_wgs") && value >= 64 && value <= 8192) { lgd_gn_set_apply_wgs(value); return LGD_OK; }
-  if (!strcmp(name, "attn32")) { g_attn32 = value; return LGD_OK; }
-  if (!strcmp(name, "attn_w4") && value >= 0 && value <= 2) { g_attn_w4.store(value, std::memory_order_relaxed); return LGD_OK; }
-  if (!strcmp(name, "attn_w4_pipe") && (value == 0 || value == 1)) { lgd_attn_w4_set_pipe(value); return LGD_OK; }
-  if (!strcmp(name, "attn32_nw") && (value == 4 || value == 8)) { g_attn32_nw = value; return LGD_OK; }
-  if (!strcmp(name, "attn32_var") && value >= 0 && value <= 2) { g_attn32_var = value; return LGD_OK; }
-  return LGD_ERR_ARG;
-}
 
 extern "C" int lgd_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
                                 int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
                                 void* o, int64_t ldo, int64_t o_bs, float* lse, int B, int H, int Sq,
                                 int Sk, int d, float scale, void* stream) {
-  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
-  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
-  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  AttnArgs a;
-  a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
-  a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
-  a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
-  a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
-  a.lse = lse; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 0;
-  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
-  a.scale_log2 = scale * 1.4426950408889634f;
+  const AttnView Q{q, ldq, q_bs}, K{k, ldk, k_bs}, V{v, ldv, v_bs}, O{o, ldo, o_bs};
+  if (int e = check_fwd(Q, K, V, O, B, H, Sq, Sk, d)) return e;
+  AttnArgs a = attn_args(Q, K, V, O, B, H, Sq, Sk, d, scale);
+  a.lse = lse;
   return launch_attn(a, reinterpret_cast<hipStream_t>(stream), false);
 }
 
@@ -1214,22 +1180,14 @@ extern "C" int lgd_attn_fwd_pair_f16(const void* q, int64_t ldq, int64_t q_bs, c
                                      int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
                                      void* o, int64_t ldo, int64_t o_bs, float* lse, int B, int H, int Sq,
                                      int Sk, int d, float scale, int pair, void* stream) {
-  if (B < 2 || (B % 2) || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
-  if (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) return LGD_ERR_ARG;
-  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
-  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  AttnArgs a;
-  a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
-  a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
-  a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
-  a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
-  a.lse = lse; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 0;
+  const AttnView Q{q, ldq, q_bs}, K{k, ldk, k_bs}, V{v, ldv, v_bs}, O{o, ldo, o_bs};
+  if (B < 2 || (B % 2) || (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP)) return LGD_ERR_ARG;
+  if (int e = check_fwd(Q, K, V, O, B, H, Sq, Sk, d)) return e;
+  AttnArgs a = attn_args(Q, K, V, O, B, H, Sq, Sk, d, scale);
+  a.lse = lse;
   a.pair = pair;
   a.o_dup = pair == LGD_PAIR_DUP ? (long)(B / 2) * o_bs : 0;
   a.lse_dup = pair == LGD_PAIR_DUP ? (long)(B / 2) * H * Sq : 0;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
-  a.scale_log2 = scale * 1.4426950408889634f;
   return launch_attn(a, reinterpret_cast<hipStream_t>(stream), false);
 }
 
@@ -1238,50 +1196,32 @@ extern "C" int lgd_cross_attn_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
                                       int64_t v_bs, void* o, int64_t ldo, int64_t o_bs, float* probs,
                                       int tok, int cond_only, int B, int H, int Sq, int Sk, int d,
                                       float scale, void* stream) {
-  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8) return LGD_ERR_ARG;
-  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
-  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
+  const AttnView Q{q, ldq, q_bs}, K{k, ldk, k_bs}, V{v, ldv, v_bs}, O{o, ldo, o_bs};
+  if (int e = check_fwd(Q, K, V, O, B, H, Sq, Sk, d)) return e;
   if (cond_only && (B % 2)) return LGD_ERR_ARG;  // attention_processor.py:475
   if (tok >= Sk) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  AttnArgs a;
-  a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
-  a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
-  a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
-  a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
-  a.lse = nullptr; a.probs = probs; a.tok = tok; a.cond_only = cond_only; a.causal = 0;
-  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return launch_attn(a, st, probs != nullptr);
+  AttnArgs a = attn_args(Q, K, V, O, B, H, Sq, Sk, d, scale);
+  a.probs = probs; a.tok = tok; a.cond_only = cond_only;
+  return launch_attn(a, reinterpret_cast<hipStream_t>(stream), probs != nullptr);
 }
 
 extern "C" int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk,
                                        int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs, void* o,
                                        int64_t ldo, int64_t o_bs, int B, int H, int S, int d, float scale,
                                        void* stream) {
-  if (B < 1 || H < 1 || S < 1 || d < 8) return LGD_ERR_ARG;
-  if (!attn_dp_of(d)) return LGD_ERR_UNSUPPORTED;
-  if (bad_view(q, ldq, q_bs, d) || bad_view(k, ldk, k_bs, d) || bad_view(v, ldv, v_bs, d) || bad_out(o, ldo, o_bs)) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  AttnArgs a;
-  a.q = (const half_t*)q; a.ldq = ldq; a.q_bs = q_bs;
-  a.k = (const half_t*)k; a.ldk = ldk; a.k_bs = k_bs;
-  a.v = (const half_t*)v; a.ldv = ldv; a.v_bs = v_bs;
-  a.o = (half_t*)o; a.ldo = ldo; a.o_bs = o_bs;
-  a.lse = nullptr; a.probs = nullptr; a.tok = -1; a.cond_only = 0; a.causal = 1;
-  a.pair = 0; a.o_dup = 0; a.lse_dup = 0;
-  a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.d = d;
-  a.scale_log2 = scale * 1.4426950408889634f;
+  const AttnView Q{q, ldq, q_bs}, K{k, ldk, k_bs}, V{v, ldv, v_bs}, O{o, ldo, o_bs};
+  if (int e = check_fwd(Q, K, V, O, B, H, S, S, d)) return e;
+  AttnArgs a = attn_args(Q, K, V, O, B, H, S, S, d, scale);
+  a.causal = 1;
   return launch_attn(a, reinterpret_cast<hipStream_t>(stream), true);   // exact two-pass softmax kernel
 }
 
-// The variant code (attn_plan.h; named in ops.ATTN_VARIANTS) the call with these arguments would run under the current
-// option state: answered by the functions the launches switch on.  Host only, touches no device.
+// The variant code (attn_plan.h; named by lgd_attn_variant) the call with these arguments would run under the current
+// option state: answered by the functions the launches look their row up with.  Host only, touches no device.
 extern "C" int lgd_attn_plan(int op, int B, int H, int Sq, int Sk, int Sk_grad, int d, int probs, int causal, int pair,
                              int aligned) {
-  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || d < 8 || (d % 8)) return LGD_ERR_ARG;
+  if (int e = check_problem(B, H, Sq, Sk, d)) return e;
+  if (!attn_vectors_ok(d, {}, {})) return LGD_ERR_ARG;      // no views here: the head dim's share of the rule
   if (pair && (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP)) return LGD_ERR_ARG;
   switch (op) {
     case LGD_ATTN_OP_FWD:
@@ -1297,4 +1237,17 @@ extern "C" int lgd_attn_plan(int op, int B, int H, int Sq, int Sk, int Sk_grad, 
     default:
       return LGD_ERR_ARG;
   }
+}
+
+// Row `index` of the variant table (families 1-4 here, 5-7 in attn_bwd.hip), in table order: its code, whether only the
+// A/B switches of the environment select it, and its name (NUL-terminated, cut to name_cap - 1 characters).  Host only.
+extern "C" int lgd_attn_variant(int index, int* code, int* env_only, char* name, int name_cap) {
+  const AttnVariantInfo* r = index < 0                  ? nullptr
+                             : index < N_FWD_VARIANTS ? &FWD_VARIANTS[index].info
+                                                        : lgd_attn_bwd_variant_info(index - N_FWD_VARIANTS);
+  if (!r) return LGD_ERR_ARG;
+  if (code) *code = r->code;
+  if (env_only) *env_only = r->env_only;
+  if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", r->name);
+  return LGD_OK;
 }

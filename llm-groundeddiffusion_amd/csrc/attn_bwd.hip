@@ -729,23 +729,42 @@ int launch_cross_bwd_mfma(const CrossBwdArgs& a, hipStream_t st) {
   return lgd_check_launch();
 }
 
-template <int DP, int NQ, int NK, int NDT, int NW = 4, bool DB = false>
-int launch_bwd_nt(const AttnBwdArgs& a, hipStream_t st) {
+int launch_cross_bwd_rows(const CrossBwdArgs& a, hipStream_t st) {
+  const int ld = a.d + 2;
+  size_t smem = (size_t)(2 * a.Sk * ld + 2) * 2 + (size_t)4 * 2 * XB_MAXD * 4 + (size_t)4 * XB_MAXSK * 4;
+  smem = (smem + 15) & ~(size_t)15;
+  static const bool attr_set = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn_bwd_kernel),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return true;
+  }();
+  (void)attr_set;
+  hipLaunchKernelGGL(cross_attn_bwd_kernel, dim3((a.Sq + 4 * XB_ROWS - 1) / (4 * XB_ROWS), a.H, a.B), dim3(256), smem, st, a);
+  return lgd_check_launch();
+}
+
+// dQ and dK / dV kernels of one table row: THREE = three 16-row tiles of d (d <= 48 at DP = 64: the fourth would be all
+// padding), SHAPE = BWD_* (tiles per wave, double buffering, waves per workgroup)
+template <int DP, int THREE, int SHAPE>
+int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {
+  static_assert(!THREE || DP == 64, "the three-tile form is the d = 40 head at DP = 64");
+  constexpr int NT = SHAPE == BWD_T1 ? 1 : 2, NDT = THREE ? 3 : DP / 16, NW = SHAPE == BWD_T2_DB_NW8 ? 8 : 4;
+  constexpr bool DB = SHAPE == BWD_T2_DB || SHAPE == BWD_T2_DB_NW8;
   constexpr int K_LD = DP + 16;
   constexpr int NST = DB ? 2 : 1;
   const size_t smem_dq = (size_t)NST * (2 * T64 * K_LD + DP * TR_LD) * 2;
   const size_t smem_dkv = (size_t)NST * ((2 * T64 * K_LD + 2 * DP * TR_LD) * 2 + 2 * T64 * 4);
   static const bool attr_set = [smem_dq, smem_dkv] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<DP, NK, NDT, NW, DB>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<DP, NT, NDT, NW, DB>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_dkv);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<DP, NQ, NDT, NW, DB>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<DP, NT, NDT, NW, DB>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_dq);
     return true;
   }();
   (void)attr_set;
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<DP, NQ, NDT, NW, DB>), dim3((a.Sq + 16 * NW * NQ - 1) / (16 * NW * NQ), a.H, a.B),
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<DP, NT, NDT, NW, DB>), dim3((a.Sq + 16 * NW * NT - 1) / (16 * NW * NT), a.H, a.B),
                      dim3(64 * NW), smem_dq, st, a);
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DP, NK, NDT, NW, DB>), dim3((a.sk_grad + 16 * NW * NK - 1) / (16 * NW * NK), a.H, a.B),
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DP, NT, NDT, NW, DB>), dim3((a.sk_grad + 16 * NW * NT - 1) / (16 * NW * NT), a.H, a.B),
                      dim3(64 * NW), smem_dkv, st, a);
   return lgd_check_launch();
 }
@@ -761,7 +780,7 @@ int attn_bwd_env() {
 
 int bwd_dp_of(int d) { return d <= 32 ? 32 : d <= 64 ? 64 : d <= 96 ? 96 : d <= 128 ? 128 : d <= 160 ? 160 : 0; }
 
-// the variant code (attn_plan.h) of a self-attention backward: launch_bwd switches on it, lgd_attn_plan reports it
+// the variant code (attn_plan.h) of a self-attention backward: the launch looks its row up, lgd_attn_plan reports it
 int plan_bwd(int B, int H, int Sq, int Sk, int d) {
   const int DP = bwd_dp_of(d);
   if (!DP) return LGD_ERR_UNSUPPORTED;
@@ -785,26 +804,6 @@ int plan_bwd(int B, int H, int Sq, int Sk, int d) {
   return attn_code(ATTN_FAM_BWD, DP, BWD_T1);
 }
 
-template <int DP>
-int launch_bwd(int code, const AttnBwdArgs& a, hipStream_t st) {
-  const int sub = attn_code_sub(code);
-  if constexpr (DP == 64) {
-    switch (sub) {
-      case 10 + BWD_T1: return launch_bwd_nt<DP, 1, 1, 3>(a, st);
-      case 10 + BWD_T2: return launch_bwd_nt<DP, 2, 2, 3>(a, st);
-      case 10 + BWD_T2_DB: return launch_bwd_nt<DP, 2, 2, 3, 4, true>(a, st);
-      case 10 + BWD_T2_DB_NW8: return launch_bwd_nt<DP, 2, 2, 3, 8, true>(a, st);
-      case BWD_T2_DB_NW8: return launch_bwd_nt<DP, 2, 2, DP / 16, 8, true>(a, st);
-      default: break;
-    }
-  }
-  if constexpr (DP <= 96) {
-    if (sub == BWD_T2_DB) return launch_bwd_nt<DP, 2, 2, DP / 16, 4, true>(a, st);
-    if (sub == BWD_T2) return launch_bwd_nt<DP, 2, 2, DP / 16>(a, st);
-  }
-  return launch_bwd_nt<DP, 1, 1, DP / 16>(a, st);
-}
-
 // the MFMA kernel holds all (<= 96) keys of a query in registers and moves q / go / gq as vectors (`aligned`); the
 // one-wave-per-row kernel serves up to 128 keys and element-wise q / go / gq views
 int plan_cross_bwd(int Sk, int d, bool aligned) {
@@ -813,27 +812,47 @@ int plan_cross_bwd(int Sk, int d, bool aligned) {
   return attn_code(ATTN_FAM_XBWD_ROWS, 0, 0);
 }
 
-bool misaligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
+// ---------------------------------------------------------------------------------------------
+// The variant tables of the backward (family 5) and the cross backward (families 6 and 7): see attn_plan.h.  ENV = 1:
+// only LGD_ATTN_BWD selects the code (plan_bwd never answers it by default).
+// ---------------------------------------------------------------------------------------------
+#define BWD_NAME_T1 "1 tile per wave"
+#define BWD_NAME_T2 "2 tiles per wave"
+#define BWD_NAME_T2_DB "2 tiles per wave, double-buffered"
+#define BWD_NAME_T2_DB_NW8 "2 tiles per wave, double-buffered, 8 waves"
+#define BWD_NAME_THREE_0 " "
+#define BWD_NAME_THREE_1 " (d <= 48, 3 tiles of d) "
+#define BWD_ROW(DP, THREE, SHAPE, ENV)                                                                              \
+  {{attn_code(ATTN_FAM_BWD, DP, 10 * THREE + BWD_##SHAPE), ENV,                                                     \
+    "attn_bwd_dq/dkv_kernel DP=" #DP BWD_NAME_THREE_##THREE BWD_NAME_##SHAPE},                                      \
+   launch_bwd<DP, THREE, BWD_##SHAPE>}
+#define XBWD_MFMA_ROW(DP) {{attn_code(ATTN_FAM_XBWD_MFMA, DP, 0), 0, "cross_attn_bwd_mfma_kernel DP=" #DP}, launch_cross_bwd_mfma<DP>}
+
+const AttnVariant<AttnBwdArgs> BWD_VARIANTS[] = {
+    // two tiles per wave (and two LDS stages) up to DP = 96; eight waves at DP = 64 only
+    BWD_ROW(32, 0, T1, 0), BWD_ROW(32, 0, T2, 0), BWD_ROW(32, 0, T2_DB, 1),
+    BWD_ROW(64, 0, T1, 0), BWD_ROW(64, 0, T2, 0), BWD_ROW(64, 0, T2_DB, 1), BWD_ROW(64, 0, T2_DB_NW8, 1),
+    BWD_ROW(64, 1, T1, 0), BWD_ROW(64, 1, T2, 1), BWD_ROW(64, 1, T2_DB, 0), BWD_ROW(64, 1, T2_DB_NW8, 0),
+    BWD_ROW(96, 0, T1, 0), BWD_ROW(96, 0, T2, 0), BWD_ROW(96, 0, T2_DB, 1),
+    BWD_ROW(128, 0, T1, 0), BWD_ROW(160, 0, T1, 0),
+};
+const AttnVariant<CrossBwdArgs> XBWD_VARIANTS[] = {
+    XBWD_MFMA_ROW(32), XBWD_MFMA_ROW(64), XBWD_MFMA_ROW(96), XBWD_MFMA_ROW(128), XBWD_MFMA_ROW(160),
+    {{attn_code(ATTN_FAM_XBWD_ROWS, 0, 0), 0, "cross_attn_bwd_kernel (one wave per query row)"}, launch_cross_bwd_rows},
+};
+constexpr int N_BWD_VARIANTS = sizeof(BWD_VARIANTS) / sizeof(BWD_VARIANTS[0]);
+constexpr int N_XBWD_VARIANTS = sizeof(XBWD_VARIANTS) / sizeof(XBWD_VARIANTS[0]);
+static_assert(N_BWD_VARIANTS == 16 && N_XBWD_VARIANTS == 5 + 1, "a kernel instantiation was added or dropped");
 
 }  // namespace
 
-extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
-                                     int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
-                                     const void* o, int64_t ldo, int64_t o_bs, const void* go,
-                                     int64_t ldgo, int64_t go_bs, const float* lse, float* delta, void* gq,
-                                     int64_t ldgq, int64_t gq_bs, void* gk, int64_t ldgk, int64_t gk_bs,
-                                     void* gv, int64_t ldgv, int64_t gv_bs, int B, int H, int Sq, int Sk,
-                                     int Sk_grad, int d, float scale, void* stream);
-
-extern "C" int lgd_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
-                                int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
-                                const void* o, int64_t ldo, int64_t o_bs, const void* go,
-                                int64_t ldgo, int64_t go_bs, const float* lse, float* delta, void* gq,
-                                int64_t ldgq, int64_t gq_bs, void* gk, int64_t ldgk, int64_t gk_bs,
-                                void* gv, int64_t ldgv, int64_t gv_bs, int B, int H, int Sq, int Sk,
-                                int d, float scale, void* stream) {
-  return lgd_attn_bwd_keys_f16(q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs, o, ldo, o_bs, go, ldgo, go_bs, lse, delta, gq, ldgq,
-                               gq_bs, gk, ldgk, gk_bs, gv, ldgv, gv_bs, B, H, Sq, Sk, Sk, d, scale, stream);
+int lgd_attn_bwd_plan(int B, int H, int Sq, int Sk, int d) { return plan_bwd(B, H, Sq, Sk, d); }
+int lgd_cross_attn_bwd_plan(int Sk, int d, int aligned) { return plan_cross_bwd(Sk, d, aligned != 0); }
+const AttnVariantInfo* lgd_attn_bwd_variant_info(int index) {
+  if (index < 0) return nullptr;
+  if (index < N_BWD_VARIANTS) return &BWD_VARIANTS[index].info;
+  index -= N_BWD_VARIANTS;
+  return index < N_XBWD_VARIANTS ? &XBWD_VARIANTS[index].info : nullptr;
 }
 
 extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
@@ -843,14 +862,10 @@ extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, c
                                      int64_t ldgq, int64_t gq_bs, void* gk, int64_t ldgk, int64_t gk_bs,
                                      void* gv, int64_t ldgv, int64_t gv_bs, int B, int H, int Sq, int Sk,
                                      int Sk_grad, int d, float scale, void* stream) {
-  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || Sk_grad < 1 || Sk_grad > Sk || d < 8 || (d % 8)) return LGD_ERR_ARG;
-  if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || (ldgo % 8) || (ldgq % 4) || (ldgk % 4) ||
-      (ldgv % 4) || !lse || !delta)
-    return LGD_ERR_ARG;
-  // rows are read as 16-byte and written as 8-byte vectors: base pointers and per-image strides keep that alignment
-  if ((q_bs % 8) || (k_bs % 8) || (v_bs % 8) || (o_bs % 8) || (go_bs % 8) || (gq_bs % 4) || (gk_bs % 4) || (gv_bs % 4) ||
-      misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(o, 16) || misaligned(go, 16) ||
-      misaligned(gq, 8) || misaligned(gk, 8) || misaligned(gv, 8))
+  if (int e = check_problem(B, H, Sq, Sk, d)) return e;
+  if (Sk_grad < 1 || Sk_grad > Sk || !lse || !delta) return LGD_ERR_ARG;
+  if (!attn_vectors_ok(d, {{q, ldq, q_bs}, {k, ldk, k_bs}, {v, ldv, v_bs}, {o, ldo, o_bs}, {go, ldgo, go_bs}},
+                       {{gq, ldgq, gq_bs}, {gk, ldgk, gk_bs}, {gv, ldgv, gv_bs}}))
     return LGD_ERR_ARG;
   const int code = plan_bwd(B, H, Sq, Sk, d);
   if (code < 0) return code;
@@ -869,30 +884,33 @@ extern "C" int lgd_attn_bwd_keys_f16(const void* q, int64_t ldq, int64_t q_bs, c
   a.sk_grad = Sk_grad;
   a.scale = scale;
   a.scale_log2 = scale * 1.4426950408889634f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  switch (attn_code_dp(code)) {
-    case 32: return launch_bwd<32>(code, a, st);
-    case 64: return launch_bwd<64>(code, a, st);
-    case 96: return launch_bwd<96>(code, a, st);
-    case 128: return launch_bwd<128>(code, a, st);
-    default: return launch_bwd<160>(code, a, st);
-  }
+  return attn_launch_code(BWD_VARIANTS, code, a, reinterpret_cast<hipStream_t>(stream));
 }
 
-int lgd_attn_bwd_plan(int B, int H, int Sq, int Sk, int d) { return plan_bwd(B, H, Sq, Sk, d); }
-int lgd_cross_attn_bwd_plan(int Sk, int d, int aligned) { return plan_cross_bwd(Sk, d, aligned != 0); }
+extern "C" int lgd_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
+                                int64_t ldk, int64_t k_bs, const void* v, int64_t ldv, int64_t v_bs,
+                                const void* o, int64_t ldo, int64_t o_bs, const void* go,
+                                int64_t ldgo, int64_t go_bs, const float* lse, float* delta, void* gq,
+                                int64_t ldgq, int64_t gq_bs, void* gk, int64_t ldgk, int64_t gk_bs,
+                                void* gv, int64_t ldgv, int64_t gv_bs, int B, int H, int Sq, int Sk,
+                                int d, float scale, void* stream) {
+  return lgd_attn_bwd_keys_f16(q, ldq, q_bs, k, ldk, k_bs, v, ldv, v_bs, o, ldo, o_bs, go, ldgo, go_bs, lse, delta, gq, ldgq,
+                               gq_bs, gk, ldgk, gk_bs, gv, ldgv, gv_bs, B, H, Sq, Sk, Sk, d, scale, stream);
+}
 
 extern "C" int lgd_cross_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void* k,
                                       int64_t ldk, int64_t k_bs, const void* v, int64_t ldv,
                                       int64_t v_bs, const void* go, int64_t ldgo, int64_t go_bs,
                                       const float* gp, void* gq, int64_t ldgq, int64_t gq_bs, int B,
                                       int H, int Sq, int Sk, int d, float scale, void* stream) {
-  if (B < 1 || H < 1 || Sq < 1 || Sk < 1 || Sk > XB_MAXSK || d < 8 || (d % 8) || d > XB_MAXD ||
-      (ldk % 8) || (ldv % 8) || (k_bs % 8) || (v_bs % 8) || misaligned(k, 16) || misaligned(v, 16) || !gq)
+  // (a head dim above XB_MAXD is an argument error here, not "unsupported": plan_cross_bwd says the same)
+  if (check_problem(B, H, Sq, Sk, d) || Sk > XB_MAXSK || d > XB_MAXD || !gq ||
+      !attn_vectors_ok(d, {{k, ldk, k_bs}, {v, ldv, v_bs}}, {}))
     return LGD_ERR_ARG;
-  // q / go / gq as 16- and 8-byte vectors (MFMA kernel) or element by element (row kernel)
-  const bool aligned = (ldq % 8) == 0 && (q_bs % 8) == 0 && !misaligned(q, 16) && (ldgq % 4) == 0 && (gq_bs % 4) == 0 &&
-                       !misaligned(gq, 8) && (ldgo % 8) == 0 && (!go || ((go_bs % 8) == 0 && !misaligned(go, 16)));
+  // q / go / gq as 16- and 8-byte vectors (MFMA kernel) or element by element (row kernel): not an error.  ldgo counts
+  // even without go.
+  const AttnView Q{q, ldq, q_bs}, GO{go, ldgo, go_bs}, GQ{gq, ldgq, gq_bs};
+  const bool aligned = Q.reads16() && GQ.writes8() && (ldgo % 8) == 0 && (!go || GO.reads16());
   const int code = plan_cross_bwd(Sk, d, aligned);
   if (code < 0) return code;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
@@ -904,26 +922,5 @@ extern "C" int lgd_cross_attn_bwd_f16(const void* q, int64_t ldq, int64_t q_bs, 
   a.gp = gp;
   a.gq = (half_t*)gq; a.ldgq = ldgq; a.gq_bs = gq_bs;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = d; a.scale = scale;
-  hipStream_t st_ = reinterpret_cast<hipStream_t>(stream);
-  if (attn_code_fam(code) == ATTN_FAM_XBWD_MFMA) {
-    switch (attn_code_dp(code)) {
-      case 32: return launch_cross_bwd_mfma<32>(a, st_);
-      case 64: return launch_cross_bwd_mfma<64>(a, st_);
-      case 96: return launch_cross_bwd_mfma<96>(a, st_);
-      case 128: return launch_cross_bwd_mfma<128>(a, st_);
-      default: return launch_cross_bwd_mfma<160>(a, st_);
-    }
-  }
-  const int ld = d + 2;
-  size_t smem = (size_t)(2 * Sk * ld + 2) * 2 + (size_t)4 * 2 * XB_MAXD * 4 + (size_t)4 * XB_MAXSK * 4;
-  smem = (smem + 15) & ~(size_t)15;
-  static const bool attr_set = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn_bwd_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();
-  (void)attr_set;
-  hipLaunchKernelGGL(cross_attn_bwd_kernel, dim3((Sq + 4 * XB_ROWS - 1) / (4 * XB_ROWS), H, B), dim3(256), smem,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  return lgd_check_launch();
+  return attn_launch_code(XBWD_VARIANTS, code, a, reinterpret_cast<hipStream_t>(stream));
 }

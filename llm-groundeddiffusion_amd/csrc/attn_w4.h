@@ -15,6 +15,5 @@ struct AttnW4Args {
   long o_dup, lse_dup;      // != 0: O / lse stores repeated that many elements further on (image b + B / 2)
 };
 
-int lgd_attn_w4_pipe();                      // the current "attn_w4_pipe" option
-int lgd_attn_w4_launch(const AttnW4Args& a, hipStream_t st, int pipe);   // pipe: the variant the plan chose
-void lgd_attn_w4_set_pipe(int v);          // 1: one wave per SIMD, in-wave software pipeline; 0: two waves per SIMD
+// pipe: the variant the plan chose (1: one wave per SIMD, in-wave software pipeline; 0: two waves per SIMD)
+int lgd_attn_w4_launch(const AttnW4Args& a, hipStream_t st, int pipe);

@@ -26,7 +26,6 @@
 #include "attn_w4.h"
 #include <stdint.h>
 #include <stdlib.h>
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -577,22 +576,8 @@ __global__ __launch_bounds__(256, PIPE ? 1 : 2) void attn_w4_kernel(const AttnW4
 
 }  // namespace
 
-// lane threads launch concurrently (lanes.py): the option is an atomic whose first reader takes LGD_W4_PIPE once
-static std::atomic<int> g_w4_pipe{-1};
-void lgd_attn_w4_set_pipe(int v) { g_w4_pipe.store(v ? 1 : 0, std::memory_order_relaxed); }
-int lgd_attn_w4_pipe() {
-  int v = g_w4_pipe.load(std::memory_order_relaxed);
-  if (v < 0) {
-    static const int env = [] { const char* e = getenv("LGD_W4_PIPE"); return e ? (atoi(e) ? 1 : 0) : 1; }();
-    int expect = -1;
-    g_w4_pipe.compare_exchange_strong(expect, env, std::memory_order_relaxed);
-    v = g_w4_pipe.load(std::memory_order_relaxed);
-  }
-  return v;
-}
-
 // K / V rows travel by global_load_lds_dwordx4 and Q by 16-byte loads, O leaves as 8-byte half4 stores: leading dimensions,
-// base pointers and per-image strides must keep that alignment.  The entry points of attn.hip (bad_view / bad_out) refuse
+// base pointers and per-image strides must keep that alignment.  The entry points of attn.hip (AttnView, attn_plan.h) refuse
 // anything else before the dispatch, for every kernel alike.
 int lgd_attn_w4_launch(const AttnW4Args& a, hipStream_t st, int pipe) {
   dim3 grid((a.Sq + 255) / 256, a.H, a.pair ? a.B / 2 : a.B);
@@ -612,7 +597,7 @@ int lgd_attn_w4_launch(const AttnW4Args& a, hipStream_t st, int pipe) {
     default: break;
   }
 #endif
-  // variant (lgd_set_option("attn_w4_pipe", v); initial value from LGD_W4_PIPE): 1 = one wave per SIMD with the in-wave
+  // variant (option "attn_w4_pipe", read by plan_fwd): 1 = one wave per SIMD with the in-wave
   // software pipeline (default), 0 = two waves per SIMD.  Measured equal within 2 % on MI355X (B = 16: 497 vs 500 us,
   // B = 8: 264 vs 259 us) — both sit at the SUM of their MFMA and softmax-VALU time, see DESIGN.md.
   if (pipe) hipLaunchKernelGGL((attn_w4_kernel<0, true>), grid, dim3(256), 0, st, a);

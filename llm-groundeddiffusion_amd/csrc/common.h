@@ -15,11 +15,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define LGD_WAVE 64
 
-// Error codes returned through the C ABI (0 = ok).
-#define LGD_OK 0
-#define LGD_ERR_ARG (-1)
-#define LGD_ERR_LAUNCH (-2)
-#define LGD_ERR_UNSUPPORTED (-3)
+#include "../../include/lgd_hip.h"  // LGD_OK / LGD_ERR_*: the codes returned through the C ABI
 
 static inline int lgd_check_launch() {
   hipError_t e = hipGetLastError();

@@ -2,6 +2,7 @@
 // All HBM-bound: 16-byte vector loads, fp32 statistics, wavefront-shuffle reductions.
 #include "common.h"
 #include "../../include/lgd_hip.h"
+#include "options.h"
 
 namespace {
 
@@ -330,9 +331,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const half_t* __restrict_
   }
 }
 
-// option "gn_fused": largest map (pixels) the one-launch GroupNorm takes; 0 = always two launches
-int g_gn_fused_hw = 256;
-
 // ------------------------------------------------------------------------------------------
 // Slab reduction shared by the one-launch GroupNorm BACKWARD below (round 6): a workgroup owns the (image, kg groups)
 // slab; a thread folds its 8 channels into the (at most two, cpg >= 8) groups its vector touches and deposits the two
@@ -505,12 +503,6 @@ __global__ __launch_bounds__(NT) void gn_bwd_slab_kernel(const half_t* __restric
     }
   }
 }
-
-// option "ln_stream": 1 = (default) statistics-only LayerNorm runs ln_stats_kernel, 0 = the row kernels
-int g_ln_stream = 1;
-
-// option "gn_slab": 1 = the one-launch backward takes every slab of <= 96 KB it can hold (default), 0 = two launches
-int g_gn_slab = 1;
 
 // slab geometry of a GroupNorm problem: kg groups per workgroup (smallest count whose channels fill whole 16-byte
 // vectors); false when the slab kernels cannot take it (a vector would straddle three groups, too many columns)
@@ -997,23 +989,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
 
 // Workgroups per image of the apply passes: about 1024 workgroups in total, at least one full
 // GN_UNROLL trip of pixels per thread.
-int g_gn_apply_wgs = 1024;        // option "gn_apply_wgs" (tools): workgroups per launch the apply passes aim at
 int gn_apply_blocks(int B, int HW, int C) {
+  const int wgs = lgd_option(OPT_GN_APPLY_WGS);     // (tools) workgroups per launch the apply passes aim at: 1024
   const int nvec = C / 8;
   const int pl = nvec < 256 ? 256 / nvec : 1;
   int px = GN_UNROLL * pl;
-  const int want = (int)(((long)HW * B + g_gn_apply_wgs - 1) / g_gn_apply_wgs);
+  const int want = (int)(((long)HW * B + wgs - 1) / wgs);
   if (px < want) px = want;
   int n = (HW + px - 1) / px;
   return n < 1 ? 1 : n;
 }
 
 }  // namespace
-
-void lgd_gn_set_fused_hw(int hw) { g_gn_fused_hw = hw; }
-void lgd_ln_set_stream(int on) { g_ln_stream = on; }        // lgd_set_option("ln_stream", 0 | 1) (attn.hip)
-void lgd_gn_set_slab(int on) { g_gn_slab = on; }
-void lgd_gn_set_apply_wgs(int n) { g_gn_apply_wgs = n; }            // lgd_set_option("gn_slab", 0 | 1) (attn.hip)    // lgd_set_option("gn_fused", hw) (attn.hip)
 
 // pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every choice below —
 // one launch or two, workgroups per image — follows the full B, so each image sees the launch geometry (and the
@@ -1035,7 +1022,7 @@ static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int 
     int kg = 1;
     while ((kg * cpg) % 8) kg *= 2;
     const int W = kg * cpg, nv = W / 8;
-    if (HW <= g_gn_fused_hw && kg <= 8 && (G % kg) == 0 && W <= 256) {
+    if (HW <= lgd_option(OPT_GN_FUSED) && kg <= 8 && (G % kg) == 0 && W <= 256) {
       const int pl = 256 / nv, npx = (HW + pl - 1) / pl;
       if (npx <= 32) {
 #define GN_FUSED(P)                                                                                                 \
@@ -1082,7 +1069,7 @@ extern "C" int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void*
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   {
     int kg, nv;
-    if (g_gn_slab && gn_slab_geometry(C, G, kg, nv)) {
+    if (lgd_option(OPT_GN_SLAB) && gn_slab_geometry(C, G, kg, nv)) {
 #define GN_BWD_SLAB_(NT, P, S)                                                                                      \
   hipLaunchKernelGGL((gn_bwd_slab_kernel<NT, P, S>), dim3(G / kg, B), dim3(NT), 0, st, (const half_t*)gy,             \
                      (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, stats, (half_t*)gx0,           \
@@ -1114,7 +1101,8 @@ static int layernorm_launch(const void* x, int64_t ldx, void* y, int64_t ldy, in
                             int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if ((C % 8) || C > 64 * 8 * LN_MAXV || rows < 1) return LGD_ERR_ARG;
-  if (!y && (!stats || C > (g_ln_stream ? 64 * 5 * 8 : 192 * 8))) return LGD_ERR_ARG;      // statistics-only form: stats required
+  const int ln_stream = lgd_option(OPT_LN_STREAM);
+  if (!y && (!stats || C > (ln_stream ? 64 * 5 * 8 : 192 * 8))) return LGD_ERR_ARG;      // statistics-only form: stats required
   if (rows_per_batch < 1) rows_per_batch = rows_all;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const half_t* xp = (const half_t*)x;
@@ -1123,7 +1111,7 @@ static int layernorm_launch(const void* x, int64_t ldx, void* y, int64_t ldy, in
   // statistics only: the streaming kernel (lane groups per row) once the map is large enough to keep every CU streaming
   // (measured, 40 launches in one graph: 65536 x 320 16.4 -> 10.0 us, 32768 x 320 8.7 -> 4.9, 16384 x 640 7.1 -> 5.0;
   // below ~8 M elements the one-wave-per-row kernels with their 4x more workgroups win: 4096 x 1280 3.7 vs 4.8 us)
-  if (!y && g_ln_stream && ((long)rows_all * C >= (8L << 20) || nvec > 192)) {
+  if (!y && ln_stream && ((long)rows_all * C >= (8L << 20) || nvec > 192)) {
 #define LGD_LN_STATS(L, R)                                                                                         \
   hipLaunchKernelGGL((ln_stats_kernel<L, R>), dim3((rows + 4 * (64 / L) * R - 1) / (4 * (64 / L) * R)), dim3(256), 0, st, xp, \
                      (long)ldx, rows, C, eps, stats, rows_per_batch, (long)x_bs)

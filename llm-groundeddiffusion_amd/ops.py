@@ -36,7 +36,7 @@ def set_option(name: str, value: int):
 
 
 def get_option(name: str) -> int:
-    """Value of an option the host side reads back (lgd_get_option): "cfg_pair"."""
+    """Current value of an option (lgd_get_option answers every name lgd_set_option knows)."""
     v = _lib.load().lgd_get_option(name.encode())
     if v < 0:
         raise RuntimeError(f"lgd_get_option({name}) failed")
@@ -586,14 +586,17 @@ def layernorm_bwd(gy, x, gamma, stats, *, gx=None, rows=None, ldgy=None, ldx=Non
 # ---------------------------------------------------------------------------------------------
 # attention.  Views are (tensor, ld, batch_stride) with head h at column offset h*d.
 # ---------------------------------------------------------------------------------------------
+def _default_views(H, Sq, Sk, d):
+    """The (ld, batch_stride) pairs of contiguous [B, S, H * d] operands: the query side and the key side."""
+    return (H * d, Sq * H * d), (H * d, Sk * H * d)
+
+
 def attn_fwd(q, k, v, o, B, H, Sq, Sk, d, scale, *, lse=None, q_view=None, k_view=None,
              v_view=None, o_view=None, pair=0):
     """pair (PAIR_HALF / PAIR_DUP): images b and b + B/2 hold identical q / k / v, images < B/2 are computed
     (lgd_attn_fwd_pair_f16: the kernel the full launch would run, over half the grid)."""
-    qv = q_view or (H * d, Sq * H * d)
-    kv = k_view or (H * d, Sk * H * d)
-    vv = v_view or (H * d, Sk * H * d)
-    ov = o_view or (H * d, Sq * H * d)
+    dq_, dk_ = _default_views(H, Sq, Sk, d)
+    qv, kv, vv, ov = q_view or dq_, k_view or dk_, v_view or dk_, o_view or dq_
     if pair:
         fn = lambda: _call("lgd_attn_fwd_pair_f16", _p(q), qv[0], qv[1], _p(k), kv[0], kv[1], _p(v), vv[0], vv[1],
                            _p(o), ov[0], ov[1], _p(lse), B, H, Sq, Sk, d, float(scale), int(pair), _stream())
@@ -614,8 +617,7 @@ def attn_bwd(q, k, v, o, go, lse, delta, gq, gk, gv, B, H, Sq, Sk, d, scale, *, 
              gv_view=None, sk_grad=None):
     """sk_grad: dK / dV are computed (and written) for the first sk_grad keys only (lgd_attn_bwd_keys_f16); default all."""
     skg = Sk if sk_grad is None else int(sk_grad)
-    dq_ = (H * d, Sq * H * d)
-    dk_ = (H * d, Sk * H * d)
+    dq_, dk_ = _default_views(H, Sq, Sk, d)
     qv, kv, vv = q_view or dq_, k_view or dk_, v_view or dk_
     ov, gov = o_view or dq_, go_view or dq_
     gqv, gkv, gvv = gq_view or dq_, gk_view or dk_, gv_view or dk_
@@ -631,10 +633,8 @@ def attn_bwd(q, k, v, o, go, lse, delta, gq, gk, gv, B, H, Sq, Sk, d, scale, *, 
 
 def cross_attn_fwd(q, k, v, o, B, H, Sq, Sk, d, scale, *, probs=None, tok=-1, cond_only=False,
                    q_view=None, k_view=None, v_view=None, o_view=None):
-    qv = q_view or (H * d, Sq * H * d)
-    kv = k_view or (H * d, Sk * H * d)
-    vv = v_view or (H * d, Sk * H * d)
-    ov = o_view or (H * d, Sq * H * d)
+    dq_, dk_ = _default_views(H, Sq, Sk, d)
+    qv, kv, vv, ov = q_view or dq_, k_view or dk_, v_view or dk_, o_view or dq_
     fn = lambda: _call("lgd_cross_attn_fwd_f16", _p(q), qv[0], qv[1], _p(k), kv[0], kv[1], _p(v), vv[0], vv[1],
                        _p(o), ov[0], ov[1], _p(probs), int(tok), 1 if cond_only else 0, B, H, Sq, Sk, d,
                        float(scale), _stream())
@@ -655,44 +655,31 @@ def attn_causal_fwd(q, k, v, o, B, H, S, d, scale, *, view=None):
 
 
 # Variant codes of the attention dispatch (lgd_attn_plan): family * 100000 + DP * 100 + sub, DP = the padded head dim of the
-# kernel instantiation.  Every code the library can answer is named here; ATTN_VARIANTS_ENV_ONLY are the ones only the
-# process-wide A/B switches of the environment (LGD_ATTN_NW, LGD_ATTN_BWD) select.
+# kernel instantiation.  The table is the library's (lgd_attn_variant): ATTN_VARIANTS names every code it can answer and
+# ATTN_VARIANTS_ENV_ONLY holds the ones only the process-wide A/B switches of the environment (LGD_ATTN_NW, LGD_ATTN_BWD)
+# select.  Both are read from the library on first access, so importing this module does not need it.
 ATTN_OP_FWD, ATTN_OP_BWD, ATTN_OP_CROSS_BWD = 0, 1, 2
 
 
-def _attn_variant_names():
-    names = {}
-    shapes = {0: "4 waves x 1 query tile", 1: "4 waves x 2 query tiles", 2: "8 waves x 2 query tiles"}
-    for dp in (32, 64, 96, 128, 160, 192):
-        modes = {0: f"d = {dp}", 1: f"d < {dp}, row of ones"}
-        if dp == 64:
-            modes[2] = "d < 48, row of ones, 3 dv tiles"
-        for m, mname in modes.items():
-            for s, sname in shapes.items():
-                if s == 0 or dp <= 96 or (dp == 160 and m == 0 and s == 2):
-                    names[100000 + dp * 100 + 10 * m + s] = f"attn_self_kernel DP={dp} ({mname}) {sname}"
-        names[400000 + dp * 100] = f"attn_fwd_kernel DP={dp} (two-pass softmax: map capture, causal)"
-    for dk in (48, 96):
-        for s, sname in {0: "4 waves", 1: "8 waves", 2: "8 waves, prefetch 4 ahead", 3: "8 waves, compiler's slot order"}.items():
-            names[200000 + dk * 100 + s] = f"attn_self32_kernel DK={dk} {sname}"
-    names[306400] = "attn_w4_kernel d=40, two waves per SIMD"
-    names[306401] = "attn_w4_kernel d=40, one wave per SIMD (in-wave pipeline)"
-    bshapes = {0: "1 tile per wave", 1: "2 tiles per wave", 2: "2 tiles per wave, double-buffered",
-               3: "2 tiles per wave, double-buffered, 8 waves"}
-    for dp in (32, 64, 96, 128, 160):
-        for s, sname in bshapes.items():
-            if s == 0 or (dp <= 96 and s < 3) or dp == 64:
-                names[500000 + dp * 100 + s] = f"attn_bwd_dq/dkv_kernel DP={dp} {sname}"
-                if dp == 64:
-                    names[500000 + dp * 100 + 10 + s] = f"attn_bwd_dq/dkv_kernel DP=64 (d <= 48, 3 tiles of d) {sname}"
-        names[600000 + dp * 100] = f"cross_attn_bwd_mfma_kernel DP={dp}"
-    names[700000] = "cross_attn_bwd_kernel (one wave per query row)"
-    return names
+def _attn_variants():
+    lib = _lib.load()
+    code, env_only, name = C.c_int(), C.c_int(), C.create_string_buffer(128)
+    names, env = {}, set()
+    while lib.lgd_attn_variant(len(names), C.byref(code), C.byref(env_only), name, len(name)) == 0:
+        if len(name.value) >= len(name) - 1:
+            raise RuntimeError(f"lgd_attn_variant: the name of code {code.value} does not fit {len(name)} bytes")
+        names[code.value] = name.value.decode()
+        if env_only.value:
+            env.add(code.value)
+    return names, frozenset(env)
 
 
-ATTN_VARIANTS = _attn_variant_names()
-ATTN_VARIANTS_ENV_ONLY = frozenset({103202, 103212, 106402, 106412, 106421, 109601, 109611,
-                                    503202, 506402, 506403, 506411, 509602})
+def __getattr__(attr):
+    if attr in ("ATTN_VARIANTS", "ATTN_VARIANTS_ENV_ONLY"):
+        g = globals()
+        g["ATTN_VARIANTS"], g["ATTN_VARIANTS_ENV_ONLY"] = _attn_variants()
+        return g[attr]
+    raise AttributeError(f"module {__name__!r} has no attribute {attr!r}")
 
 
 def attn_plan(op, B, H, Sq, Sk, d, *, sk_grad=None, probs=False, causal=False, pair=0, aligned=True) -> int:
@@ -742,8 +729,7 @@ def sam_window_merge(oa, B, Hs, Ws, window, NH, d, DA):
 
 def cross_attn_bwd(q, k, v, go, gp, gq, B, H, Sq, Sk, d, scale, *, q_view=None, k_view=None,
                    v_view=None, go_view=None, gq_view=None):
-    dq_ = (H * d, Sq * H * d)
-    dk_ = (H * d, Sk * H * d)
+    dq_, dk_ = _default_views(H, Sq, Sk, d)
     qv, kv, vv = q_view or dq_, k_view or dk_, v_view or dk_
     gov, gqv = go_view or dq_, gq_view or dq_
     # dQ only (text K / V are constants of the run): recomputed scores, dP = dO V^T (+ the map gradient), dQ = dS K

@@ -44,6 +44,38 @@ def test_every_row_selects_the_code_it_claims():
     assert not wrong, wrong
 
 
+def test_the_variant_table_of_the_library():
+    """lgd_attn_variant enumerated to its end: unique codes that decode to a family 1..7, names that fit the buffer, and
+    LGD_ERR_ARG past the end; ops.ATTN_VARIANTS / ATTN_VARIANTS_ENV_ONLY are that table."""
+    import ctypes as C
+    lib = _lib.load()
+    code, env_only, name = C.c_int(), C.c_int(), C.create_string_buffer(128)
+    rows = []
+    while lib.lgd_attn_variant(len(rows), C.byref(code), C.byref(env_only), name, len(name)) == 0:
+        rows.append((code.value, env_only.value, name.value.decode()))
+        assert len(rows) <= 1000
+    n = len(rows)
+    assert n == 66
+    for bad in (n, n + 1, 1 << 20, -1):
+        assert lib.lgd_attn_variant(bad, C.byref(code), C.byref(env_only), name, len(name)) == -1, bad
+    assert lib.lgd_attn_variant(0, None, None, None, 0) == 0                       # every output is optional
+    codes = [c for c, _, _ in rows]
+    assert len(set(codes)) == n
+    for c, env, nm in rows:
+        fam, dp, sub = c // 100000, (c // 100) % 1000, c % 100
+        assert 1 <= fam <= 7 and fam * 100000 + dp * 100 + sub == c, c
+        assert dp in ((0,) if fam == 7 else (48, 96) if fam == 2 else (32, 64, 96, 128, 160, 192)), c
+        assert env in (0, 1), c
+        assert 0 < len(nm) < len(name) - 1, c
+    short = C.create_string_buffer(b"x" * 8, 8)
+    assert lib.lgd_attn_variant(0, None, None, short, 5) == 0
+    assert short.raw[:5] == rows[0][2].encode()[:4] + b"\0" and short.raw[5:] == b"xxx"    # cut to the capacity given, not beyond
+    assert ops.ATTN_VARIANTS == {c: nm for c, _, nm in rows}
+    assert ops.ATTN_VARIANTS_ENV_ONLY == frozenset(c for c, env, _ in rows if env)
+    assert isinstance(ops.ATTN_VARIANTS, dict) and isinstance(ops.ATTN_VARIANTS_ENV_ONLY, frozenset)
+    assert len(ops.ATTN_VARIANTS_ENV_ONLY) == 12
+
+
 def test_every_reachable_code_has_a_row():
     assert set(acc.CODES) <= set(ops.ATTN_VARIANTS)
     missing = sorted(set(ops.ATTN_VARIANTS) - ops.ATTN_VARIANTS_ENV_ONLY - set(acc.CODES))
