@@ -498,6 +498,48 @@ int lgd_boxdiff_energy_f32(const float* const* maps, float* const* gmaps, int n_
                            const float* masks, const float* smooth, const int32_t* groups, int n_samples,
                            int max_items, int H, int T, float loss_scale, float grad_scale, float* loss, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Stage-2 evaluator (additive exports: LGD_ABI_VERSION stays 12) — scripts/owl_vit_eval.py -> utils/eval/eval.py:120-174
+ * (`eval_prompt`): OWL-ViT open-vocabulary detection, `post_process`, score filter, NMS.  The towers and the linears of
+ * the heads are the GEMM / LayerNorm / attention calls above; these two are the detection tail.
+ * ------------------------------------------------------------------------------------------- */
+/* Tail of the class head and of the box head — [ext] transformers modeling_owlvit.py, OwlViTClassPredictionHead.forward
+ * (image_class_embeds / (norm + 1e-6), query_embeds / (norm + 1e-6), einsum "...pd,...qd->...pq", + logit_shift,
+ * * (elu(logit_scale) + 1), torch.where(query_mask == 0, finfo.min, .)) and OwlViTForObjectDetection.box_predictor
+ * (pred_boxes += box_bias; sigmoid):
+ *   logits[b][p][q]  = (e.q / ((|e| + 1e-6) (|q| + 1e-6)) + shift) * (elu(scale_raw) + 1),  -FLT_MAX where query_mask == 0
+ *   pred_boxes[b][p] = sigmoid(box_raw + box_bias[p])                                        (cx, cy, w, h)
+ * class_embeds: fp16 [B*P][ld_embeds], the `dense0` output (D columns read); query_embeds: fp32 [B][Q][D]; query_mask:
+ * int32 [B][Q] or NULL (none masked); shift / scale_raw: fp32, element t at [t * ld_ss] (the two 1-wide linears, e.g.
+ * columns 0 and 1 of one fp32 GEMM output); box_raw: [B*P][4], fp32 when box_is_f32 else fp16 (the last box-MLP layer);
+ * box_bias: fp32 [P][4] (compute_box_bias, host table).  logits: fp32 [B][P][Q]; pred_boxes: fp32 [B][P][4].  Norms and
+ * dot products are fp32, one wave per token.  D <= 1024 and Q <= 64, else LGD_ERR_UNSUPPORTED. */
+int lgd_owl_heads_f32(const void* class_embeds, int64_t ld_embeds, const float* query_embeds,
+                      const int32_t* query_mask, const float* shift, const float* scale_raw, int64_t ld_ss,
+                      const void* box_raw, int box_is_f32, const float* box_bias, float* logits, float* pred_boxes,
+                      int B, int P, int Q, int D, void* stream);
+/* `post_process` + score filter + greedy NMS in one launch, one workgroup per image — [ext] OwlViTImageProcessor
+ * .post_process (max / argmax over the queries, sigmoid, center_to_corners_format), utils/eval/eval.py:144-148 (keep
+ * score >= score_threshold), :11-81 (`nms`) and :83-105 (`class_aware_nms`), boxes normalised to [0, 1] as eval_prompt
+ * passes them (input_in_pixels=False: areas without the +1).
+ *   mode 0 (from the model): logits_or_scores = logits fp32 [B][P][Q], boxes = pred_boxes fp32 [B][P][4] cxcywh; per
+ *          token score = sigmoid(max_q logit), label = the first argmax_q, box = (cx - w/2, cy - h/2, cx + w/2, cy + h/2);
+ *          labels / counts are not read.
+ *   mode 1 (candidates): logits_or_scores = scores fp32 [B][P] (>= 0), labels int32 [B][P] in [0, 2^20) or NULL (all 0),
+ *          boxes fp32 [B][P][4] xyxy, counts int32 [B] = candidates of each image (NULL: P); Q is not read.
+ * Candidates with score >= score_threshold are ordered by descending score, EQUAL scores by ascending token index (a
+ * choice: numpy's argsort at eval.py:45 leaves it open), and walked greedily in fp32: a picked box drops every later box
+ * whose inter / (area_i + area_j - inter) is not < nms_threshold.  class_aware != 0 runs that walk per label and emits
+ * the labels in ascending order, each label's picks by descending score (the output order of class_aware_nms).
+ * out_boxes fp32 [B][P][4] xyxy, out_scores fp32 [B][P], out_labels / out_index int32 [B][P] (out_index = the token a
+ * pick came from) in picking order, out_count int32 [B]; rows past the count are left untouched.  Deterministic, no
+ * atomics.  boxes / out_boxes 16-byte aligned, else LGD_ERR_ARG; P <= 4096 (large-patch14 has 3600 tokens), else
+ * LGD_ERR_UNSUPPORTED. */
+int lgd_detect_nms_f32(int mode, const float* logits_or_scores, const float* boxes, const int32_t* labels,
+                       const int32_t* counts, int B, int P, int Q, float score_threshold, float nms_threshold,
+                       int class_aware, float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_index,
+                       int32_t* out_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

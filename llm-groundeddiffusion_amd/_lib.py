@@ -99,6 +99,8 @@ SIGNATURES = {
     "lgd_sam_window_merge_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lgd_ca_energy_f32": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "lgd_boxdiff_energy_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
+    "lgd_owl_heads_f32": [_P, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "lgd_detect_nms_f32": [_I, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -6,4 +6,4 @@ from .utils import *  # noqa: F401,F403
 
 _ref = _os.environ.get("LGD_REFERENCE_ROOT")
 if _ref and _os.path.isdir(_os.path.join(_ref, "utils")):
-    __path__.append(_os.path.join(_ref, "utils"))   # parse, cache, vis, llm, eval ... (out of scope)
+    __path__.append(_os.path.join(_ref, "utils"))   # parse, cache, vis, llm ... (out of scope)

@@ -886,3 +886,52 @@ def boxdiff_energy(map_ptrs, gmap_ptrs, n_maps, side, items, masks, smooth, grou
           lambda: _call("lgd_boxdiff_energy_f32", _p(map_ptrs), _p(gmap_ptrs), int(n_maps), int(side), _p(items), _p(masks),
                         _p(smooth), _p(groups), int(n_samples), int(max_items), int(H), int(T), float(loss_scale),
                         float(grad_scale), _p(loss), _stream()))
+
+
+# ---------------------------------------------------------------------------------------------
+# detection tail of the stage-2 evaluator (csrc/detect.hip)
+# ---------------------------------------------------------------------------------------------
+def owl_heads(class_embeds, query_embeds, query_mask, shift, scale_raw, box_raw, box_bias, B, P, *, logits=None,
+              pred_boxes=None):
+    """Tail of OWL-ViT's class and box heads (lgd_owl_heads_f32).  class_embeds fp16 [B*P, >=D] (row stride = its
+    stride(0)), query_embeds fp32 [B, Q, D], query_mask int32 [B, Q] or None, shift / scale_raw fp32 views of B*P
+    elements with a common stride, box_raw fp16 / fp32 [B*P, 4], box_bias fp32 [P, 4] ->
+    (logits fp32 [B, P, Q], pred_boxes fp32 [B, P, 4])."""
+    _, Q, D = query_embeds.shape
+    dev = class_embeds.device
+    if logits is None:
+        logits = torch.empty((B, P, Q), device=dev, dtype=F32)
+    if pred_boxes is None:
+        pred_boxes = torch.empty((B, P, 4), device=dev, dtype=F32)
+    if class_embeds.dtype != F16 or query_embeds.dtype != F32 or shift.dtype != F32 or scale_raw.dtype != F32:
+        raise RuntimeError("owl_heads: class_embeds fp16; query_embeds, shift and scale_raw fp32")
+    if shift.stride(0) != scale_raw.stride(0) or not query_embeds.is_contiguous() or not box_raw.is_contiguous():
+        raise RuntimeError("owl_heads: shift / scale_raw share a stride; query_embeds and box_raw are contiguous")
+    _call("lgd_owl_heads_f32", _p(class_embeds), class_embeds.stride(0), _p(query_embeds), _p(query_mask), _p(shift),
+          _p(scale_raw), shift.stride(0), _p(box_raw), 1 if box_raw.dtype == F32 else 0, _p(box_bias), _p(logits),
+          _p(pred_boxes), B, P, Q, D, _stream())
+    return logits, pred_boxes
+
+
+def detect_nms(scores_or_logits, boxes, *, labels=None, counts=None, score_threshold=0.1, nms_threshold=0.5,
+               class_aware=False, out=None):
+    """post_process + score filter + greedy NMS (lgd_detect_nms_f32).  3-D `scores_or_logits` [B, P, Q] with cxcywh
+    `boxes` is mode 0 (from the model); 2-D scores [B, P] with int32 labels, xyxy boxes and per-image int32 counts is
+    mode 1 (candidates).  Returns (boxes [B, P, 4], scores [B, P], labels, index int32 [B, P], count int32 [B]) in
+    picking order; rows past an image's count are not written.  `out`: that tuple, preallocated."""
+    mode = 0 if scores_or_logits.dim() == 3 else 1
+    B, P = scores_or_logits.shape[:2]
+    Q = scores_or_logits.shape[2] if mode == 0 else 0
+    dev = scores_or_logits.device
+    if scores_or_logits.dtype != F32 or boxes.dtype != F32 or not scores_or_logits.is_contiguous() or not boxes.is_contiguous():
+        raise RuntimeError("detect_nms: contiguous fp32 scores / logits and boxes")
+    for t in (labels, counts):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise RuntimeError("detect_nms: labels and counts are contiguous int32")
+    if out is None:
+        out = (torch.zeros((B, P, 4), device=dev, dtype=F32), torch.zeros((B, P), device=dev, dtype=F32),
+               torch.zeros((B, P), device=dev, dtype=torch.int32), torch.zeros((B, P), device=dev, dtype=torch.int32),
+               torch.zeros((B,), device=dev, dtype=torch.int32))
+    _call("lgd_detect_nms_f32", mode, _p(scores_or_logits), _p(boxes), _p(labels), _p(counts), B, P, Q,
+          float(score_threshold), float(nms_threshold), 1 if class_aware else 0, *(_p(t) for t in out), _stream())
+    return out
