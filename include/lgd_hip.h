@@ -172,6 +172,33 @@ int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void* x1, int c0
                           int HW, int G, const float* gamma, const float* beta, int silu,
                           const float* stats, void* gx0, void* gx1, float* part, int nchunk,
                           int accumulate, void* stream);
+/* lgd_groupnorm_plan (additive export: LGD_ABI_VERSION stays 12): the code of the kernel instantiation a GroupNorm call
+ * with these arguments runs under the current option state ("gn_fused", "gn_slab") — answered by the function the launches
+ * themselves choose their kernel with; host only, nothing is launched.
+ *   op = LGD_GN_OP_FWD: lgd_groupnorm_f16 (pair = 0) / lgd_groupnorm_pair_f16 (pair = LGD_PAIR_HALF / LGD_PAIR_DUP; the
+ *                       choice follows the full B).  `silu` is not read: every forward kernel serves both.
+ *   op = LGD_GN_OP_BWD: lgd_groupnorm_bwd_f16 (pair must be 0).
+ * Negative: LGD_ERR_ARG, as the launch would answer.
+ * Preconditions of the three GroupNorm entry points (else LGD_ERR_ARG, before anything touches the device):
+ *   1 <= G <= 64; B >= 1; HW >= 1; c0 >= 8, c1 >= 0, both multiples of 8; c0 + c1 <= 4096 and a multiple of G;
+ *   nchunk >= 1; x0, gamma, beta, y and part not NULL (part also where one launch does not read it); x1 not NULL when
+ *   c1 > 0; pair form: pair LGD_PAIR_HALF or LGD_PAIR_DUP and B even (it has no statistics output);
+ *   backward: gy, stats, gx0 and part not NULL, x1 and gx1 not NULL when c1 > 0.
+ * The plan query checks those of them that its arguments show. */
+#define LGD_GN_OP_FWD 0
+#define LGD_GN_OP_BWD 1
+#define LGD_GN_FUSED_4 104            /* gn_fused_kernel<4>: one launch, at most 4 pixels per thread */
+#define LGD_GN_FUSED_8 108            /* gn_fused_kernel<8> */
+#define LGD_GN_FUSED_16 116           /* gn_fused_kernel<16> */
+#define LGD_GN_FUSED_32 132           /* gn_fused_kernel<32> */
+#define LGD_GN_TWO_LAUNCH 201         /* gn_stats_kernel + gn_apply_kernel, one channel pass (C <= 2048) */
+#define LGD_GN_TWO_LAUNCH_2PASS 202   /* the same kernels, two channel passes */
+#define LGD_GN_BWD_SLAB_256 300       /* gn_bwd_slab_kernel<256, 8, false> */
+#define LGD_GN_BWD_SLAB_256_SILU 301  /* gn_bwd_slab_kernel<256, 8, true> */
+#define LGD_GN_BWD_SLAB_512 310       /* gn_bwd_slab_kernel<512, 11, false> */
+#define LGD_GN_BWD_SLAB_512_SILU 311  /* gn_bwd_slab_kernel<512, 11, true> */
+#define LGD_GN_BWD_TWO_LAUNCH 400     /* gn_bwd_stats_kernel + gn_bwd_apply_kernel */
+int lgd_groupnorm_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair);
 
 /* LayerNorm over the last dim (attention.py:185,206,223; GatedSelfAttentionDense norm1/norm2
  * attention.py:35-36,50-51). rows x C, C % 8 == 0. y row stride ldy (lets the fuser write visual

@@ -1002,21 +1002,27 @@ int gn_apply_blocks(int B, int HW, int C) {
 
 }  // namespace
 
-// pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every choice below —
+// ------------------------------------------------------------------------------------------
+// The GroupNorm dispatch: gn_plan CHOOSES the kernel instantiation (a LGD_GN_* code of include/lgd_hip.h) from the
+// arguments and the option state; groupnorm_launch and lgd_groupnorm_bwd_f16 launch what it answers and
+// lgd_groupnorm_plan reports it, so every predicate below exists once.  Bad arguments: LGD_ERR_ARG.
+// pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every choice —
 // one launch or two, workgroups per image — follows the full B, so each image sees the launch geometry (and the
 // summation order) of the full call.  LGD_PAIR_DUP: the apply pass stores each piece for image b + B / 2 as well.
-static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G, float eps,
-                            const float* gamma, const float* beta, int silu, void* y, float* part, int nchunk,
-                            float* stats, int pair, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+// ------------------------------------------------------------------------------------------
+struct GnPlan {
+  int code;   // LGD_GN_* (> 0) or LGD_ERR_ARG
+  int kg;     // groups per workgroup of the one-launch kernels
+};
+
+static GnPlan gn_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair) {
+  const GnPlan bad = {LGD_ERR_ARG, 0};
+  if (op != LGD_GN_OP_FWD && op != LGD_GN_OP_BWD) return bad;
+  if (G < 1 || G > 64 || B < 1 || HW < 1 || c0 < 8 || c1 < 0) return bad;
   const int C = c0 + c1;
-  if (G > 64 || C > GN_MAXC || (C % G) || (c0 % 8) || (c1 % 8) || nchunk < 1) return LGD_ERR_ARG;
-  if (c1 > 0 && !x1) return LGD_ERR_ARG;
-  if (pair && ((pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) || B < 2 || (B % 2) || stats)) return LGD_ERR_ARG;
-  const int Bg = pair ? B / 2 : B;                                     // images launched
-  const long y_dup = pair == LGD_PAIR_DUP ? (long)Bg * HW * C : 0L;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  {
+  if (C > GN_MAXC || (C % G) || (c0 % 8) || (c1 % 8)) return bad;
+  if (pair && (op != LGD_GN_OP_FWD || (pair != LGD_PAIR_HALF && pair != LGD_PAIR_DUP) || (B % 2))) return bad;
+  if (op == LGD_GN_OP_FWD) {
     // one launch when a workgroup can hold its (image, kg groups) slab in registers
     const int cpg = C / G;
     int kg = 1;
@@ -1024,19 +1030,51 @@ static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int 
     const int W = kg * cpg, nv = W / 8;
     if (HW <= lgd_option(OPT_GN_FUSED) && kg <= 8 && (G % kg) == 0 && W <= 256) {
       const int pl = 256 / nv, npx = (HW + pl - 1) / pl;
-      if (npx <= 32) {
+      if (npx <= 4) return {LGD_GN_FUSED_4, kg};
+      if (npx <= 8) return {LGD_GN_FUSED_8, kg};
+      if (npx <= 16) return {LGD_GN_FUSED_16, kg};
+      if (npx <= 32) return {LGD_GN_FUSED_32, kg};
+    }
+    return {C <= GN_PASS_C ? LGD_GN_TWO_LAUNCH : LGD_GN_TWO_LAUNCH_2PASS, 0};
+  }
+  int kg, nv;
+  if (lgd_option(OPT_GN_SLAB) && gn_slab_geometry(C, G, kg, nv)) {
+    const long slab_bytes = 2L * HW * (8 * nv) * 2;             // x and gy of one workgroup
+    if (slab_bytes <= 96 * 1024) {
+      if (HW <= 8 * (256 / nv)) return {silu ? LGD_GN_BWD_SLAB_256_SILU : LGD_GN_BWD_SLAB_256, kg};
+      if (HW <= 11 * (512 / nv)) return {silu ? LGD_GN_BWD_SLAB_512_SILU : LGD_GN_BWD_SLAB_512, kg};
+    }
+  }
+  return {LGD_GN_BWD_TWO_LAUNCH, 0};
+}
+
+extern "C" int lgd_groupnorm_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair) {
+  return gn_plan(op, c0, c1, B, HW, G, silu, pair).code;
+}
+
+static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G, float eps,
+                            const float* gamma, const float* beta, int silu, void* y, float* part, int nchunk,
+                            float* stats, int pair, void* stream) {
+  const GnPlan plan = gn_plan(LGD_GN_OP_FWD, c0, c1, B, HW, G, silu, pair);
+  if (plan.code < 0) return plan.code;
+  if (!x0 || !gamma || !beta || !y || !part || nchunk < 1 || (c1 > 0 && !x1) || (pair && stats)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  const int C = c0 + c1;
+  const int Bg = pair ? B / 2 : B;                                     // images launched
+  const long y_dup = pair == LGD_PAIR_DUP ? (long)Bg * HW * C : 0L;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int kg = plan.kg;
 #define GN_FUSED(P)                                                                                                 \
   hipLaunchKernelGGL(gn_fused_kernel<P>, dim3(G / kg, Bg), dim3(256), 0, st, (const half_t*)x0, (const half_t*)x1,   \
                      c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, stats, kg, y_dup)
-        if (npx <= 4) GN_FUSED(4);
-        else if (npx <= 8) GN_FUSED(8);
-        else if (npx <= 16) GN_FUSED(16);
-        else GN_FUSED(32);
-#undef GN_FUSED
-        return lgd_check_launch();
-      }
-    }
+  switch (plan.code) {
+    case LGD_GN_FUSED_4: GN_FUSED(4); return lgd_check_launch();
+    case LGD_GN_FUSED_8: GN_FUSED(8); return lgd_check_launch();
+    case LGD_GN_FUSED_16: GN_FUSED(16); return lgd_check_launch();
+    case LGD_GN_FUSED_32: GN_FUSED(32); return lgd_check_launch();
+    default: break;
   }
+#undef GN_FUSED
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, Bg), dim3(256), 0, st, (const half_t*)x0,
                      (const half_t*)x1, c0, c1, HW, G, part, nchunk);
   const int napply = gn_apply_blocks(B, HW, C);
@@ -1063,27 +1101,25 @@ extern "C" int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void*
                                      int B, int HW, int G, const float* gamma, const float* beta,
                                      int silu, const float* stats, void* gx0, void* gx1, float* part,
                                      int nchunk, int accumulate, void* stream) {
+  const GnPlan plan = gn_plan(LGD_GN_OP_BWD, c0, c1, B, HW, G, silu, 0);
+  if (plan.code < 0) return plan.code;
+  if (!gy || !x0 || !gamma || !beta || !stats || !gx0 || !part || nchunk < 1 || (c1 > 0 && (!x1 || !gx1))) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const int C = c0 + c1;
-  if (G > 64 || C > GN_MAXC || (C % G) || (c0 % 8) || (c1 % 8) || nchunk < 1) return LGD_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  {
-    int kg, nv;
-    if (lgd_option(OPT_GN_SLAB) && gn_slab_geometry(C, G, kg, nv)) {
-#define GN_BWD_SLAB_(NT, P, S)                                                                                      \
+  const int kg = plan.kg;
+#define GN_BWD_SLAB(NT, P, S)                                                                                       \
   hipLaunchKernelGGL((gn_bwd_slab_kernel<NT, P, S>), dim3(G / kg, B), dim3(NT), 0, st, (const half_t*)gy,             \
                      (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, stats, (half_t*)gx0,           \
                      (half_t*)gx1, accumulate, kg)
-#define GN_BWD_SLAB(NT, P) do { if (silu) GN_BWD_SLAB_(NT, P, true); else GN_BWD_SLAB_(NT, P, false); } while (0)
-      const long slab_bytes = 2L * HW * (8 * nv) * 2;             // x and gy of one workgroup
-      if (slab_bytes <= 96 * 1024) {
-        if (HW <= 8 * (256 / nv)) { GN_BWD_SLAB(256, 8); return lgd_check_launch(); }
-        if (HW <= 11 * (512 / nv)) { GN_BWD_SLAB(512, 11); return lgd_check_launch(); }
-      }
-#undef GN_BWD_SLAB
-#undef GN_BWD_SLAB_
-    }
+  switch (plan.code) {
+    case LGD_GN_BWD_SLAB_256: GN_BWD_SLAB(256, 8, false); return lgd_check_launch();
+    case LGD_GN_BWD_SLAB_256_SILU: GN_BWD_SLAB(256, 8, true); return lgd_check_launch();
+    case LGD_GN_BWD_SLAB_512: GN_BWD_SLAB(512, 11, false); return lgd_check_launch();
+    case LGD_GN_BWD_SLAB_512_SILU: GN_BWD_SLAB(512, 11, true); return lgd_check_launch();
+    default: break;
   }
+#undef GN_BWD_SLAB
   hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(nchunk, B), dim3(256), 0, st, (const half_t*)gy,
                      (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, silu, stats,
                      part, nchunk);

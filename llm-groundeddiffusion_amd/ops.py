@@ -532,6 +532,25 @@ def groupnorm_bwd(gy, x, B, HW, G, gamma, beta, silu, stats, *, x1=None, gx0=Non
     return gx0, gx1
 
 
+# Codes of the GroupNorm dispatch (lgd_groupnorm_plan, LGD_GN_* of include/lgd_hip.h): the kernel instantiation a call runs.
+GN_OP_FWD, GN_OP_BWD = 0, 1
+GN_VARIANTS = {
+    104: "gn_fused_kernel<4>", 108: "gn_fused_kernel<8>", 116: "gn_fused_kernel<16>", 132: "gn_fused_kernel<32>",
+    201: "gn_stats_kernel + gn_apply_kernel, one channel pass", 202: "gn_stats_kernel + gn_apply_kernel, two channel passes",
+    300: "gn_bwd_slab_kernel<256, 8, false>", 301: "gn_bwd_slab_kernel<256, 8, true>",
+    310: "gn_bwd_slab_kernel<512, 11, false>", 311: "gn_bwd_slab_kernel<512, 11, true>",
+    400: "gn_bwd_stats_kernel + gn_bwd_apply_kernel",
+}
+
+
+def groupnorm_plan(op, c0, c1, B, HW, G, *, silu=False, pair=0) -> int:
+    """The code (a key of GN_VARIANTS) of the kernel instantiation the GroupNorm call with these arguments runs under the
+    current option state ("gn_fused", "gn_slab"); host only.  Raises for arguments the library refuses."""
+    code = _lib.load().lgd_groupnorm_plan(int(op), c0, c1, B, HW, G, 1 if silu else 0, int(pair))
+    _lib.check(min(code, 0), "lgd_groupnorm_plan")
+    return code
+
+
 def layernorm(x, gamma, beta, eps=1e-5, *, out=None, ldy=None, stats=None, rows_per_batch=0,
               x_bs=0, y_bs=0, rows=None, ldx=None, pair=0):
     """pair = PAIR_HALF: rows r and r + rows/2 are identical, the first rows/2 are normalised (lgd_layernorm_pair_f16)."""

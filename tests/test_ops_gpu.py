@@ -307,7 +307,7 @@ def test_groupnorm_fwd_bwd(dev, B, HW, C0, C1, silu, eps):
     (2, 256, 1280, 0, True), (2, 256, 1280, 1280, True), (3, 256, 1280, 640, True),    # cpg 40, 80, 60 (two groups per workgroup)
     (2, 256, 640, 0, True), (2, 64, 1280, 1280, True), (5, 64, 1280, 0, False),          # cpg 20; the 8x8 level
     (2, 256, 320, 0, False), (1, 100, 960, 0, True), (2, 256, 128, 64, False),           # cpg 10 (4 groups), 30, 6 (concat inside a group)
-    (2, 1024, 640, 320, True), (1, 1024, 1280, 640, True),                               # 32x32 with "gn_fused" raised to 1024
+    (2, 1024, 640, 0, True), (1, 1024, 1280, 0, True),                                   # 32x32 with "gn_fused" raised to 1024: gn_fused_kernel<32>
 ])
 def test_groupnorm_one_launch_vs_torch_and_two_launch(dev, B, HW, C0, C1, silu):
     """The register-resident one-launch GroupNorm of the small maps (csrc/norm.hip gn_fused_kernel) against
@@ -320,8 +320,10 @@ def test_groupnorm_one_launch_vs_torch_and_two_launch(dev, B, HW, C0, C1, silu):
     st1, st2 = torch.zeros(B, G, 2, device=dev), torch.zeros(B, G, 2, device=dev)
     try:
         ops.set_option("gn_fused", max(HW, 256))
+        assert ops.groupnorm_plan(ops.GN_OP_FWD, C0, C1, B, HW, G, silu=silu) in (104, 108, 116, 132)      # a gn_fused_kernel
         y1 = ops.groupnorm(x0, B, HW, G, eps, gamma, beta, silu, x1=x1, stats=st1)
         ops.set_option("gn_fused", 0)
+        assert ops.groupnorm_plan(ops.GN_OP_FWD, C0, C1, B, HW, G, silu=silu) in (201, 202)                # gn_stats + gn_apply
         y2 = ops.groupnorm(x0, B, HW, G, eps, gamma, beta, silu, x1=x1, stats=st2)
     finally:
         ops.set_option("gn_fused", 256)
