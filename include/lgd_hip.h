@@ -136,6 +136,11 @@ int lgd_gemm_f16(const LgdGemmDesc* desc /* host */, void* stream);
  * lgd_gemm_f16 runs first.  Host only: no HIP runtime call, pointers count for NULL-ness and alignment and are never
  * dereferenced, so it answers on a host without a GPU (e.g. whether a tuning-table tile serves a descriptor). */
 int lgd_gemm_check(const LgdGemmDesc* desc /* host */);
+/* lgd_gemm_tile (additive export: LGD_ABI_VERSION stays 12): row `index` (0, 1, ..) of the tile table: the code
+ * LgdGemmDesc.tile takes, the block shape and the name of the kernel instantiation the code launches (NUL-terminated, cut
+ * to name_cap - 1 characters; every output pointer may be NULL).  LGD_ERR_ARG past the end.  Host only.  The Python
+ * binding fills ops.TILE_NAMES (the profiler's kernel names) from it. */
+int lgd_gemm_tile(int index, int* code, int* bm, int* bn, char* name, int name_cap);
 
 /* ---------------------------------------------------------------------------------------------
  * conv_in: latents NCHW fp32 (B,4,L,L) -> [B][L*L][Cout] fp16, 3x3 pad 1 (unet_2d_condition.py:860)
@@ -187,17 +192,18 @@ int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void* x1, int c0
  * The plan query checks those of them that its arguments show. */
 #define LGD_GN_OP_FWD 0
 #define LGD_GN_OP_BWD 1
-#define LGD_GN_FUSED_4 104            /* gn_fused_kernel<4>: one launch, at most 4 pixels per thread */
-#define LGD_GN_FUSED_8 108            /* gn_fused_kernel<8> */
-#define LGD_GN_FUSED_16 116           /* gn_fused_kernel<16> */
-#define LGD_GN_FUSED_32 132           /* gn_fused_kernel<32> */
-#define LGD_GN_TWO_LAUNCH 201         /* gn_stats_kernel + gn_apply_kernel, one channel pass (C <= 2048) */
-#define LGD_GN_TWO_LAUNCH_2PASS 202   /* the same kernels, two channel passes */
-#define LGD_GN_BWD_SLAB_256 300       /* gn_bwd_slab_kernel<256, 8, false> */
-#define LGD_GN_BWD_SLAB_256_SILU 301  /* gn_bwd_slab_kernel<256, 8, true> */
-#define LGD_GN_BWD_SLAB_512 310       /* gn_bwd_slab_kernel<512, 11, false> */
-#define LGD_GN_BWD_SLAB_512_SILU 311  /* gn_bwd_slab_kernel<512, 11, true> */
-#define LGD_GN_BWD_TWO_LAUNCH 400     /* gn_bwd_stats_kernel + gn_bwd_apply_kernel */
+/* (lgd_norm_variant below names the kernel instantiation behind each code) */
+#define LGD_GN_FUSED_4 104            /* forward in one launch, at most 4 pixels per thread */
+#define LGD_GN_FUSED_8 108            /* at most 8 */
+#define LGD_GN_FUSED_16 116           /* at most 16 */
+#define LGD_GN_FUSED_32 132           /* at most 32 */
+#define LGD_GN_TWO_LAUNCH 201         /* forward in two launches (statistics, apply), one channel pass (C <= 2048) */
+#define LGD_GN_TWO_LAUNCH_2PASS 202   /* the same, two channel passes */
+#define LGD_GN_BWD_SLAB_256 300       /* backward in one launch, 256 threads hold the slab in registers */
+#define LGD_GN_BWD_SLAB_256_SILU 301  /* the same through SiLU */
+#define LGD_GN_BWD_SLAB_512 310       /* 512 threads */
+#define LGD_GN_BWD_SLAB_512_SILU 311  /* the same through SiLU */
+#define LGD_GN_BWD_TWO_LAUNCH 400     /* backward in two launches */
 int lgd_groupnorm_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair);
 
 /* LayerNorm over the last dim (attention.py:185,206,223; GatedSelfAttentionDense norm1/norm2
@@ -215,6 +221,39 @@ int lgd_layernorm_bwd_f16(const void* gy, int64_t ldgy, const void* x, int64_t l
                           int64_t ldgx, int rows, int C, const float* gamma, const float* stats,
                           int rows_per_batch, int64_t gy_bs, int64_t x_bs, int64_t gx_bs,
                           int accumulate, void* stream);
+/* lgd_layernorm_plan (additive export: LGD_ABI_VERSION stays 12): the code of the kernel instantiation a LayerNorm call
+ * runs — answered by the function the launches themselves choose their kernel with; host only, nothing is launched.
+ *   op = LGD_LN_OP_FWD: lgd_layernorm_f16 / lgd_layernorm_pair_f16 with y; LGD_LN_OP_STATS: the same with y = NULL
+ *        (statistics only); LGD_LN_OP_BWD: lgd_layernorm_bwd_f16.
+ *   rows: the row count of the FULL call (the pair form launches the kernel chosen for it over the first rows / 2).
+ *   ln_stream: the "ln_stream" option the answer holds under, 0 or 1; negative = the current option state.
+ * Negative: LGD_ERR_ARG, as the launch would answer.
+ * Preconditions of the three LayerNorm entry points (else LGD_ERR_ARG, before anything touches the device):
+ *   C a multiple of 8, C <= 2560; rows >= 1; statistics only: stats not NULL and C <= 1536 unless "ln_stream" is on;
+ *   pair form: pair LGD_PAIR_HALF, rows even and rows / 2 a multiple of rows_per_batch (where that is >= 1);
+ *   x not NULL; with y: y, gamma and beta not NULL; backward: gy, gx, gamma and stats not NULL;
+ *   every fp16 operand moves as 16-byte vectors: base pointer 16-byte aligned, leading dimension a multiple of 8, and the
+ *   batch stride too once rows > rows_per_batch >= 1 makes it count.
+ * The plan query checks those of them that its arguments show. */
+#define LGD_LN_OP_FWD 0
+#define LGD_LN_OP_STATS 1
+#define LGD_LN_OP_BWD 2
+/* (GroupNorm codes lie below 500, LayerNorm codes from 500 up; lgd_norm_variant names the instantiation behind each) */
+#define LGD_LN_ROWS_1 514    /* a wave per row set, one 16-byte vector per lane: C <= 512 */
+#define LGD_LN_ROWS_2 524    /* two vectors per lane: C <= 1024 */
+#define LGD_LN_ROWS_3 532    /* three: C <= 1536 */
+#define LGD_LN_WAVE 550      /* a wave per row, up to five vectors per lane: C <= 2560 */
+#define LGD_LN_STATS_8 608   /* statistics only, streaming: 8 lanes share a row, C <= 320 */
+#define LGD_LN_STATS_16 616  /* 16 lanes: C <= 640 */
+#define LGD_LN_STATS_32 632  /* 32 lanes: C <= 1280 */
+#define LGD_LN_STATS_64 664  /* 64 lanes: C <= 2560 */
+#define LGD_LN_BWD 700       /* the backward: a wave per row */
+int lgd_layernorm_plan(int op, int rows, int C, int ln_stream);
+/* lgd_norm_variant (additive export: LGD_ABI_VERSION stays 12): row `index` (0, 1, ..) of the library's table of norm
+ * kernel instantiations, GroupNorm rows then LayerNorm rows: its LGD_GN_* / LGD_LN_* code and the name of what it
+ * launches (NUL-terminated, cut to name_cap - 1 characters; every output pointer may be NULL).  LGD_ERR_ARG past the
+ * end.  Host only.  The Python binding fills ops.GN_VARIANTS / ops.LN_VARIANTS from it. */
+int lgd_norm_variant(int index, int* code, char* name, int name_cap);
 
 /* ---------------------------------------------------------------------------------------------
  * Scaled-dot-product attention, flash style (online softmax, K/V tiles staged in LDS, MFMA for

@@ -55,12 +55,15 @@ SIGNATURES = {
     "lgd_get_option": [C.c_char_p],
     "lgd_gemm_f16": [C.POINTER(LgdGemmDesc), _P],
     "lgd_gemm_check": [C.POINTER(LgdGemmDesc)],
+    "lgd_gemm_tile": [_I, _P, _P, _P, _P, _I],
     "lgd_conv_in_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgd_conv_out_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lgd_groupnorm_f16": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _P, _I, _P, _P],
     "lgd_groupnorm_pair_f16": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _P, _I, _I, _P],
     "lgd_groupnorm_bwd_f16": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P],
     "lgd_groupnorm_plan": [_I] * 8,
+    "lgd_layernorm_plan": [_I] * 4,
+    "lgd_norm_variant": [_I, _P, _P, _I],
     "lgd_layernorm_f16": [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _I, _L, _L, _P],
     "lgd_layernorm_pair_f16": [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _I, _L, _L, _I, _P],
     "lgd_layernorm_bwd_f16": [_P, _L, _P, _L, _P, _L, _I, _I, _P, _P, _I, _L, _L, _L, _I, _P],

@@ -1879,9 +1879,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs ga) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Launch contract.  Every tile code lgd_gemm_f16 accepts, described once: main-loop family, block shape and what the
-// code serves beyond the generic rules of gemm_check.  launch_tile maps a code to its template instantiation; nothing
-// else spells a code (the tile == 0 heuristic in gemm_check picks among them).
+// Launch contract.  Every tile code lgd_gemm_f16 accepts, described once: main-loop family, block shape, what the code
+// serves beyond the generic rules of gemm_check, the name of its kernel instantiation and its launcher.  Nothing else
+// spells a code (the tile == 0 heuristic in gemm_check picks among them); lgd_gemm_tile enumerates the table.
 // ---------------------------------------------------------------------------------------------
 enum GemmLoop : int {
   LOOP_REG,    // gemm_kernel, 4 waves: register-staged, any K
@@ -1905,25 +1905,40 @@ struct GemmTile {
   GemmLoop loop;
   int bm, bn;
   unsigned flags;
+  const char *kernel, *note;   // the profiler's name of the code: "<kernel> <bm>x<bn><note>"
+  int (*launch)(const GemmArgs&, hipStream_t);
 };
+template <int MI, int NI, int WM, bool DMA> int launch_gemm(const GemmArgs&, hipStream_t);
+template <int MI, int NI, int WM, int WN, int NS> int launch_gemm_pipe(const GemmArgs&, hipStream_t);
+template <int MI, int NI> int launch_gemm_phase(const GemmArgs&, hipStream_t);
+// One row macro per main-loop family: the template arguments, written once, give the block shape, the name and the
+// launcher.  A REG / DMA twin shares the two kernels of launch_gemm<MI, NI, 2, *>.
+#define REG_TILE(CODE, MI, NI, FLAGS) \
+  {CODE, LOOP_REG, 32 * MI, 32 * NI, FLAGS, "gemm_kernel<" #MI "," #NI ">", "", launch_gemm<MI, NI, 2, false>}
+#define DMA_TILE(CODE, MI, NI, WM, FLAGS)                                                                          \
+  {CODE, WM == 2 ? LOOP_DMA : LOOP_DMA8, 16 * WM * MI, 32 * NI, FLAGS, "gemm_dma_kernel<" #MI "," #NI "," #WM ">", "", \
+   launch_gemm<MI, NI, WM, true>}
+#define PIPE_TILE(CODE, MI, NI, NS, FLAGS, ...)                                                                 \
+  {CODE, LOOP_PIPE, 64 * MI, 32 * NI, FLAGS, "gemm_pipe_kernel<" #MI "," #NI ",4,2," #NS ">", "" __VA_ARGS__, \
+   launch_gemm_pipe<MI, NI, 4, 2, NS>}
+#define PHASE_TILE(CODE, MI, NI, FLAGS) \
+  {CODE, LOOP_PHASE, 32 * MI, 64 * NI, FLAGS, "gemm_phase_kernel<" #MI "," #NI ">", "", launch_gemm_phase<MI, NI>}
 constexpr unsigned TILE_STD = TILE_GEGLU | TILE_CNT;
+// The order of the rows is the order of first instantiation, which fixes the kernels' order in the code object.
 constexpr GemmTile GEMM_TILES[] = {
-    {1, LOOP_REG, 128, 128, TILE_STD},   {2, LOOP_REG, 128, 64, TILE_STD},     {3, LOOP_REG, 64, 128, TILE_STD},
-    {4, LOOP_REG, 64, 64, TILE_STD},     {5, LOOP_REG, 32, 128, TILE_STD},     {6, LOOP_REG, 128, 160, TILE_CNT},
-    {7, LOOP_REG, 64, 160, TILE_CNT},
-    {17, LOOP_DMA, 128, 128, TILE_STD},  {18, LOOP_DMA, 128, 64, TILE_STD},    {19, LOOP_DMA, 64, 128, TILE_STD},
-    {20, LOOP_DMA, 64, 64, TILE_STD},    {21, LOOP_DMA, 32, 128, TILE_STD},    {22, LOOP_DMA, 128, 160, TILE_CNT},
-    {23, LOOP_DMA, 64, 160, TILE_CNT},
-    {25, LOOP_DMA8, 256, 320, TILE_CNT}, {26, LOOP_DMA8, 256, 128, TILE_STD},
     // three to six stages
-    {33, LOOP_PIPE, 256, 160, TILE_CNT}, {34, LOOP_PIPE, 256, 128, TILE_STD}, {35, LOOP_PIPE, 256, 64, TILE_STD},
-    {37, LOOP_PIPE, 128, 160, TILE_CNT}, {38, LOOP_PIPE, 128, 128, TILE_STD}, {39, LOOP_PIPE, 128, 64, TILE_STD},
-    {40, LOOP_PIPE, 64, 160, TILE_CNT},  {41, LOOP_PIPE, 64, 128, TILE_STD},  {42, LOOP_PIPE, 64, 64, TILE_STD},
+    PIPE_TILE(33, 4, 5, 3, TILE_CNT), PIPE_TILE(34, 4, 4, 3, TILE_STD), PIPE_TILE(35, 4, 2, 4, TILE_STD),
+    PIPE_TILE(37, 2, 5, 4, TILE_CNT), PIPE_TILE(38, 2, 4, 4, TILE_STD), PIPE_TILE(39, 2, 2, 5, TILE_STD),
+    PIPE_TILE(40, 1, 5, 5, TILE_CNT), PIPE_TILE(41, 1, 4, 5, TILE_STD), PIPE_TILE(42, 1, 2, 6, TILE_STD),
     // two stages: eight waves of 64 x 128; 128 x 128 at two workgroups per CU
-    {44, LOOP_PIPE, 256, 256, TILE_GEGLU | TILE_PLAIN | TILE_ONE_SPLIT | TILE_LDS_EPI},
-    {45, LOOP_PIPE, 128, 128, TILE_STD | TILE_PLAIN},
-    {46, LOOP_PHASE, 256, 256, TILE_GEGLU | TILE_LDS_EPI | TILE_CONV_SAME},
-    {47, LOOP_PHASE, 256, 320, TILE_LDS_EPI | TILE_CONV_SAME},
+    PIPE_TILE(44, 4, 8, 2, TILE_GEGLU | TILE_PLAIN | TILE_ONE_SPLIT | TILE_LDS_EPI),
+    PIPE_TILE(45, 2, 4, 2, TILE_STD | TILE_PLAIN, " x2/CU"),
+    PHASE_TILE(46, 8, 4, TILE_GEGLU | TILE_LDS_EPI | TILE_CONV_SAME), PHASE_TILE(47, 8, 5, TILE_LDS_EPI | TILE_CONV_SAME),
+    REG_TILE(1, 4, 4, TILE_STD), REG_TILE(2, 4, 2, TILE_STD), REG_TILE(3, 2, 4, TILE_STD), REG_TILE(4, 2, 2, TILE_STD),
+    REG_TILE(5, 1, 4, TILE_STD), REG_TILE(6, 4, 5, TILE_CNT), REG_TILE(7, 2, 5, TILE_CNT),
+    DMA_TILE(17, 4, 4, 2, TILE_STD), DMA_TILE(18, 4, 2, 2, TILE_STD), DMA_TILE(19, 2, 4, 2, TILE_STD),
+    DMA_TILE(20, 2, 2, 2, TILE_STD), DMA_TILE(21, 1, 4, 2, TILE_STD), DMA_TILE(22, 4, 5, 2, TILE_CNT),
+    DMA_TILE(23, 2, 5, 2, TILE_CNT), DMA_TILE(25, 4, 10, 4, TILE_CNT), DMA_TILE(26, 4, 4, 4, TILE_STD),
 };
 
 // Every precondition of lgd_gemm_f16, host only: no HIP runtime call, and pointers count for NULL-ness and alignment
@@ -2047,14 +2062,14 @@ int lds_kernel(GemmKernel kern, int smem, int threads, long* resident = nullptr)
   return LGD_OK;
 }
 
-template <int MI, int NI, int WM = 2>
-int launch_gemm(const GemmArgs& ga, hipStream_t st, bool dma) {
+template <int MI, int NI, int WM, bool DMA>
+int launch_gemm(const GemmArgs& ga, hipStream_t st) {
   constexpr int BM = WM * 16 * MI, BN = 32 * NI;
   const LgdGemmDesc& d = ga.d;
   long tiles = (long)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
   dim3 grid((unsigned)tiles, 1, (unsigned)(d.nb_o * d.nb_i * d.splits));
   if constexpr (WM == 2) {
-    if (dma) hipLaunchKernelGGL((gemm_dma_kernel<MI, NI, 2>), grid, dim3(256), 0, st, ga);
+    if (DMA && d.K % BK == 0) hipLaunchKernelGGL((gemm_dma_kernel<MI, NI, 2>), grid, dim3(256), 0, st, ga);
     else hipLaunchKernelGGL((gemm_kernel<MI, NI>), grid, dim3(256), 0, st, ga);
   } else {  // the 8-wave tiles exist only with the LDS-DMA main loop
     hipLaunchKernelGGL((gemm_dma_kernel<MI, NI, WM>), grid, dim3(128 * WM), 0, st, ga);
@@ -2154,37 +2169,6 @@ int launch_gemm_phase(const GemmArgs& ga, hipStream_t st) {
   return lgd_check_launch();
 }
 
-// The instantiation behind each code of GEMM_TILES (gemm_check has accepted the descriptor for it).  The order of the
-// cases is the order of first instantiation, which fixes the kernels' order in the code object.
-int launch_tile(const GemmTile& t, const GemmArgs& ga, hipStream_t st) {
-  const bool dma = t.loop == LOOP_DMA && ga.d.K % BK == 0;
-  switch (t.code) {
-    case 33: return launch_gemm_pipe<4, 5, 4, 2, 3>(ga, st);
-    case 34: return launch_gemm_pipe<4, 4, 4, 2, 3>(ga, st);
-    case 35: return launch_gemm_pipe<4, 2, 4, 2, 4>(ga, st);
-    case 37: return launch_gemm_pipe<2, 5, 4, 2, 4>(ga, st);
-    case 38: return launch_gemm_pipe<2, 4, 4, 2, 4>(ga, st);
-    case 39: return launch_gemm_pipe<2, 2, 4, 2, 5>(ga, st);
-    case 40: return launch_gemm_pipe<1, 5, 4, 2, 5>(ga, st);
-    case 41: return launch_gemm_pipe<1, 4, 4, 2, 5>(ga, st);
-    case 42: return launch_gemm_pipe<1, 2, 4, 2, 6>(ga, st);
-    case 44: return launch_gemm_pipe<4, 8, 4, 2, 2>(ga, st);
-    case 45: return launch_gemm_pipe<2, 4, 4, 2, 2>(ga, st);
-    case 46: return launch_gemm_phase<8, 4>(ga, st);
-    case 47: return launch_gemm_phase<8, 5>(ga, st);
-    case 1: case 17: return launch_gemm<4, 4>(ga, st, dma);
-    case 2: case 18: return launch_gemm<4, 2>(ga, st, dma);
-    case 3: case 19: return launch_gemm<2, 4>(ga, st, dma);
-    case 4: case 20: return launch_gemm<2, 2>(ga, st, dma);
-    case 5: case 21: return launch_gemm<1, 4>(ga, st, dma);
-    case 6: case 22: return launch_gemm<4, 5>(ga, st, dma);
-    case 7: case 23: return launch_gemm<2, 5>(ga, st, dma);
-    case 25: return launch_gemm<4, 10, 4>(ga, st, true);
-    case 26: return launch_gemm<4, 4, 4>(ga, st, true);
-  }
-  return LGD_ERR_ARG;  // a code of GEMM_TILES without an instantiation
-}
-
 }  // namespace
 
 extern "C" int lgd_abi_version(void) { return LGD_ABI_VERSION; }
@@ -2192,6 +2176,16 @@ extern "C" int lgd_abi_version(void) { return LGD_ABI_VERSION; }
 extern "C" int lgd_gemm_check(const LgdGemmDesc* desc) {
   GemmArgs ga;
   return desc && gemm_check(*desc, ga) ? LGD_OK : LGD_ERR_ARG;
+}
+
+extern "C" int lgd_gemm_tile(int index, int* code, int* bm, int* bn, char* name, int name_cap) {
+  if (index < 0 || index >= (int)(sizeof(GEMM_TILES) / sizeof(GEMM_TILES[0]))) return LGD_ERR_ARG;
+  const GemmTile& t = GEMM_TILES[index];
+  if (code) *code = t.code;
+  if (bm) *bm = t.bm;
+  if (bn) *bn = t.bn;
+  if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s %dx%d%s", t.kernel, t.bm, t.bn, t.note);
+  return LGD_OK;
 }
 
 extern "C" int lgd_gemm_f16(const LgdGemmDesc* desc, void* stream) {
@@ -2215,7 +2209,7 @@ extern "C" int lgd_gemm_f16(const LgdGemmDesc* desc, void* stream) {
       ga.group_m = forced > 0 ? forced : (int)(g < 1 ? 1 : g > 8 ? 8 : g);
     }
   }
-  int rc = launch_tile(*t, ga, st);
+  int rc = t->launch(ga, st);
   if (rc || d.splits == 1 || d.cnt) return rc;
   // the split-K partials: a second launch sums them and applies the epilogue
   int n_out = (d.epi & LGD_EPI_GEGLU) ? d.N / 2 : d.N;

@@ -1000,22 +1000,128 @@ int gn_apply_blocks(int B, int HW, int C) {
   return n < 1 ? 1 : n;
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------
+// The norm launch contract.  Every launch path first CHOOSES a code (gn_plan / ln_plan: arguments + option state -> a
+// LGD_GN_* / LGD_LN_* code of include/lgd_hip.h), looks its row up in the variant table and calls the row's launcher;
+// lgd_groupnorm_plan / lgd_layernorm_plan report the same answer and lgd_norm_variant enumerates the table, so every
+// predicate and every code-to-instantiation mapping exists once.  A row is written as ONE set of arguments from which
+// its code, its name and the template arguments of its launcher follow.  A code without a row: LGD_ERR_UNSUPPORTED; bad
+// arguments: LGD_ERR_ARG, before anything touches the device.
+// ------------------------------------------------------------------------------------------
+struct GnArgs {             // one GroupNorm call, forward or backward
+  const half_t *gy, *x0, *x1;
+  half_t *y, *gx0, *gx1;
+  const float *gamma, *beta;
+  float *part, *stats;      // stats: written by the forward (or NULL), only read by the backward
+  float eps;
+  int c0, c1, B, Bg, HW, G, silu, kg, nchunk, accumulate;   // Bg: images launched (B / 2 in pair mode)
+  long y_dup;
+};
+struct LnArgs {             // one LayerNorm call: row r of image b of an operand starts at p + b * bs + r * ld
+  const half_t *gy, *x;
+  half_t* y;                // NULL: statistics only; the backward's gx
+  const float *gamma, *beta;
+  float* stats;             // written by the forward (or NULL), only read by the backward
+  float eps;
+  long ldgy, ldx, ldy, gy_bs, x_bs, y_bs;
+  int rows, C, rpb, accumulate;
+};
+template <class Args>
+struct NormVariant {
+  int code;
+  const char* name;         // the kernel instantiation(s) the launcher runs
+  void (*launch)(const Args&, hipStream_t);
+};
 
-// ------------------------------------------------------------------------------------------
-// The GroupNorm dispatch: gn_plan CHOOSES the kernel instantiation (a LGD_GN_* code of include/lgd_hip.h) from the
-// arguments and the option state; groupnorm_launch and lgd_groupnorm_bwd_f16 launch what it answers and
-// lgd_groupnorm_plan reports it, so every predicate below exists once.  Bad arguments: LGD_ERR_ARG.
-// pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every choice —
-// one launch or two, workgroups per image — follows the full B, so each image sees the launch geometry (and the
+template <int P>
+void launch_gn_fused(const GnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(gn_fused_kernel<P>, dim3(a.G / a.kg, a.Bg), dim3(256), 0, st, a.x0, a.x1, a.c0, a.c1, a.HW, a.G,
+                     a.eps, a.gamma, a.beta, a.silu, a.y, a.stats, a.kg, a.y_dup);
+}
+void launch_gn_two(const GnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(a.nchunk, a.Bg), dim3(256), 0, st, a.x0, a.x1, a.c0, a.c1, a.HW, a.G, a.part,
+                     a.nchunk);
+  const int napply = gn_apply_blocks(a.B, a.HW, a.c0 + a.c1);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(napply, a.Bg), dim3(256), 0, st, a.x0, a.x1, a.c0, a.c1, a.HW, a.G, a.eps,
+                     a.gamma, a.beta, a.silu, a.y, a.part, a.nchunk, a.stats, napply, a.y_dup);
+}
+template <int NT, int P, bool SILU>
+void launch_gn_bwd_slab(const GnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL((gn_bwd_slab_kernel<NT, P, SILU>), dim3(a.G / a.kg, a.B), dim3(NT), 0, st, a.gy, a.x0, a.x1, a.c0,
+                     a.c1, a.HW, a.G, a.gamma, a.beta, a.stats, a.gx0, a.gx1, a.accumulate, a.kg);
+}
+void launch_gn_bwd_two(const GnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(a.nchunk, a.B), dim3(256), 0, st, a.gy, a.x0, a.x1, a.c0, a.c1, a.HW, a.G,
+                     a.gamma, a.beta, a.silu, a.stats, a.part, a.nchunk);
+  const int napply = gn_apply_blocks(a.B, a.HW, a.c0 + a.c1);
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(napply, a.B), dim3(256), 0, st, a.gy, a.x0, a.x1, a.c0, a.c1, a.HW, a.G,
+                     a.gamma, a.beta, a.silu, a.stats, a.gx0, a.gx1, a.part, a.nchunk, a.accumulate, napply);
+}
+
+template <int MAXV, int ROWS>
+void launch_ln_rows(const LnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL((layernorm_rows_kernel<MAXV, ROWS>), dim3((a.rows + 4 * ROWS - 1) / (4 * ROWS)), dim3(256), 0, st,
+                     a.x, a.ldx, a.y, a.ldy, a.rows, a.C, a.eps, a.gamma, a.beta, a.stats, a.rpb, a.x_bs, a.y_bs);
+}
+void launch_ln_wave(const LnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(layernorm_kernel, dim3((a.rows + 3) / 4), dim3(256), 0, st, a.x, a.ldx, a.y, a.ldy, a.rows, a.C,
+                     a.eps, a.gamma, a.beta, a.stats, a.rpb, a.x_bs, a.y_bs);
+}
+template <int L, int R>
+void launch_ln_stats(const LnArgs& a, hipStream_t st) {
+  constexpr int RPG = 4 * (64 / L) * R;      // rows per workgroup
+  hipLaunchKernelGGL((ln_stats_kernel<L, R>), dim3((a.rows + RPG - 1) / RPG), dim3(256), 0, st, a.x, a.ldx, a.rows, a.C,
+                     a.eps, a.stats, a.rpb, a.x_bs);
+}
+void launch_ln_bwd(const LnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((a.rows + 3) / 4), dim3(256), 0, st, a.gy, a.ldgy, a.x, a.ldx, a.y,
+                     a.ldy, a.rows, a.C, a.gamma, a.stats, a.rpb, a.gy_bs, a.x_bs, a.y_bs, a.accumulate);
+}
+
+#define GN_FUSED_ROW(P) {LGD_GN_FUSED_##P, "gn_fused_kernel<" #P ">", launch_gn_fused<P>}
+#define GN_BWD_SLAB_ROW(NT, P, SILU)                                                                     \
+  {LGD_GN_BWD_SLAB_##NT + (SILU ? 1 : 0), "gn_bwd_slab_kernel<" #NT ", " #P ", " #SILU ">", launch_gn_bwd_slab<NT, P, SILU>}
+static_assert(LGD_GN_BWD_SLAB_256_SILU == LGD_GN_BWD_SLAB_256 + 1 && LGD_GN_BWD_SLAB_512_SILU == LGD_GN_BWD_SLAB_512 + 1,
+              "the SiLU twin of a slab code is the code + 1");
+#define LN_ROWS_ROW(MAXV, ROWS) {LGD_LN_ROWS_##MAXV, "layernorm_rows_kernel<" #MAXV ", " #ROWS ">", launch_ln_rows<MAXV, ROWS>}
+#define LN_STATS_ROW(L, R) {LGD_LN_STATS_##L, "ln_stats_kernel<" #L ", " #R ">", launch_ln_stats<L, R>}
+
+const NormVariant<GnArgs> GN_VARIANTS[] = {
+    GN_FUSED_ROW(4), GN_FUSED_ROW(8), GN_FUSED_ROW(16), GN_FUSED_ROW(32),
+    {LGD_GN_TWO_LAUNCH, "gn_stats_kernel + gn_apply_kernel, one channel pass", launch_gn_two},
+    {LGD_GN_TWO_LAUNCH_2PASS, "gn_stats_kernel + gn_apply_kernel, two channel passes", launch_gn_two},
+    GN_BWD_SLAB_ROW(256, 8, false), GN_BWD_SLAB_ROW(256, 8, true), GN_BWD_SLAB_ROW(512, 11, false), GN_BWD_SLAB_ROW(512, 11, true),
+    {LGD_GN_BWD_TWO_LAUNCH, "gn_bwd_stats_kernel + gn_bwd_apply_kernel", launch_gn_bwd_two},
+};
+const NormVariant<LnArgs> LN_VARIANTS[] = {   // (the rows' order is the kernels' order in the code object)
+    LN_STATS_ROW(8, 4), LN_STATS_ROW(16, 4), LN_STATS_ROW(32, 4), LN_STATS_ROW(64, 2),
+    LN_ROWS_ROW(1, 4), LN_ROWS_ROW(2, 4), LN_ROWS_ROW(3, 2),
+    {LGD_LN_WAVE, "layernorm_kernel", launch_ln_wave},
+    {LGD_LN_BWD, "layernorm_bwd_kernel", launch_ln_bwd},
+};
+constexpr int N_GN_VARIANTS = sizeof(GN_VARIANTS) / sizeof(GN_VARIANTS[0]);
+constexpr int N_LN_VARIANTS = sizeof(LN_VARIANTS) / sizeof(LN_VARIANTS[0]);
+
+template <class Args, int N>
+int norm_launch(const NormVariant<Args> (&rows)[N], int code, const Args& a, void* stream) {
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  for (const NormVariant<Args>& r : rows)
+    if (r.code == code) {
+      r.launch(a, reinterpret_cast<hipStream_t>(stream));
+      return lgd_check_launch();
+    }
+  return LGD_ERR_UNSUPPORTED;
+}
+
+// GroupNorm.  pair (CFG pair mode, lgd_groupnorm_pair_f16): images b < B / 2 are normalised (grid.y = B / 2); every
+// choice — one launch or two, workgroups per image — follows the full B, so each image sees the launch geometry (and the
 // summation order) of the full call.  LGD_PAIR_DUP: the apply pass stores each piece for image b + B / 2 as well.
-// ------------------------------------------------------------------------------------------
 struct GnPlan {
   int code;   // LGD_GN_* (> 0) or LGD_ERR_ARG
   int kg;     // groups per workgroup of the one-launch kernels
 };
 
-static GnPlan gn_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair) {
+GnPlan gn_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair) {
   const GnPlan bad = {LGD_ERR_ARG, 0};
   if (op != LGD_GN_OP_FWD && op != LGD_GN_OP_BWD) return bad;
   if (G < 1 || G > 64 || B < 1 || HW < 1 || c0 < 8 || c1 < 0) return bad;
@@ -1048,40 +1154,90 @@ static GnPlan gn_plan(int op, int c0, int c1, int B, int HW, int G, int silu, in
   return {LGD_GN_BWD_TWO_LAUNCH, 0};
 }
 
+int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G, float eps, const float* gamma,
+                     const float* beta, int silu, void* y, float* part, int nchunk, float* stats, int pair, void* stream) {
+  const GnPlan plan = gn_plan(LGD_GN_OP_FWD, c0, c1, B, HW, G, silu, pair);
+  if (plan.code < 0) return plan.code;
+  if (!x0 || !gamma || !beta || !y || !part || nchunk < 1 || (c1 > 0 && !x1) || (pair && stats)) return LGD_ERR_ARG;
+  const int Bg = pair ? B / 2 : B;
+  const GnArgs a = {nullptr, (const half_t*)x0, (const half_t*)x1, (half_t*)y, nullptr, nullptr, gamma, beta, part, stats, eps,
+                    c0, c1, B, Bg, HW, G, silu, plan.kg, nchunk, 0, pair == LGD_PAIR_DUP ? (long)Bg * HW * (c0 + c1) : 0L};
+  return norm_launch(GN_VARIANTS, plan.code, a, stream);
+}
+
+// LayerNorm.  `rows` is the FULL call's row count: the pair form launches the kernel chosen for it over the first half.
+int ln_plan(int op, long rows, int C, int ln_stream) {
+  if ((C % 8) || C > 64 * 8 * LN_MAXV || rows < 1) return LGD_ERR_ARG;
+  const int nvec = C / 8;
+  if (op == LGD_LN_OP_BWD) return LGD_LN_BWD;
+  if (op == LGD_LN_OP_STATS) {
+    // the streaming kernel (lane groups per row) once the map is large enough to keep every CU streaming
+    // (measured, 40 launches in one graph: 65536 x 320 16.4 -> 10.0 us, 32768 x 320 8.7 -> 4.9, 16384 x 640 7.1 -> 5.0;
+    // below ~8 M elements the one-wave-per-row kernels with their 4x more workgroups win: 4096 x 1280 3.7 vs 4.8 us)
+    if (ln_stream && (rows * C >= (8L << 20) || nvec > 192))
+      return nvec <= 40 ? LGD_LN_STATS_8 : nvec <= 80 ? LGD_LN_STATS_16 : nvec <= 160 ? LGD_LN_STATS_32 : LGD_LN_STATS_64;
+    if (nvec > 192) return LGD_ERR_ARG;      // the row kernels serve the statistics-only form: three vectors per lane
+  } else if (op != LGD_LN_OP_FWD) {
+    return LGD_ERR_ARG;
+  }
+  return nvec <= 64 ? LGD_LN_ROWS_1 : nvec <= 128 ? LGD_LN_ROWS_2 : nvec <= 192 ? LGD_LN_ROWS_3 : LGD_LN_WAVE;
+}
+
+// rows of an operand move as 16-byte vectors (bs is read once a second image exists)
+bool ln_vectors(const void* p, long ld, long bs, bool batched) {
+  return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 8 == 0 && (!batched || bs % 8 == 0);
+}
+
+// Every precondition of the three LayerNorm entry points, host only.  `a` comes in with the full call's rows and the
+// caller's rows_per_batch and leaves with the rows to launch and rpb >= 1; the answer is the code to launch.
+enum LnEntry { LN_FULL, LN_PAIR, LN_BACKWARD };
+int ln_check(LnEntry entry, int pair, LnArgs& a) {
+  const int rows_all = a.rows;
+  if (entry == LN_PAIR) {
+    // rows of the second half are copies of the first: only HALF exists here (the consumers of a LayerNorm inside the
+    // shared prefix are pair-mode GEMMs, which read row m only); the half is a whole number of images
+    if (pair != LGD_PAIR_HALF || rows_all < 2 || (rows_all % 2)) return LGD_ERR_ARG;
+    if (a.rpb >= 1 && ((rows_all / 2) % a.rpb)) return LGD_ERR_ARG;
+    a.rows = rows_all / 2;
+  }
+  const int op = entry == LN_BACKWARD ? LGD_LN_OP_BWD : a.y ? LGD_LN_OP_FWD : LGD_LN_OP_STATS;
+  const int code = ln_plan(op, rows_all, a.C, lgd_option(OPT_LN_STREAM));
+  if (code < 0) return code;
+  if (a.rpb < 1) a.rpb = rows_all;
+  const bool batched = a.rpb < a.rows;
+  bool ok = ln_vectors(a.x, a.ldx, a.x_bs, batched);
+  if (op == LGD_LN_OP_FWD) ok = ok && a.gamma && a.beta && ln_vectors(a.y, a.ldy, a.y_bs, batched);
+  if (op == LGD_LN_OP_STATS) ok = ok && a.stats;
+  if (op == LGD_LN_OP_BWD)
+    ok = ok && a.gamma && a.stats && ln_vectors(a.gy, a.ldgy, a.gy_bs, batched) && ln_vectors(a.y, a.ldy, a.y_bs, batched);
+  return ok ? code : LGD_ERR_ARG;
+}
+
+int layernorm_launch(LnEntry entry, int pair, const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C, float eps,
+                     const float* gamma, const float* beta, float* stats, int rows_per_batch, int64_t x_bs, int64_t y_bs,
+                     void* stream) {
+  LnArgs a = {nullptr, (const half_t*)x, (half_t*)y, gamma, beta, stats, eps, 0, ldx, ldy, 0, x_bs, y_bs, rows, C, rows_per_batch, 0};
+  const int code = ln_check(entry, pair, a);
+  return code < 0 ? code : norm_launch(LN_VARIANTS, code, a, stream);
+}
+
+}  // namespace
+
 extern "C" int lgd_groupnorm_plan(int op, int c0, int c1, int B, int HW, int G, int silu, int pair) {
   return gn_plan(op, c0, c1, B, HW, G, silu, pair).code;
 }
 
-static int groupnorm_launch(const void* x0, const void* x1, int c0, int c1, int B, int HW, int G, float eps,
-                            const float* gamma, const float* beta, int silu, void* y, float* part, int nchunk,
-                            float* stats, int pair, void* stream) {
-  const GnPlan plan = gn_plan(LGD_GN_OP_FWD, c0, c1, B, HW, G, silu, pair);
-  if (plan.code < 0) return plan.code;
-  if (!x0 || !gamma || !beta || !y || !part || nchunk < 1 || (c1 > 0 && !x1) || (pair && stats)) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  const int C = c0 + c1;
-  const int Bg = pair ? B / 2 : B;                                     // images launched
-  const long y_dup = pair == LGD_PAIR_DUP ? (long)Bg * HW * C : 0L;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int kg = plan.kg;
-#define GN_FUSED(P)                                                                                                 \
-  hipLaunchKernelGGL(gn_fused_kernel<P>, dim3(G / kg, Bg), dim3(256), 0, st, (const half_t*)x0, (const half_t*)x1,   \
-                     c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, stats, kg, y_dup)
-  switch (plan.code) {
-    case LGD_GN_FUSED_4: GN_FUSED(4); return lgd_check_launch();
-    case LGD_GN_FUSED_8: GN_FUSED(8); return lgd_check_launch();
-    case LGD_GN_FUSED_16: GN_FUSED(16); return lgd_check_launch();
-    case LGD_GN_FUSED_32: GN_FUSED(32); return lgd_check_launch();
-    default: break;
-  }
-#undef GN_FUSED
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, Bg), dim3(256), 0, st, (const half_t*)x0,
-                     (const half_t*)x1, c0, c1, HW, G, part, nchunk);
-  const int napply = gn_apply_blocks(B, HW, C);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(napply, Bg), dim3(256), 0, st, (const half_t*)x0,
-                     (const half_t*)x1, c0, c1, HW, G, eps, gamma, beta, silu, (half_t*)y, part,
-                     nchunk, stats, napply, y_dup);
-  return lgd_check_launch();
+extern "C" int lgd_layernorm_plan(int op, int rows, int C, int ln_stream) {
+  return ln_plan(op, rows, C, ln_stream < 0 ? lgd_option(OPT_LN_STREAM) : ln_stream);
+}
+
+// Row `index` of the variant table (GroupNorm rows, then LayerNorm rows), in table order.  Host only.
+extern "C" int lgd_norm_variant(int index, int* code, char* name, int name_cap) {
+  if (index < 0 || index >= N_GN_VARIANTS + N_LN_VARIANTS) return LGD_ERR_ARG;
+  const bool gn = index < N_GN_VARIANTS;
+  if (code) *code = gn ? GN_VARIANTS[index].code : LN_VARIANTS[index - N_GN_VARIANTS].code;
+  if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", gn ? GN_VARIANTS[index].name : LN_VARIANTS[index - N_GN_VARIANTS].name);
+  return LGD_OK;
 }
 
 extern "C" int lgd_groupnorm_f16(const void* x0, const void* x1, int c0, int c1, int B, int HW,
@@ -1104,102 +1260,29 @@ extern "C" int lgd_groupnorm_bwd_f16(const void* gy, const void* x0, const void*
   const GnPlan plan = gn_plan(LGD_GN_OP_BWD, c0, c1, B, HW, G, silu, 0);
   if (plan.code < 0) return plan.code;
   if (!gy || !x0 || !gamma || !beta || !stats || !gx0 || !part || nchunk < 1 || (c1 > 0 && (!x1 || !gx1))) return LGD_ERR_ARG;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  const int C = c0 + c1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int kg = plan.kg;
-#define GN_BWD_SLAB(NT, P, S)                                                                                       \
-  hipLaunchKernelGGL((gn_bwd_slab_kernel<NT, P, S>), dim3(G / kg, B), dim3(NT), 0, st, (const half_t*)gy,             \
-                     (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, stats, (half_t*)gx0,           \
-                     (half_t*)gx1, accumulate, kg)
-  switch (plan.code) {
-    case LGD_GN_BWD_SLAB_256: GN_BWD_SLAB(256, 8, false); return lgd_check_launch();
-    case LGD_GN_BWD_SLAB_256_SILU: GN_BWD_SLAB(256, 8, true); return lgd_check_launch();
-    case LGD_GN_BWD_SLAB_512: GN_BWD_SLAB(512, 11, false); return lgd_check_launch();
-    case LGD_GN_BWD_SLAB_512_SILU: GN_BWD_SLAB(512, 11, true); return lgd_check_launch();
-    default: break;
-  }
-#undef GN_BWD_SLAB
-  hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(nchunk, B), dim3(256), 0, st, (const half_t*)gy,
-                     (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, silu, stats,
-                     part, nchunk);
-  const int napply = gn_apply_blocks(B, HW, C);
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(napply, B), dim3(256), 0, st, (const half_t*)gy,
-                     (const half_t*)x0, (const half_t*)x1, c0, c1, HW, G, gamma, beta, silu, stats,
-                     (half_t*)gx0, (half_t*)gx1, part, nchunk, accumulate, napply);
-  return lgd_check_launch();
-}
-
-// half (CFG pair mode, lgd_layernorm_pair_f16): the kernel is CHOSEN for `rows_all` rows — what the full call would
-// run — and launched over the first `rows` = rows_all / 2 of them.
-static int layernorm_launch(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int rows_all, int C,
-                            float eps, const float* gamma, const float* beta, float* stats,
-                            int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if ((C % 8) || C > 64 * 8 * LN_MAXV || rows < 1) return LGD_ERR_ARG;
-  const int ln_stream = lgd_option(OPT_LN_STREAM);
-  if (!y && (!stats || C > (ln_stream ? 64 * 5 * 8 : 192 * 8))) return LGD_ERR_ARG;      // statistics-only form: stats required
-  if (rows_per_batch < 1) rows_per_batch = rows_all;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const half_t* xp = (const half_t*)x;
-  half_t* yp = (half_t*)y;
-  const int nvec = C / 8;
-  // statistics only: the streaming kernel (lane groups per row) once the map is large enough to keep every CU streaming
-  // (measured, 40 launches in one graph: 65536 x 320 16.4 -> 10.0 us, 32768 x 320 8.7 -> 4.9, 16384 x 640 7.1 -> 5.0;
-  // below ~8 M elements the one-wave-per-row kernels with their 4x more workgroups win: 4096 x 1280 3.7 vs 4.8 us)
-  if (!y && ln_stream && ((long)rows_all * C >= (8L << 20) || nvec > 192)) {
-#define LGD_LN_STATS(L, R)                                                                                         \
-  hipLaunchKernelGGL((ln_stats_kernel<L, R>), dim3((rows + 4 * (64 / L) * R - 1) / (4 * (64 / L) * R)), dim3(256), 0, st, xp, \
-                     (long)ldx, rows, C, eps, stats, rows_per_batch, (long)x_bs)
-    if (nvec <= 40) LGD_LN_STATS(8, 4);
-    else if (nvec <= 80) LGD_LN_STATS(16, 4);
-    else if (nvec <= 160) LGD_LN_STATS(32, 4);
-    else LGD_LN_STATS(64, 2);
-#undef LGD_LN_STATS
-    return lgd_check_launch();
-  }
-#define LGD_LN_LAUNCH(MAXV, ROWS)                                                                   \
-  hipLaunchKernelGGL((layernorm_rows_kernel<MAXV, ROWS>), dim3((rows + 4 * ROWS - 1) / (4 * ROWS)), \
-                     dim3(256), 0, st, xp, (long)ldx, yp, (long)ldy, rows, C, eps, gamma, beta,      \
-                     stats, rows_per_batch, (long)x_bs, (long)y_bs)
-  if (nvec <= 64) LGD_LN_LAUNCH(1, 4);
-  else if (nvec <= 128) LGD_LN_LAUNCH(2, 4);
-  else if (nvec <= 192) LGD_LN_LAUNCH(3, 2);
-  else
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, xp, (long)ldx, yp,
-                       (long)ldy, rows, C, eps, gamma, beta, stats, rows_per_batch, (long)x_bs,
-                       (long)y_bs);
-#undef LGD_LN_LAUNCH
-  return lgd_check_launch();
+  const GnArgs a = {(const half_t*)gy, (const half_t*)x0, (const half_t*)x1, nullptr, (half_t*)gx0, (half_t*)gx1, gamma, beta, part,
+                    const_cast<float*>(stats), 0.f, c0, c1, B, B, HW, G, silu, plan.kg, nchunk, accumulate, 0L};
+  return norm_launch(GN_VARIANTS, plan.code, a, stream);
 }
 
 extern "C" int lgd_layernorm_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C,
                                  float eps, const float* gamma, const float* beta, float* stats,
                                  int rows_per_batch, int64_t x_bs, int64_t y_bs, void* stream) {
-  return layernorm_launch(x, ldx, y, ldy, rows, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
+  return layernorm_launch(LN_FULL, 0, x, ldx, y, ldy, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
 }
 
 extern "C" int lgd_layernorm_pair_f16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int C,
                                       float eps, const float* gamma, const float* beta, float* stats,
                                       int rows_per_batch, int64_t x_bs, int64_t y_bs, int pair, void* stream) {
-  // rows of the second half are copies of the first: only HALF exists here (the consumers of a LayerNorm inside the
-  // shared prefix are pair-mode GEMMs, which read row m only)
-  if (pair != LGD_PAIR_HALF || rows < 2 || (rows % 2)) return LGD_ERR_ARG;
-  if (rows_per_batch >= 1 && ((rows / 2) % rows_per_batch)) return LGD_ERR_ARG;   // the half is a whole number of images
-  return layernorm_launch(x, ldx, y, ldy, rows / 2, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
+  return layernorm_launch(LN_PAIR, pair, x, ldx, y, ldy, rows, C, eps, gamma, beta, stats, rows_per_batch, x_bs, y_bs, stream);
 }
 
 extern "C" int lgd_layernorm_bwd_f16(const void* gy, int64_t ldgy, const void* x, int64_t ldx,
                                      void* gx, int64_t ldgx, int rows, int C, const float* gamma,
                                      const float* stats, int rows_per_batch, int64_t gy_bs,
                                      int64_t x_bs, int64_t gx_bs, int accumulate, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if ((C % 8) || C > 64 * 8 * LN_MAXV || rows < 1 || !stats) return LGD_ERR_ARG;
-  if (rows_per_batch < 1) rows_per_batch = rows;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st,
-                     (const half_t*)gy, (long)ldgy, (const half_t*)x, (long)ldx, (half_t*)gx,
-                     (long)ldgx, rows, C, gamma, stats, rows_per_batch, (long)gy_bs, (long)x_bs,
-                     (long)gx_bs, accumulate);
-  return lgd_check_launch();
+  LnArgs a = {(const half_t*)gy, (const half_t*)x, (half_t*)gx, gamma, nullptr, const_cast<float*>(stats), 0.f,
+              ldgy, ldx, ldgx, gy_bs, x_bs, gx_bs, rows, C, rows_per_batch, accumulate};
+  const int code = ln_check(LN_BACKWARD, 0, a);
+  return code < 0 ? code : norm_launch(LN_VARIANTS, code, a, stream);
 }

@@ -171,24 +171,6 @@ def gemm_set_pair(d, mode) -> bool:
     return True
 
 
-# profiler kernel names of the tile codes (tools/ and profiles/ key on them); which descriptors a code serves is the
-# library's to say (gemm_accepts)
-TILE_NAMES = {
-    1: "gemm_kernel<4,4> 128x128", 2: "gemm_kernel<4,2> 128x64", 3: "gemm_kernel<2,4> 64x128", 4: "gemm_kernel<2,2> 64x64",
-    5: "gemm_kernel<1,4> 32x128", 6: "gemm_kernel<4,5> 128x160", 7: "gemm_kernel<2,5> 64x160",
-    17: "gemm_dma_kernel<4,4,2> 128x128", 18: "gemm_dma_kernel<4,2,2> 128x64", 19: "gemm_dma_kernel<2,4,2> 64x128",
-    20: "gemm_dma_kernel<2,2,2> 64x64", 21: "gemm_dma_kernel<1,4,2> 32x128", 22: "gemm_dma_kernel<4,5,2> 128x160",
-    23: "gemm_dma_kernel<2,5,2> 64x160", 25: "gemm_dma_kernel<4,10,4> 256x320", 26: "gemm_dma_kernel<4,4,4> 256x128",
-    33: "gemm_pipe_kernel<4,5,4,2,3> 256x160", 34: "gemm_pipe_kernel<4,4,4,2,3> 256x128",
-    35: "gemm_pipe_kernel<4,2,4,2,4> 256x64", 37: "gemm_pipe_kernel<2,5,4,2,4> 128x160",
-    38: "gemm_pipe_kernel<2,4,4,2,4> 128x128", 39: "gemm_pipe_kernel<2,2,4,2,5> 128x64",
-    40: "gemm_pipe_kernel<1,5,4,2,5> 64x160", 41: "gemm_pipe_kernel<1,4,4,2,5> 64x128",
-    42: "gemm_pipe_kernel<1,2,4,2,6> 64x64", 44: "gemm_pipe_kernel<4,8,4,2,2> 256x256",
-    45: "gemm_pipe_kernel<2,4,4,2,2> 128x128 x2/CU", 46: "gemm_phase_kernel<8,4> 256x256",
-    47: "gemm_phase_kernel<8,5> 256x320",
-}
-
-
 def choose_tile(M, N, batches=1, geglu=False, K=64, pipe_ok=False):
     """Tile heuristic for shapes the tuning table does not list (same rule as the library's auto mode,
     done here so the choice is known to the profiler): the largest tile that still yields enough
@@ -363,7 +345,7 @@ def gemm_launch(desc, tag=None, flops=None):
             flops *= 0.5
         m_in, m_out = (desc.M // 2 if desc.pair else desc.M), (desc.M // 2 if desc.pair == PAIR_HALF else desc.M)
         nbytes = 2.0 * nb * (m_in * desc.K / max(desc.taps, 1) + desc.N * desc.K + m_out * desc.N)
-        return PROFILER.wrap(TILE_NAMES.get(desc.tile, "gemm"), flops, nbytes,
+        return PROFILER.wrap(_table("TILE_NAMES").get(desc.tile, "gemm"), flops, nbytes,
                              lambda: _call("lgd_gemm_f16", C.byref(desc), _stream()), tag,
                              shape=f"{shape_key(desc)} splits={desc.splits}")
     _call("lgd_gemm_f16", C.byref(desc), _stream())
@@ -532,15 +514,10 @@ def groupnorm_bwd(gy, x, B, HW, G, gamma, beta, silu, stats, *, x1=None, gx0=Non
     return gx0, gx1
 
 
-# Codes of the GroupNorm dispatch (lgd_groupnorm_plan, LGD_GN_* of include/lgd_hip.h): the kernel instantiation a call runs.
+# Codes of the norm dispatch (LGD_GN_* / LGD_LN_* of include/lgd_hip.h): the kernel instantiation a call runs; GN_VARIANTS /
+# LN_VARIANTS (below) name them.
 GN_OP_FWD, GN_OP_BWD = 0, 1
-GN_VARIANTS = {
-    104: "gn_fused_kernel<4>", 108: "gn_fused_kernel<8>", 116: "gn_fused_kernel<16>", 132: "gn_fused_kernel<32>",
-    201: "gn_stats_kernel + gn_apply_kernel, one channel pass", 202: "gn_stats_kernel + gn_apply_kernel, two channel passes",
-    300: "gn_bwd_slab_kernel<256, 8, false>", 301: "gn_bwd_slab_kernel<256, 8, true>",
-    310: "gn_bwd_slab_kernel<512, 11, false>", 311: "gn_bwd_slab_kernel<512, 11, true>",
-    400: "gn_bwd_stats_kernel + gn_bwd_apply_kernel",
-}
+LN_OP_FWD, LN_OP_STATS, LN_OP_BWD = 0, 1, 2
 
 
 def groupnorm_plan(op, c0, c1, B, HW, G, *, silu=False, pair=0) -> int:
@@ -549,6 +526,20 @@ def groupnorm_plan(op, c0, c1, B, HW, G, *, silu=False, pair=0) -> int:
     code = _lib.load().lgd_groupnorm_plan(int(op), c0, c1, B, HW, G, 1 if silu else 0, int(pair))
     _lib.check(min(code, 0), "lgd_groupnorm_plan")
     return code
+
+
+def layernorm_plan(op, rows, C_, *, ln_stream=None) -> int:
+    """The code (a key of LN_VARIANTS) of the kernel instantiation the LayerNorm call runs: op LN_OP_FWD (y written),
+    LN_OP_STATS (statistics only) or LN_OP_BWD, `rows` of the full call (a pair launch runs the kernel chosen for them),
+    under "ln_stream" = 0 / 1 or, by default, the current option state; host only.  Raises for arguments the library refuses."""
+    code = _lib.load().lgd_layernorm_plan(int(op), rows, C_, -1 if ln_stream is None else int(ln_stream))
+    _lib.check(min(code, 0), "lgd_layernorm_plan")
+    return code
+
+
+def layernorm_stats_served(rows, C_) -> bool:
+    """Whether the statistics-only form serves rows of C_ channels whatever "ln_stream" says (the row kernels do)."""
+    return _lib.load().lgd_layernorm_plan(LN_OP_STATS, rows, C_, 0) > 0
 
 
 def layernorm(x, gamma, beta, eps=1e-5, *, out=None, ldy=None, stats=None, rows_per_batch=0,
@@ -674,30 +665,44 @@ def attn_causal_fwd(q, k, v, o, B, H, S, d, scale, *, view=None):
 
 
 # Variant codes of the attention dispatch (lgd_attn_plan): family * 100000 + DP * 100 + sub, DP = the padded head dim of the
-# kernel instantiation.  The table is the library's (lgd_attn_variant): ATTN_VARIANTS names every code it can answer and
-# ATTN_VARIANTS_ENV_ONLY holds the ones only the process-wide A/B switches of the environment (LGD_ATTN_NW, LGD_ATTN_BWD)
-# select.  Both are read from the library on first access, so importing this module does not need it.
+# kernel instantiation.
 ATTN_OP_FWD, ATTN_OP_BWD, ATTN_OP_CROSS_BWD = 0, 1, 2
 
 
-def _attn_variants():
-    lib = _lib.load()
-    code, env_only, name = C.c_int(), C.c_int(), C.create_string_buffer(128)
-    names, env = {}, set()
-    while lib.lgd_attn_variant(len(names), C.byref(code), C.byref(env_only), name, len(name)) == 0:
+# Tables the library owns, read from it on first access (so importing this module does not need it):
+#   TILE_NAMES              GEMM tile code -> profiler kernel name (lgd_gemm_tile; tools/ and profiles/ key on the names;
+#                           which descriptors a code serves is the library's to say: gemm_accepts)
+#   GN_VARIANTS, LN_VARIANTS  LGD_GN_* (below 500) / LGD_LN_* code -> kernel instantiation (lgd_norm_variant)
+#   ATTN_VARIANTS           attention variant code -> kernel instantiation (lgd_attn_variant); ATTN_VARIANTS_ENV_ONLY: the
+#                           codes only the process-wide A/B switches of the environment (LGD_ATTN_NW, LGD_ATTN_BWD) select
+_TABLES = ("TILE_NAMES", "GN_VARIANTS", "LN_VARIANTS", "ATTN_VARIANTS", "ATTN_VARIANTS_ENV_ONLY")
+
+
+def _rows(export, n_ints):
+    """The rows (int, .., name) of a table the library enumerates with export(index, &int, .., name, name_cap)."""
+    fn = getattr(_lib.load(), export)
+    ints, name, rows = [C.c_int() for _ in range(n_ints)], C.create_string_buffer(128), []
+    while fn(len(rows), *map(C.byref, ints), name, len(name)) == 0:
         if len(name.value) >= len(name) - 1:
-            raise RuntimeError(f"lgd_attn_variant: the name of code {code.value} does not fit {len(name)} bytes")
-        names[code.value] = name.value.decode()
-        if env_only.value:
-            env.add(code.value)
-    return names, frozenset(env)
+            raise RuntimeError(f"{export}: the name of row {len(rows)} does not fit {len(name)} bytes")
+        rows.append(tuple(i.value for i in ints) + (name.value.decode(),))
+    return rows
+
+
+def _table(attr):
+    g = globals()
+    if attr not in g:
+        attn, norm = _rows("lgd_attn_variant", 2), _rows("lgd_norm_variant", 1)
+        g.update(TILE_NAMES=dict(sorted((c, nm) for c, _, _, nm in _rows("lgd_gemm_tile", 3))),
+                 GN_VARIANTS={c: nm for c, nm in norm if c < 500}, LN_VARIANTS={c: nm for c, nm in norm if c >= 500},
+                 ATTN_VARIANTS={c: nm for c, _, nm in attn},
+                 ATTN_VARIANTS_ENV_ONLY=frozenset(c for c, env, _ in attn if env))
+    return g[attr]
 
 
 def __getattr__(attr):
-    if attr in ("ATTN_VARIANTS", "ATTN_VARIANTS_ENV_ONLY"):
-        g = globals()
-        g["ATTN_VARIANTS"], g["ATTN_VARIANTS_ENV_ONLY"] = _attn_variants()
-        return g[attr]
+    if attr in _TABLES:
+        return _table(attr)
     raise AttributeError(f"module {__name__!r} has no attribute {attr!r}")
 
 

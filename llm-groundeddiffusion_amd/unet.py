@@ -366,9 +366,8 @@ class Plan:
         LGD_EPI_ROWNORM).  Grad plans keep the two ops: the backward needs the LayerNorm's own node."""
         eng = self.eng
         has_b = f"{name}.b" in eng.w.f
-        # the statistics-only form of lgd_layernorm_f16 (y = NULL) exists in the row kernels only: widths up to 1536
-        # (every SD 1.x / 2.x / SDXL-refiner transformer); wider rows keep the two ops
-        if self.grad or not eng.fold_ln or x.C > 1536:
+        # rows too wide for the statistics-only form of lgd_layernorm_f16 (y = NULL) keep the two ops
+        if self.grad or not eng.fold_ln or not ops.layernorm_stats_served(x.rows, x.C):
             y = self.layernorm(x, norm, half=True)       # (HALF only where the linear behind it runs in pair mode)
             if geglu:
                 return self.linear(y, name, geglu=True, half=half)

@@ -22,7 +22,10 @@ import math
 
 import torch
 
+import __graft_entry__
 from lgd_amd import ops
+
+__graft_entry__.build()         # TILES below is read from the library's tile table
 
 P = 1 << 20                     # an aligned placeholder address: descriptors are only checked with it
 GUARD = 4096                    # guard elements in front of and behind every carved operand

@@ -42,6 +42,63 @@ def test_tile_codes_are_exactly_tile_names():
     assert ops.gemm_accepts(ops.gemm_desc(p, p, p, 512, 640, 640, splits=1, tile=0))          # 0 = the library's heuristic
 
 
+# the profiler's kernel names (profiles/, tools/ and bench.py's roofline key on them), pinned: code, then the name
+PINNED_TILE_NAMES = """
+1 gemm_kernel<4,4> 128x128
+2 gemm_kernel<4,2> 128x64
+3 gemm_kernel<2,4> 64x128
+4 gemm_kernel<2,2> 64x64
+5 gemm_kernel<1,4> 32x128
+6 gemm_kernel<4,5> 128x160
+7 gemm_kernel<2,5> 64x160
+17 gemm_dma_kernel<4,4,2> 128x128
+18 gemm_dma_kernel<4,2,2> 128x64
+19 gemm_dma_kernel<2,4,2> 64x128
+20 gemm_dma_kernel<2,2,2> 64x64
+21 gemm_dma_kernel<1,4,2> 32x128
+22 gemm_dma_kernel<4,5,2> 128x160
+23 gemm_dma_kernel<2,5,2> 64x160
+25 gemm_dma_kernel<4,10,4> 256x320
+26 gemm_dma_kernel<4,4,4> 256x128
+33 gemm_pipe_kernel<4,5,4,2,3> 256x160
+34 gemm_pipe_kernel<4,4,4,2,3> 256x128
+35 gemm_pipe_kernel<4,2,4,2,4> 256x64
+37 gemm_pipe_kernel<2,5,4,2,4> 128x160
+38 gemm_pipe_kernel<2,4,4,2,4> 128x128
+39 gemm_pipe_kernel<2,2,4,2,5> 128x64
+40 gemm_pipe_kernel<1,5,4,2,5> 64x160
+41 gemm_pipe_kernel<1,4,4,2,5> 64x128
+42 gemm_pipe_kernel<1,2,4,2,6> 64x64
+44 gemm_pipe_kernel<4,8,4,2,2> 256x256
+45 gemm_pipe_kernel<2,4,4,2,2> 128x128 x2/CU
+46 gemm_phase_kernel<8,4> 256x256
+47 gemm_phase_kernel<8,5> 256x320
+"""
+
+
+def test_the_tile_table_carries_the_pinned_names():
+    """lgd_gemm_tile enumerated to its end: unique codes, the block shape its name states, LGD_ERR_ARG past the end, and
+    the 29 (code, name) pairs byte for byte; ops.TILE_NAMES is that table in code order."""
+    import ctypes as C
+    from lgd_amd import _lib
+    lib = _lib.load()
+    code, bm, bn, name, rows = C.c_int(), C.c_int(), C.c_int(), C.create_string_buffer(128), []
+    while lib.lgd_gemm_tile(len(rows), C.byref(code), C.byref(bm), C.byref(bn), name, len(name)) == 0:
+        assert len(name.value) < len(name) - 1
+        rows.append((code.value, bm.value, bn.value, name.value.decode()))
+    for bad in (-1, len(rows), len(rows) + 5):
+        assert lib.lgd_gemm_tile(bad, C.byref(code), C.byref(bm), C.byref(bn), name, len(name)) == -1, bad
+    assert lib.lgd_gemm_tile(0, None, None, None, None, 0) == 0                   # every output is optional
+    short = C.create_string_buffer(b"#" * 8, 8)
+    assert lib.lgd_gemm_tile(0, None, None, None, short, 5) == 0
+    assert short.raw[:5] == rows[0][3].encode()[:4] + b"\0" and short.raw[5:] == b"###"
+    pinned = [ln.split(" ", 1) for ln in PINNED_TILE_NAMES.strip().splitlines()]
+    assert len(pinned) == 29 and sorted((c, nm) for c, _, _, nm in rows) == [(int(c), nm) for c, nm in pinned]
+    assert list(ops.TILE_NAMES.items()) == [(int(c), nm) for c, nm in pinned]
+    for c, m, n, nm in rows:
+        assert nm.split(" ")[1] == f"{m}x{n}", (c, nm)
+
+
 def test_acceptance_floors():
     """No code and no form may drop out of the matrix unnoticed: the minima of the pinned table."""
     pinned = gcc.pinned()

@@ -56,6 +56,30 @@ def test_the_table_reaches_every_code():
     assert header == set(ops.GN_VARIANTS), header ^ set(ops.GN_VARIANTS)
 
 
+# the names the profiles and the gate messages carry, pinned: code, then the kernel instantiation(s) the code launches
+PINNED_VARIANTS = """
+104 gn_fused_kernel<4>
+108 gn_fused_kernel<8>
+116 gn_fused_kernel<16>
+132 gn_fused_kernel<32>
+201 gn_stats_kernel + gn_apply_kernel, one channel pass
+202 gn_stats_kernel + gn_apply_kernel, two channel passes
+300 gn_bwd_slab_kernel<256, 8, false>
+301 gn_bwd_slab_kernel<256, 8, true>
+310 gn_bwd_slab_kernel<512, 11, false>
+311 gn_bwd_slab_kernel<512, 11, true>
+400 gn_bwd_stats_kernel + gn_bwd_apply_kernel
+"""
+
+
+def test_the_variant_names_are_the_pinned_ones():
+    """ops.GN_VARIANTS is read from the library's table (lgd_norm_variant; tests/test_layernorm_contract_cpu.py compares
+    the whole table with the header): the 11 (code, name) pairs, byte for byte."""
+    pinned = [ln.split(" ", 1) for ln in PINNED_VARIANTS.strip().splitlines()]
+    assert list(ops.GN_VARIANTS.items()) == [(int(c), nm) for c, nm in pinned]
+    assert isinstance(ops.GN_VARIANTS, dict) and len(pinned) == 11
+
+
 _HWS = sorted(set(range(1, 42)) | {48, 63, 64, 65, 100, 136, 137, 200, 201, 255, 256, 257, 288, 300, 408, 409, 420, 512, 561, 562,
                                    576, 700, 1024, 1122, 1123, 2048, 4095, 4096})
 

@@ -1,6 +1,6 @@
-"""LayerNorm on the view forms the engine launches, for every kernel layernorm_launch (csrc/norm.hip) can pick:
-layernorm_rows_kernel<1,4> (C <= 512), <2,4> (C <= 1024), <3,2> (C <= 1536), layernorm_kernel (C = 2560), the ln_stats_kernel
-lane widths 8 / 16 / 32 / 64 under "ln_stream" = 1 (and the row kernels in their place under 0), and layernorm_bwd_kernel.
+"""LayerNorm on the view forms the engine launches, for every kernel instantiation of the LayerNorm dispatch (ops.LN_VARIANTS):
+before each launch the case asserts the code ops.layernorm_plan answers for it, and the last test of the module asserts that
+the cases together claimed every code.
 
 Forms: the GLIGEN fuser's — B = 3 images of S = 100 rows, x contiguous (x_bs = S C), y at the head of an [S + 30][ldy] block
 per image with ldy wider than C (a workgroup's rows straddle two images; the 30 preset grounding rows and the pad columns
@@ -36,6 +36,17 @@ NAN = float("nan")
 EPS = 1e-5
 WIDTHS = [64, 320, 640, 1280, 1536, 2560]
 B, S, TAIL = 3, 100, 30
+ROW_CODE = {64: 514, 320: 514, 640: 524, 1280: 532, 1536: 532, 2560: 550}        # the row kernels, the wave kernel at 2560
+STREAM_CODE = {64: 608, 320: 608, 640: 616, 1280: 632, 1536: 664, 2560: 664}     # ln_stats_kernel: 8 / 16 / 32 / 64 lanes per row
+BWD_CODE = 700
+CLAIMED = set()
+
+
+def _claim(code, op, rows, C):
+    """The library answers `code` for the launch that follows (under the current option state)."""
+    got = ops.layernorm_plan(op, rows, C)
+    assert got == code, (op, rows, C, got, ops.LN_VARIANTS.get(got))
+    CLAIMED.add(code)
 
 
 def _bits(t):
@@ -107,6 +118,7 @@ def test_layernorm_fuser_form(dev, C):
 
     def launch():
         out, st = yc.fresh(), sc.fresh()
+        _claim(ROW_CODE[C], ops.LN_OP_FWD, rows, C)
         ops.layernorm(xc.ptr(), gamma_t, bc.ptr(), EPS, out=yc.ptr(out), ldy=ldy, stats=sc.ptr(st), rows_per_batch=S,
                       x_bs=S * C, y_bs=(S + TAIL) * ldy, rows=rows, ldx=C)
         return out, st
@@ -131,6 +143,7 @@ def test_layernorm_fuser_form(dev, C):
     outs = []
     for pair in (0, ops.PAIR_HALF):
         o = yc4.fresh()
+        _claim(ROW_CODE[C], ops.LN_OP_FWD, 4 * S, C)            # chosen for the full call's rows, with and without pair
         ops.layernorm(xc4.ptr(), gamma_t, bc.ptr(), EPS, out=yc4.ptr(o), ldy=ldy, rows_per_batch=S, x_bs=S * C + 16,
                       y_bs=S * ldy + 8, rows=4 * S, ldx=C, pair=pair)
         assert yc4.outside_untouched(o)
@@ -145,12 +158,13 @@ def test_layernorm_fuser_form(dev, C):
 @pytest.mark.parametrize("stream", [0, 1])
 @pytest.mark.parametrize("C", WIDTHS)
 def test_layernorm_statistics_only(dev, C, stream):
-    """y = NULL: the row kernels (ln_stream = 0, C <= 1536; ln_stream = 1 below 8 M elements) and ln_stats_kernel with 8 /
-    16 / 32 / 64 lanes per row (ln_stream = 1 from 8 M elements, and always at C = 2560), at a row stride wider than C and a
-    row count that is no multiple of any kernel's rows per workgroup."""
+    """y = NULL, at a row stride wider than C and row counts that are no multiple of any kernel's rows per workgroup, one
+    below and one above the 8 M elements from which "ln_stream" = 1 takes ln_stats_kernel (C = 2560: at every size)."""
     if stream == 0 and C > 1536:                   # the row kernels hold three vectors per lane: refused, not served
         ops.set_option("ln_stream", 0)
         try:
+            with pytest.raises(RuntimeError):
+                ops.layernorm_plan(ops.LN_OP_STATS, 8, C)
             with pytest.raises(RuntimeError):
                 ops.layernorm_stats(torch.zeros(8, C, device=dev, dtype=H16), C)
         finally:
@@ -165,6 +179,8 @@ def test_layernorm_statistics_only(dev, C, stream):
             xc = Carved(x, (C + 16, 1), NAN, H16, dev)
             sc = Carved(torch.full((rows, 2), SENT32, dtype=F64), (2, 1), SENT32, F32, dev)
             st = sc.fresh()
+            streams = stream and (rows * C >= 8 << 20 or C > 1536)
+            _claim((STREAM_CODE if streams else ROW_CODE)[C], ops.LN_OP_STATS, rows, C)
             ops.layernorm_stats(xc.ptr(), C, EPS, stats=sc.ptr(st), rows=rows, ldx=C + 16)
             assert sc.outside_untouched(st), "a guard of the statistics was written"
             stats = sc.logical(st)
@@ -201,6 +217,7 @@ def test_layernorm_bwd_fuser_form(dev, C, accumulate):
 
     def launch():
         out = gxc.fresh()
+        _claim(BWD_CODE, ops.LN_OP_BWD, rows, C)
         ops.layernorm_bwd(gyc.ptr(), xc.ptr(), gamma_t, sc.ptr(), gx=gxc.ptr(out), rows=rows, ldgy=ldgy, ldx=C, ldgx=C,
                           rows_per_batch=S, gy_bs=(S + TAIL) * ldgy, x_bs=S * C, gx_bs=S * C + 24, accumulate=accumulate)
         return out
@@ -209,3 +226,9 @@ def test_layernorm_bwd_fuser_form(dev, C, accumulate):
     r = _ratio(gxc.logical(out).reshape(rows, C), ref, bound, "gx")
     assert torch.equal(_bits(launch()), _bits(out)), "a second launch is not bit-identical"
     gate(f"layernorm backward fuser form C={C} accumulate={accumulate}: max error / derived bound", r, 1.0)
+
+
+def test_the_cases_claimed_every_code():
+    """Runs last: the cases above asserted, launch by launch, the code the library answers; together they reach every row of
+    the LayerNorm variant table."""
+    assert CLAIMED == set(ops.LN_VARIANTS), sorted(CLAIMED ^ set(ops.LN_VARIANTS))
