@@ -606,6 +606,48 @@ int lgd_detect_nms_f32(int mode, const float* logits_or_scores, const float* box
                        int class_aware, float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_index,
                        int32_t* out_count, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mask refinement around the SAM network for a batch of (image, prompt) items (additive exports: LGD_ABI_VERSION stays
+ * 12) — models/sam.py as generation/lmd_plus.py:122-130 and generation/lmd.py:124-149 call it, everything that follows
+ * the model's logits and, for LMD, everything that precedes its point prompt, without a host read.
+ * ------------------------------------------------------------------------------------------- */
+/* Low-resolution mask logits -> the selected mask on the latent grid: models/sam.py:45-55 (`post_process_masks` of the
+ * [ext] SamImageProcessor: bilinear to target x target, crop to the resized size, bilinear to the original size, > 0; then
+ * F.interpolate(.float(), (H, W), mode="bilinear").bool()), :63-65 (get_iou_with_resize), :67-111 (select_mask, rule
+ * "largest_over_conf") and the per-box part of :182-213 (sam_refine_boxes).
+ *   logits: fp32 [N][K][S][S] (pred_masks of the model, S = 256 for sam-vit-base); iou: fp32 [N][K], the model's predicted
+ *   IoUs — item n is scored with ITS row (the reference's sam() hands out row 0 of image 0; its plugins call with one
+ *   image and one prompt); geom: int32 [N][4] = {h, w, nh, nw}, original and resized (unpadded) image size per item —
+ *   items of different sizes may share a launch, a row outside 1 <= nh, nw <= target is clamped into it; target: the
+ *   model's input side; coarse: uint8 [N][hc][wc], non-zero = inside.
+ *   Every resampling is torch's upsample_bilinear2d with align_corners=False in fp32: src = (in / out) (dst + 0.5) - 0.5,
+ *   clamped at 0; i1 = i0 + (i0 < in - 1); value = l0h (l0w a + l1w b) + l1h (l0w c + l1w d), evaluated without
+ *   contraction.  Step 3 (0 / 1 image at h x w -> H x W) keeps `!= 0`; when (hc, wc) != (H, W) the candidates are
+ *   resampled once more to hc x wc and kept where > 0 before they meet the coarse mask.  Counts are integers;
+ *   IoU_k = inter_k / (union_k + 1e-6) in fp64; score_k = area_k - max(area) [iou[n][k] < (float)below_conf]
+ *   - max(area) [IoU_k < below_iou]; the first maximum wins.
+ *   cand: uint8 [N][K][H][W] (0 / 1) or NULL; mask: uint8 [N][H][W], the winning candidate; conf: fp32 [N] =
+ *   iou[n][pick]; stats: int32 [N][1 + 3K] = {pick, area_k.., inter_k.., union_k..} (area on H x W, the other two on
+ *   hc x wc); workspace: 12 N K H bytes, plus N K H W when cand is NULL, 4-byte aligned.
+ * Two launches, no atomics, deterministic: one wave per (row block, candidate, item), then one workgroup per item.
+ * LGD_ERR_ARG: a NULL operand other than cand, K > 4, a size <= 0, fp32 / int32 operands not 4-byte aligned.
+ * LGD_ERR_UNSUPPORTED: H, W, hc or wc > 4096, S or target > 32768, N > 65535. */
+int lgd_sam_mask_tail_f32(const float* logits, const float* iou, const int32_t* geom, const uint8_t* coarse, int N,
+                          int K, int S, int target, int H, int W, int hc, int wc, double below_conf,
+                          double below_iou, uint8_t* cand, uint8_t* mask, float* conf, int32_t* stats, void* workspace,
+                          void* stream);
+/* LMD's prompt from the object token's attention map: models/sam.py:125-147 with use_box_input=False (scipy.ndimage
+ * .gaussian_filter, the arg-max as the point prompt) and :113-122 (preprocess_mask without erosion: min-max normalise,
+ * > mask_th).  The smoothing is scipy's with its defaults: separable, axis 0 then axis 1, radius int(4 sigma + 0.5),
+ * weights exp(-x^2 / 2 sigma^2) normalised to sum 1, mode `reflect` (d c b a | a b c d | d c b a) at any distance.
+ *   attn: fp32 [N][hm][wm]; coarse: uint8 [N][hm][wm] (0 / 1); points: fp32 [N][2] = {peak_x * up_h, peak_y * up_w} of
+ *   the first maximum in raster order — up_w = height / wm and up_h = width / hm, the reference's swapped naming
+ *   (:135,:146) kept; smooth: fp32 [N][hm][wm], the filtered map, or NULL.  One workgroup per item, fp32 in LDS.
+ * LGD_ERR_ARG: NULL attn / coarse / points, a size or scale <= 0, sigma <= 0.  LGD_ERR_UNSUPPORTED: hm * wm > 4096 (a
+ * 64 x 64 map), radius > 64, N > 65535.  The box branch (use_box_input=True) needs an erosion and stays on the host. */
+int lgd_sam_attn_prompt_f32(const float* attn, int N, int hm, int wm, float sigma, float mask_th, int up_w, int up_h,
+                            uint8_t* coarse, float* points, float* smooth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

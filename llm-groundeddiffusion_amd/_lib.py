@@ -48,7 +48,7 @@ EPI_GEGLU, EPI_OUT_F32, EPI_RES_F32, EPI_ROWNORM = 1, 2, 4, 8
 PAIR_HALF, PAIR_DUP = 1, 2      # CFG pair modes (LgdGemmDesc.pair, lgd_*_pair_f16)
 
 # name -> argtypes (every function returns int; the last argument of a launching call is the hipStream_t)
-_P, _I, _L, _F = c_void_p, c_int, c_i64, c_float
+_P, _I, _L, _F, _D = c_void_p, c_int, c_i64, c_float, C.c_double
 SIGNATURES = {
     "lgd_abi_version": [],
     "lgd_set_option": [C.c_char_p, _I],
@@ -105,6 +105,8 @@ SIGNATURES = {
     "lgd_boxdiff_energy_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
     "lgd_owl_heads_f32": [_P, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgd_detect_nms_f32": [_I, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P],
+    "lgd_sam_mask_tail_f32": [_P, _P, _P, _P] + [_I] * 8 + [_D, _D] + [_P] * 6,
+    "lgd_sam_attn_prompt_f32": [_P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P],
 }
 
 _lib = None

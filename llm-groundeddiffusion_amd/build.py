@@ -13,13 +13,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblgd_hip.so")
 STAMP = OUT + ".stamp"
-SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "attn_w4.hip", "attn_bwd.hip", "misc.hip", "energy.hip", "boxdiff.hip", "sam.hip", "options.hip", "detect.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "attn_w4.hip", "attn_bwd.hip", "misc.hip", "energy.hip", "boxdiff.hip", "sam.hip", "options.hip", "detect.hip", "sam_tail.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-Wno-unused-value"]
 # Per-file extras.  The attention kernels run softmax VALU work on MFMA results every key tile: keep
 # the accumulators in VGPRs (not AGPRs) so that no v_accvgpr_read/write traffic is generated.
 EXTRA_FLAGS = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               # the resampling chain reproduces torch's bilinear arithmetic term for term: no fused multiply-adds
+               "sam_tail.hip": ["-ffp-contract=off"]}
 
 
 def _digest():

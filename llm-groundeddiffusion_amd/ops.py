@@ -959,3 +959,46 @@ def detect_nms(scores_or_logits, boxes, *, labels=None, counts=None, score_thres
     _call("lgd_detect_nms_f32", mode, _p(scores_or_logits), _p(boxes), _p(labels), _p(counts), B, P, Q,
           float(score_threshold), float(nms_threshold), 1 if class_aware else 0, *(_p(t) for t in out), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# mask refinement around the SAM network (csrc/sam_tail.hip)
+# ---------------------------------------------------------------------------------------------
+def sam_mask_tail(logits, iou, geom, target, grid, coarse, below_conf, below_iou, *, want_cand=True):
+    """SAM's low-resolution logits -> the selected latent-grid mask of every item (lgd_sam_mask_tail_f32).  logits fp32
+    [N, K, S, S], iou fp32 [N, K], geom int32 [N, 4] = (h, w, nh, nw), coarse uint8 / bool [N, hc, wc], grid = (H, W) ->
+    (mask uint8 [N, H, W], conf fp32 [N], stats int32 [N, 1 + 3K], cand uint8 [N, K, H, W] or None)."""
+    N, K, S = logits.shape[:3]
+    H, W = int(grid[0]), int(grid[1])
+    dev = logits.device
+    if coarse.dtype == torch.bool:
+        coarse = coarse.view(torch.uint8)
+    if (logits.dtype != F32 or iou.dtype != F32 or geom.dtype != torch.int32 or coarse.dtype != torch.uint8
+            or logits.dim() != 4 or logits.shape[3] != S or tuple(iou.shape) != (N, K) or tuple(geom.shape) != (N, 4)
+            or coarse.dim() != 3 or coarse.shape[0] != N):
+        raise RuntimeError("sam_mask_tail: logits fp32 [N,K,S,S], iou fp32 [N,K], geom int32 [N,4], coarse uint8 [N,hc,wc]")
+    if not (logits.is_contiguous() and iou.is_contiguous() and geom.is_contiguous() and coarse.is_contiguous()):
+        raise RuntimeError("sam_mask_tail: contiguous operands")
+    mask = torch.empty((N, H, W), device=dev, dtype=torch.uint8)
+    conf = torch.empty((N,), device=dev, dtype=F32)
+    stats = torch.empty((N, 1 + 3 * K), device=dev, dtype=torch.int32)
+    cand = torch.empty((N, K, H, W), device=dev, dtype=torch.uint8) if want_cand else None
+    ws = torch.empty((3 * N * K * H + (0 if want_cand else (N * K * H * W + 3) // 4),), device=dev, dtype=torch.int32)
+    _call("lgd_sam_mask_tail_f32", _p(logits), _p(iou), _p(geom), _p(coarse), N, K, S, int(target), H, W,
+          coarse.shape[1], coarse.shape[2], float(below_conf), float(below_iou), _p(cand), _p(mask), _p(conf), _p(stats),
+          _p(ws), _stream())
+    return mask, conf, stats, cand
+
+
+def sam_attn_prompt(attn, sigma, mask_th, up_w, up_h, *, want_smooth=False):
+    """LMD's point prompt and coarse mask from the object token's attention maps (lgd_sam_attn_prompt_f32).  attn fp32
+    [N, hm, wm] -> (coarse uint8 [N, hm, wm], points fp32 [N, 2] = (peak_x * up_h, peak_y * up_w), smoothed map or None)."""
+    if attn.dtype != F32 or attn.dim() != 3 or not attn.is_contiguous():
+        raise RuntimeError("sam_attn_prompt: attn is a contiguous fp32 [N, hm, wm] tensor")
+    N, hm, wm = attn.shape
+    coarse = torch.empty((N, hm, wm), device=attn.device, dtype=torch.uint8)
+    points = torch.empty((N, 2), device=attn.device, dtype=F32)
+    smooth = torch.empty_like(attn) if want_smooth else None
+    _call("lgd_sam_attn_prompt_f32", _p(attn), N, hm, wm, float(sigma), float(mask_th), int(up_w), int(up_h), _p(coarse),
+          _p(points), _p(smooth), _stream())
+    return coarse, points, smooth

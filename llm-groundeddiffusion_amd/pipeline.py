@@ -133,15 +133,16 @@ def _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_onl
             saved[k] = m.flatten(3, 4)
 
 
-def _token_attn(saved, start):
+def _token_attn(saved, start, on_device=False):
     """utils/attn.py:9-38 (get_token_attnv2 with input_ca_has_condition_only, one saved token): mean over heads and over
-    the steps from `start` on of the object token's map at OBJ_ATTN_KEY -> numpy [side, side]."""
+    the steps from `start` on of the object token's map at OBJ_ATTN_KEY -> numpy [side, side] (on_device: the tensor)."""
     m = saved[OBJ_ATTN_KEY][start:, 0, :, :, 0]
     if m.shape[0] == 0:
         raise RuntimeError(f"no saved attention at or after step {start}")
     mean = m.float().mean(dim=(0, 1))
     side = int(round(mean.numel() ** 0.5))
-    return mean.reshape(side, side).cpu().numpy()
+    mean = mean.reshape(side, side)
+    return mean if on_device else mean.cpu().numpy()
 
 
 def _so_mask(refiner, kind, image, box, L, token_attn=None):
@@ -155,6 +156,14 @@ def _so_mask(refiner, kind, image, box, L, token_attn=None):
         raise RuntimeError("mask refinement needs the decoded single-object images (decode=True)")
     mask, _conf = refiner.box(image, box) if kind == "box" else refiner.attn(image, token_attn)
     return torch.as_tensor(mask).bool()
+
+
+def _batched(refiner, kind):
+    """Whether the refiner takes all boxes in one call (SamRefiner.boxes / .attns) or one at a time (.box / .attn).  The
+    box prompt of an attention map (`use_box_input`) is always made per image."""
+    if refiner is None or not getattr(refiner, "batched", False):
+        return False
+    return kind == "box" or not getattr(refiner, "attn_kw", {}).get("use_box_input", False)
 
 
 def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule,
@@ -173,22 +182,29 @@ def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ra
     return L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps
 
 
-def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, **denoise_kw):
+def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, masks_of=None, **denoise_kw):
     """One generation per box (job_of(layout, its index, box index, box)), all boxes of all layouts as one batched
     denoising call -> per layout the histories, saved maps, foreground masks (mask_of(decoded image or None, box, result)),
-    decoded images and guidance iteration counts of its boxes."""
+    decoded images and guidance iteration counts of its boxes.  masks_of(decoded uint8 batch on the device, boxes,
+    results) -> all masks (n, L, L) at once: the batched refinement, enqueued before the images go to the host."""
     owner = [(li, i) for li in range(len(lays)) for i in range(len(so_boxes[li]))]
     jobs = [job_of(lays[li], li, i, so_boxes[li][i]) for li, i in owner]
     res_a = sampler.denoise_batch(jobs, T, return_cond_ca_only=True, **denoise_kw) if jobs else []
     per_lay = [dict(latents_all=[], masks=[], saved=[], so_images=[], guidance_iters=[]) for _ in lays]
+    masks = None
     if decode and res_a:
-        imgs = sampler.decode(torch.cat([r["latents"] for r in res_a]))      # feeds SAM in the reference
+        imgs = sampler.decode_device(torch.cat([r["latents"] for r in res_a]))      # feeds SAM in the reference
+        if masks_of is not None:
+            masks = masks_of(imgs, [so_boxes[li][i] for li, i in owner], res_a)
+        imgs = imgs.cpu().numpy()
+        if masks is not None:
+            masks = torch.as_tensor(masks).bool().cpu()           # the composition (hostprep.compose) is host code
     for n, ((li, i), r) in enumerate(zip(owner, res_a)):
         d = per_lay[li]
         d["latents_all"].append(r["latents_all"])
         d["saved"].append(r["saved"])
         d["guidance_iters"].append(r["guidance_iters"])
-        d["masks"].append(mask_of(imgs[n] if decode else None, so_boxes[li][i], r))
+        d["masks"].append(masks[n] if masks is not None else mask_of(imgs[n] if decode else None, so_boxes[li][i], r))
         if decode:
             d["so_images"].append(imgs[n:n + 1])
     return per_lay
@@ -272,8 +288,12 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
     def overall_gligen(lay):
         flat = [i for grp in lay.overall_groups for i in grp]
         return prepare_gligen_condition([list(lay.boxes[i]) for i in flat], lay.phrase_embeddings[flat], dev)
+
+    def so_masks(images, boxes, res):                        # one SAM pass for all boxes of all layouts
+        return mask_refiner.boxes(images, boxes)[0]
     per_lay = _stage_a(sampler, lays, so_boxes if use_ref_ca or frozen_steps > 0 else [[]] * len(lays), T, decode, so_job,
                        lambda image, box, r: _so_mask(mask_refiner, "box", image, box, L),
+                       so_masks if _batched(mask_refiner, "box") else None,
                        guidance_scale=guidance_scale, use_gligen=True,
                        gligen_scheduled_sampling_beta=so_gligen_scheduled_sampling_beta,
                        saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys] if use_ref_ca else [OBJ_ATTN_KEY],
@@ -327,7 +347,12 @@ def lmd_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num_inf
     def so_mask(image, box, r):
         return _so_mask(mask_refiner, "attn", image, box, L,
                         token_attn=_token_attn(r["saved"], attn_aggregation_step_start) if mask_refiner else None)
-    per_lay = _stage_a(sampler, lays, so_boxes, T, decode, so_job, so_mask, guidance_scale=guidance_scale,
+
+    def so_masks(images, boxes, res):                        # one SAM pass for all boxes of all layouts
+        maps = torch.stack([_token_attn(r["saved"], attn_aggregation_step_start, on_device=True) for r in res])
+        return mask_refiner.attns(images, maps)[0]
+    per_lay = _stage_a(sampler, lays, so_boxes, T, decode, so_job, so_mask, so_masks if _batched(mask_refiner, "attn") else None,
+                       guidance_scale=guidance_scale,
                        saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys], fast_after_steps=fast_after)
     return _stage_b(
         sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only, use_ref_ca,

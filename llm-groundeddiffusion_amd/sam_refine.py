@@ -45,32 +45,50 @@ class DeviceSamProcessor:
         self.dev, self.target = torch.device(device), int(longest_edge)
         self.image_processor = self
         self.on_device = True
+        self._mean = torch.tensor(self.MEAN, device=self.dev).view(1, 3, 1, 1)
+        self._std = torch.tensor(self.STD, device=self.dev).view(1, 3, 1, 1)
 
     def _shape(self, h, w):
         scale = self.target / max(h, w)
         return int(h * scale + 0.5), int(w * scale + 0.5)
 
+    def _resize(self, t):
+        """uint8 (n, h, w, 3) on the device -> normalised, padded fp32 (n, 3, target, target) and the resized size."""
+        h, w = int(t.shape[1]), int(t.shape[2])
+        nh, nw = self._shape(h, w)
+        r = F.interpolate(t.permute(0, 3, 1, 2).float(), (nh, nw), mode="bilinear", align_corners=False,
+                          antialias=(nh < h or nw < w)).round().clamp(0, 255)
+        r = (r / 255.0 - self._mean) / self._std
+        return F.pad(r, (0, self.target - nw, 0, self.target - nh)), (nh, nw)
+
+    def pixels(self, images):
+        """One HxWx3 image, a list of them, a stacked (N, h, w, 3) array or a uint8 tensor (N, h, w, 3), on the host or
+        already on the device -> (pixel_values (N, 3, target, target), [[h, w]] * N, [[nh, nw]] * N).  Images of one size
+        are resized in one call; the result per image does not depend on what it shares the call with."""
+        if torch.is_tensor(images):
+            batch = images[None] if images.dim() == 3 else images
+        elif isinstance(images, np.ndarray):
+            batch = torch.as_tensor(np.ascontiguousarray(images[None] if images.ndim == 3 else images))
+        else:
+            imgs = [im if torch.is_tensor(im) else torch.as_tensor(np.ascontiguousarray(im)) for im in images]
+            if len({tuple(im.shape) for im in imgs}) != 1:        # mixed sizes (or none): one call per image
+                if not imgs:
+                    raise ValueError("images must be HxWx3 arrays")
+                parts = [self.pixels(im) for im in imgs]
+                return torch.cat([p[0] for p in parts]), [p[1][0] for p in parts], [p[2][0] for p in parts]
+            batch = torch.stack(imgs) if imgs[0].dim() == 3 else None
+        if batch is None or batch.dim() != 4 or batch.shape[3] != 3:
+            raise ValueError("images must be HxWx3 arrays")
+        px, (nh, nw) = self._resize(batch.to(self.dev))
+        n, h, w = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+        return px, [[h, w]] * n, [[nh, nw]] * n
+
     def __call__(self, images, input_points=None, input_labels=None, input_boxes=None, return_tensors="pt", **_kw):
-        imgs = [images] if isinstance(images, np.ndarray) and images.ndim == 3 else list(images)
-        mean = torch.tensor(self.MEAN, device=self.dev).view(1, 3, 1, 1)
-        std = torch.tensor(self.STD, device=self.dev).view(1, 3, 1, 1)
-        px, orig, resh = [], [], []
-        for im in imgs:
-            t = torch.as_tensor(np.ascontiguousarray(im)).to(self.dev)
-            if t.dim() != 3 or t.shape[2] != 3:
-                raise ValueError("images must be HxWx3 arrays")
-            h, w = int(t.shape[0]), int(t.shape[1])
-            nh, nw = self._shape(h, w)
-            r = F.interpolate(t.permute(2, 0, 1)[None].float(), (nh, nw), mode="bilinear", align_corners=False,
-                              antialias=(nh < h or nw < w)).round().clamp(0, 255)
-            r = (r / 255.0 - mean) / std
-            px.append(F.pad(r, (0, self.target - nw, 0, self.target - nh)))
-            orig.append([h, w])
-            resh.append([nh, nw])
-        enc = _Encoding(pixel_values=torch.cat(px), original_sizes=torch.tensor(orig), reshaped_input_sizes=torch.tensor(resh))
+        pixel_values, orig, resh = self.pixels(images)
+        enc = _Encoding(pixel_values=pixel_values, original_sizes=torch.tensor(orig), reshaped_input_sizes=torch.tensor(resh))
 
         def scaled(prompts, box):
-            if len(prompts) != len(imgs):
+            if len(prompts) != len(orig):
                 sizes = [(orig[0], resh[0])] * len(prompts)
             else:
                 sizes = list(zip(orig, resh))
@@ -231,15 +249,35 @@ def sam_refine_box(sam_input_image, box, *args, **kwargs):
     return masks[0][0], confs[0][0]
 
 
+def _upload(t, dev):
+    """Host tensor -> device without stalling the stream (pinned staging, asynchronous copy); device tensors pass."""
+    if t.device == dev or dev.type != "cuda" or t.is_cuda:
+        return t.to(dev)
+    return t.pin_memory().to(dev, non_blocking=True)
+
+
 class SamRefiner:
     """What the generation pipelines (lgd_amd.pipeline) call per generated single-object image: the arguments the
     reference's plugins put into `sam_refine_kwargs` (generation/lmd_plus.py:320-327, generation/lmd.py:354-366), bound
-    once."""
+    once.
+
+    `box` / `attn` refine one image, with host work between the processor, the model and the selection.  `boxes` /
+    `attns` refine a batch in one pass that stays on the device: processor -> HipSamModel in chunks of at most
+    MODEL_CHUNK images -> ops.sam_mask_tail (for `attns`, ops.sam_attn_prompt first).  They need the device processor.
+    `batched` tells the pipelines which pair to call: None = on exactly when the processor is `DeviceSamProcessor`
+    (measured faster there), False = the per-image path only.  `attns` covers the point prompt; with
+    `use_box_input` the attention maps go through `attn` whatever `batched` says (the box prompt needs an erosion, which
+    is host code).  Each item is scored with its own predicted IoUs."""
+    MODEL_CHUNK = 8
 
     def __init__(self, sam_model_dict, height=512, width=512, discourage_mask_below_confidence=0.85,
                  discourage_mask_below_coarse_iou=0.25, use_box_input=False, gaussian_sigma=None, mask_th_for_box=0.05,
-                 n_erode_dilate_mask_for_box=1, mask_th_for_point=0.25, verbose=False):
+                 n_erode_dilate_mask_for_box=1, mask_th_for_point=0.25, verbose=False, batched=None):
         self.md, self.verbose = sam_model_dict, verbose
+        on_device = bool(getattr(sam_model_dict["sam_processor"], "on_device", False))
+        if batched and not on_device:
+            raise ValueError("batched refinement needs the device processor (wrap_sam(..., sam_processor='device'))")
+        self.batched = on_device if batched is None else bool(batched)
         self.common = dict(height=height, width=width, H=height // 8, W=width // 8,
                            discourage_mask_below_confidence=discourage_mask_below_confidence,
                            discourage_mask_below_coarse_iou=discourage_mask_below_coarse_iou)
@@ -256,3 +294,63 @@ class SamRefiner:
         """LMD (generation/lmd.py:141-147) -> (bool mask [H/8, W/8], confidence)."""
         return sam_refine_attn(sam_input_image=image, token_attn_np=token_attn_np, model_dict=self.md,
                                verbose=self.verbose, **self.attn_kw, **self.common)
+
+    # ---- a batch in one pass, on the device
+    def _device_processor(self):
+        processor = self.md["sam_processor"]
+        if not getattr(processor, "on_device", False):
+            raise RuntimeError("boxes() / attns() need the device processor; use box() / attn() with the Hugging Face one")
+        return processor
+
+    def _tail(self, images, coarse, **prompt):
+        """processor -> model (chunks of MODEL_CHUNK) -> mask tail.  coarse: uint8 (N, hc, wc) on the device; prompt:
+        `input_boxes=` (N, 1, 4) or `input_points=` (N, 1, 1, 2) in pixels of the ORIGINAL image, device or host."""
+        from . import ops
+        model, processor = self.md["sam_model"], self._device_processor()
+        pixel_values, orig, resh = processor.pixels(images)
+        N, dev = pixel_values.shape[0], pixel_values.device
+        if coarse.shape[0] != N:
+            raise ValueError(f"{N} images but {coarse.shape[0]} prompts")
+        # one upload, in front of the model: the tail's geometry rows and the prompt scaling of processing_sam.py
+        # `_normalize_coordinates` (x * new_w / old_w, y * new_h / old_h, in fp64)
+        meta = _upload(torch.tensor([[h, w, nh, nw, nw / w, nh / h] for (h, w), (nh, nw) in zip(orig, resh)],
+                                    dtype=torch.float64), dev)
+        geom, ratio = meta[:, :4].to(torch.int32), meta[:, 4:]
+        (name, p), = prompt.items()
+        p = _upload(p, dev).to(torch.float64)
+        p = (p.reshape(N, -1, 2) * ratio[:, None]).reshape(p.shape).float()
+        logits, iou = [], []
+        for c0 in range(0, N, self.MODEL_CHUNK):
+            out = model(pixel_values=pixel_values[c0:c0 + self.MODEL_CHUNK], **{name: p[c0:c0 + self.MODEL_CHUNK]})
+            logits.append(out.pred_masks[:, 0].float())
+            iou.append(out.iou_scores[:, 0].float())
+        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        iou = iou[0] if len(iou) == 1 else torch.cat(iou)
+        mask, conf, _stats, _cand = ops.sam_mask_tail(
+            logits.contiguous(), iou.contiguous(), geom, processor.target, (self.common["H"], self.common["W"]), coarse,
+            self.common["discourage_mask_below_confidence"], self.common["discourage_mask_below_coarse_iou"])
+        return mask.bool(), conf
+
+    def boxes(self, images, boxes):
+        """LMD+ for N (image, box) pairs: images uint8 (N, h, w, 3) (a device tensor, or anything the processor takes),
+        boxes N (x0, y0, x1, y1) proportions -> (bool masks (N, H/8, W/8), confidences fp32 (N)), both on the device."""
+        dev = self._device_processor().dev
+        height, width, H, W = (self.common[k] for k in ("height", "width", "H", "W"))
+        pixel = np.array([hostprep.scale_proportion(b, H=height, W=width) for b in boxes], dtype=np.float64)
+        coarse = np.stack([hostprep.proportion_to_mask(b, H, W, return_np=True) for b in boxes]).astype(np.uint8)
+        return self._tail(images, _upload(torch.from_numpy(coarse), dev), input_boxes=torch.from_numpy(pixel).reshape(-1, 1, 4))
+
+    def attns(self, images, token_attns):
+        """LMD for N (image, attention map) pairs: token_attns fp32 (N, hm, wm), a device tensor or a list of arrays ->
+        (bool masks (N, H/8, W/8), confidences fp32 (N)), both on the device.  The point-prompt branch only."""
+        from . import ops
+        if self.attn_kw["use_box_input"]:
+            raise NotImplementedError("attns() covers the point prompt; the box prompt of the attention map is attn()'s")
+        dev = self._device_processor().dev
+        if not torch.is_tensor(token_attns):
+            token_attns = torch.from_numpy(np.stack([np.asarray(t, dtype=np.float32) for t in token_attns]))
+        maps = _upload(token_attns, dev).to(torch.float32).contiguous()
+        up_w, up_h = self.common["height"] // maps.shape[2], self.common["width"] // maps.shape[1]     # (w, h) as attn()
+        coarse, points, _ = ops.sam_attn_prompt(maps, self.attn_kw["gaussian_sigma"], self.attn_kw["mask_th_for_point"],
+                                                up_w, up_h)
+        return self._tail(images, coarse, input_points=points.reshape(-1, 1, 1, 2))

@@ -565,6 +565,12 @@ class LMDSampler:
     @torch.no_grad()
     def decode(self, latents: torch.Tensor):
         """pipelines.py:117-127: VAE decode -> uint8 HWC (the VAE is [ext] and stays PyTorch/MIOpen)."""
+        return self.decode_device(latents).cpu().numpy()
+
+    @torch.no_grad()
+    def decode_device(self, latents: torch.Tensor):
+        """decode() without its host copy: the uint8 (N, h, w, 3) batch on the device, for consumers that stay there (the
+        batched mask refinement)."""
         if self.vae is None:
             raise RuntimeError("no VAE attached to the sampler")
         outs = []
@@ -572,4 +578,4 @@ class LMDSampler:
             image = self.vae.decode(latents[c0:c0 + 8] / 0.18215)
             image = (image / 2 + 0.5).clamp(0, 1)
             outs.append((image.detach().float().permute(0, 2, 3, 1) * 255).round().to(torch.uint8))
-        return torch.cat(outs).cpu().numpy()
+        return torch.cat(outs)
