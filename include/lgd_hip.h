@@ -648,6 +648,58 @@ int lgd_sam_mask_tail_f32(const float* logits, const float* iou, const int32_t* 
 int lgd_sam_attn_prompt_f32(const float* attn, int N, int hm, int wm, float sigma, float mask_th, int up_w, int up_h,
                             uint8_t* coarse, float* points, float* smooth, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The hand-off between the two stages of LMD / LMD+ for all layouts of a batch (additive exports: LGD_ABI_VERSION stays
+ * 12; csrc/handoff.hip) — centre-of-mass alignment, painter's-order composition and the reference-map gather as three
+ * launches without a host read.  Boxes are numbered through the batch; `seg`: int32 [NL + 1], layout l owns boxes
+ * seg[l] .. seg[l + 1] - 1.  L (the latent side) must be a multiple of 8, as shift_tensor asserts: else LGD_ERR_ARG.
+ * ------------------------------------------------------------------------------------------- */
+/* Place: utils/latents.py:85-106 (align_with_bboxes), utils/utils.py:102-123 (binary_mask_to_center), :145-180
+ * (shift_tensor's offset rule), :72-100 (binary_mask_to_box / _box_mask) and the ordering of utils/latents.py:52-57
+ * (compose_latents: np.argsort of the negated mask areas).  One workgroup per layout.
+ *   masks: uint8 [NB][L][L], non-zero = inside; targets: fp64 [NB][4], the xyxy box (fractions of the frame) each
+ *   generation will occupy in the overall one.
+ *   plan: int32 [NB][8] = {ox, oy, area, x0, y0, x1, y1, empty}.  Sum m, sum x m and sum y m are exact integers; the centre
+ *   is float(sum x m) / float(sum m), ONE fp32 division (the reference divides torch / numpy fp32 scalars); then in fp64
+ *   c = centre / L, off = (t[0] + t[2]) / 2 - c (y likewise, or 0 with horizontal_only) and ox = rint(off * 8) * (L / 8),
+ *   rint half to even as Python's round.  align == 0: the offsets are 0.  The shifted mask is M(y, x) = m(y - oy, x - ox),
+ *   0 where the source lies outside the frame; `area` counts M; the box is M's bounding box grown by one and clipped as
+ *   binary_mask_to_box does (near side to 0, far side to L; covered pixels are x0 <= x <= x1).  A box whose M is empty
+ *   has empty = 1, area 0, an empty box, and takes no part below (the reference raises ValueError('The mask is empty')
+ *   there; a launch cannot raise without a read).
+ *   win: int32 [NL][2][L][L].  Painter's order = descending area, EQUAL areas lower index first (a choice: np.argsort
+ *   leaves it open).  win[l][0] = the last box in that order whose M covers the pixel, win[l][1] = the last whose grown
+ *   box covers it, as indices inside the layout, -1 where none does.
+ *   max_boxes: the largest box count of a layout (host; what seg holds).  NB == 0 (no layout has a box): the per-box
+ *   tables may be NULL, here and in the composition, and both owner maps are -1 throughout.
+ * LGD_ERR_ARG: NULL operand, NL <= 0, L % 8 != 0, misaligned tables.  LGD_ERR_UNSUPPORTED: max_boxes > 64, L > 1024,
+ * NL > 65535. */
+int lgd_handoff_place(const uint8_t* masks, const double* targets, const int32_t* seg, int NL, int NB, int max_boxes,
+                      int L, int align, int horizontal_only, int32_t* plan, int32_t* win, void* stream);
+/* Compose: utils/latents.py:38-83 (compose_latents with compose_box_to_bg) on the histories shifted as
+ * utils/latents.py:96-100 shifts them (shift_tensor, utils/utils.py:145-180), as ONE gather per output element.
+ *   hist: int64 [NB][2] = {device address of the box's history, fp32 [rows >= steps + 1][C][L][L] with the steps
+ *   `stride` elements apart; that stride} — the histories are views of the denoising batches; bg: fp32 [NL][C][L][L].
+ *   composed: fp32 [NL][steps + 1][C][L][L]; fg_idx: int64 [NL][L][L].  With w = win[l][0] at the pixel: w >= 0 -> every
+ *   step t takes box w's history of step t at (y - oy_w, x - ox_w), fg_idx = w + 1.  Else fg_idx = 0, steps >= 1 are 0 and
+ *   step 0 takes box win[l][1]'s step-0 latent at its shifted source — 0 where that lies outside the frame — or bg where
+ *   no grown box covers the pixel.
+ *   aligned: fp32 [NB][rows][C][L][L] or NULL — the shifted histories themselves, zero filled (what align_with_bboxes
+ *   returns); `rows` is read only with it.
+ * One thread per output element; every element is written.  LGD_ERR_ARG / LGD_ERR_UNSUPPORTED as above. */
+int lgd_handoff_compose_f32(const int32_t* plan, const int32_t* win, const int32_t* seg, const int64_t* hist,
+                            const float* bg, int NL, int NB, int steps, int C, int L, int rows, float* composed,
+                            int64_t* fg_idx, float* aligned, void* stream);
+/* Reference maps: utils/attn.py:40-70 (shift_saved_attns) and the gather of utils/guidance.py:201.
+ *   maps: int64 [NB][NK][3] = {device address of the saved map, fp32 [rows][1][heads][side * side][1]; rows; side};
+ *   lay_of: int32 [NB], the layout of each box.  out: fp32, per layout [T][n_boxes][NK][heads][max_hw], the layouts back
+ *   to back (layout l starts at seg[l] * T * NK * heads * max_hw).  Element (t, b, k, h, p) = the map at the source of
+ *   p = y * side + x under the offset (ox / (L / 8)) * (side / 8) — the same eighth of the frame as the latents; 0
+ *   outside the frame, for t >= rows and for p >= side * side.  Every element is written.  side % 8 == 0 is the
+ *   caller's to check (shift_tensor asserts it). */
+int lgd_handoff_ref_maps_f32(const int32_t* plan, const int32_t* seg, const int32_t* lay_of, const int64_t* maps, int NB,
+                             int T, int NK, int heads, int max_hw, int L, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

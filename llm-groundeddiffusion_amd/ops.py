@@ -1002,3 +1002,72 @@ def sam_attn_prompt(attn, sigma, mask_th, up_w, up_h, *, want_smooth=False):
     _call("lgd_sam_attn_prompt_f32", _p(attn), N, hm, wm, float(sigma), float(mask_th), int(up_w), int(up_h), _p(coarse),
           _p(points), _p(smooth), _stream())
     return coarse, points, smooth
+
+
+# ---------------------------------------------------------------------------------------------
+# the hand-off between the two stages of LMD / LMD+ (csrc/handoff.hip; the tables are packed by lgd_amd.handoff)
+# ---------------------------------------------------------------------------------------------
+HANDOFF_PLAN = 8            # int32 per plan row: ox, oy, area, x0, y0, x1, y1, empty
+
+
+def _i32(t, name, shape=None):
+    if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{name}: a contiguous int32 tensor" + (f" of shape {tuple(shape)}" if shape else ""))
+    return t
+
+
+def handoff_place(masks, targets, seg, max_boxes, *, align, horizontal_shift_only):
+    """Per-box placement of a batch of layouts (lgd_handoff_place).  masks uint8 / bool [NB, L, L], targets fp64 [NB, 4],
+    seg int32 [NL + 1], max_boxes = the largest box count of a layout (host int) -> (plan int32 [NB, 8], win int32
+    [NL, 2, L, L] = the owner maps win_mask, win_box)."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    NB, NL = targets.shape[0], seg.shape[0] - 1
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or masks.shape[0] != NB or masks.shape[1] != masks.shape[2] \
+            or not masks.is_contiguous():
+        raise RuntimeError("handoff_place: masks is a contiguous uint8 [NB, L, L] tensor")
+    if targets.dtype != torch.float64 or tuple(targets.shape) != (NB, 4) or not targets.is_contiguous():
+        raise RuntimeError("handoff_place: targets is a contiguous fp64 [NB, 4] tensor")
+    _i32(seg, "handoff_place: seg")
+    L, dev = masks.shape[1], seg.device
+    plan = torch.empty((NB, HANDOFF_PLAN), device=dev, dtype=torch.int32)
+    win = torch.empty((NL, 2, L, L), device=dev, dtype=torch.int32)
+    _call("lgd_handoff_place", _p(masks), _p(targets), _p(seg), NL, NB, int(max_boxes), L, 1 if align else 0,
+          1 if horizontal_shift_only else 0, _p(plan), _p(win), _stream())
+    return plan, win
+
+
+def handoff_compose(plan, win, seg, hist, bg, steps, *, rows=None):
+    """Composition of every layout from the placement (lgd_handoff_compose_f32).  hist int64 [NB, 2] = (address, step
+    stride in elements) of each box's fp32 history, bg fp32 [NL, C, L, L] -> (composed fp32 [NL, steps + 1, C, L, L],
+    fg_idx int64 [NL, L, L], aligned fp32 [NB, rows, C, L, L] or None).  rows: also write the aligned histories, that many
+    steps of each."""
+    NL, C, L = bg.shape[0], bg.shape[1], bg.shape[2]
+    NB = plan.shape[0]
+    if bg.dtype != F32 or bg.dim() != 4 or bg.shape[3] != L or not bg.is_contiguous():
+        raise RuntimeError("handoff_compose: bg is a contiguous fp32 [NL, C, L, L] tensor")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] < NB or hist.shape[1] != 2 or not hist.is_contiguous():
+        raise RuntimeError("handoff_compose: hist is a contiguous int64 [NB, 2] tensor")
+    _i32(plan, "handoff_compose: plan"), _i32(win, "handoff_compose: win", (NL, 2, L, L)), _i32(seg, "handoff_compose: seg", (NL + 1,))
+    dev = bg.device
+    composed = torch.empty((NL, int(steps) + 1, C, L, L), device=dev, dtype=F32)
+    fg_idx = torch.empty((NL, L, L), device=dev, dtype=torch.int64)
+    aligned = torch.empty((NB, int(rows), C, L, L), device=dev, dtype=F32) if rows is not None and NB else None
+    _call("lgd_handoff_compose_f32", _p(plan), _p(win), _p(seg), _p(hist), _p(bg), NL, NB, int(steps), C, L,
+          int(rows) if aligned is not None else 0, _p(composed), _p(fg_idx), _p(aligned), _stream())
+    return composed, fg_idx, aligned
+
+
+def handoff_ref_maps(plan, seg, lay_of, maps, T, heads, max_hw, L):
+    """The reference-map tensors of every layout (lgd_handoff_ref_maps_f32).  maps int64 [NB, NK, 3] = (address, rows,
+    side) of each saved map, lay_of int32 [NB] -> one flat fp32 buffer; layout l's [T, n_boxes, NK, heads, max_hw] block
+    starts at seg[l] * T * NK * heads * max_hw."""
+    NB, NK = maps.shape[0], maps.shape[1]
+    if maps.dtype != torch.int64 or maps.dim() != 3 or maps.shape[2] != 3 or not maps.is_contiguous():
+        raise RuntimeError("handoff_ref_maps: maps is a contiguous int64 [NB, NK, 3] tensor")
+    _i32(plan, "handoff_ref_maps: plan", (NB, HANDOFF_PLAN)), _i32(seg, "handoff_ref_maps: seg"), _i32(lay_of, "handoff_ref_maps: lay_of", (NB,))
+    out = torch.empty((NB * int(T) * NK * int(heads) * int(max_hw),), device=plan.device, dtype=F32)
+    if NB:
+        _call("lgd_handoff_ref_maps_f32", _p(plan), _p(seg), _p(lay_of), _p(maps), NB, int(T), NK, int(heads), int(max_hw),
+              int(L), _p(out), _stream())
+    return out

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import handoff as device_handoff
 from .hostprep import (align_with_bboxes, compose as compose_latents, get_centered_box,
                        input_latents_list as _input_latents_list, proportion_to_mask, seeded_noise, shift_tensor)
 from .sampler import (BOXDIFF_GUIDANCE_ATTN_KEYS, DEFAULT_GUIDANCE_ATTN_KEYS, Job, LMDSampler,
@@ -182,11 +183,12 @@ def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ra
     return L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps
 
 
-def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, masks_of=None, **denoise_kw):
+def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, masks_of=None, masks_stay=False, **denoise_kw):
     """One generation per box (job_of(layout, its index, box index, box)), all boxes of all layouts as one batched
     denoising call -> per layout the histories, saved maps, foreground masks (mask_of(decoded image or None, box, result)),
     decoded images and guidance iteration counts of its boxes.  masks_of(decoded uint8 batch on the device, boxes,
-    results) -> all masks (n, L, L) at once: the batched refinement, enqueued before the images go to the host."""
+    results) -> all masks (n, L, L) at once: the batched refinement, enqueued before the images go to the host.
+    masks_stay: the device hand-off follows, which reads those masks where they are."""
     owner = [(li, i) for li in range(len(lays)) for i in range(len(so_boxes[li]))]
     jobs = [job_of(lays[li], li, i, so_boxes[li][i]) for li, i in owner]
     res_a = sampler.denoise_batch(jobs, T, return_cond_ca_only=True, **denoise_kw) if jobs else []
@@ -198,7 +200,9 @@ def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, masks_of=None,
             masks = masks_of(imgs, [so_boxes[li][i] for li, i in owner], res_a)
         imgs = imgs.cpu().numpy()
         if masks is not None:
-            masks = torch.as_tensor(masks).bool().cpu()           # the composition (hostprep.compose) is host code
+            masks = torch.as_tensor(masks).bool()
+            if not masks_stay:
+                masks = masks.cpu()                               # the composition (hostprep.compose) is host code
     for n, ((li, i), r) in enumerate(zip(owner, res_a)):
         d = per_lay[li]
         d["latents_all"].append(r["latents_all"])
@@ -210,34 +214,52 @@ def _stage_a(sampler, lays, so_boxes, T, decode, job_of, mask_of, masks_of=None,
     return per_lay
 
 
-def _overall_guidance(sampler, lay, saved, keys, L, T, use_ref_ca, max_iter=None, **thresholds_and_weights):
-    """Guidance of the overall generation (lmd_plus.py:487 / lmd.py:521), or None for a layout without boxes."""
+def _overall_guidance(sampler, lay, saved, keys, L, T, use_ref_ca, max_iter=None, ref_maps=None, **thresholds_and_weights):
+    """Guidance of the overall generation (lmd_plus.py:487 / lmd.py:521), or None for a layout without boxes.  ref_maps: the
+    ready reference tensor of the device hand-off; without it the saved maps are gathered here."""
     overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
     if not overall_bboxes:
         return None
     return dict(bboxes=overall_bboxes, object_positions=lay.overall_object_positions, max_iter=max_iter or DEFAULT_MAX_ITER,
                 ref_ca_word_token_only=True, ref_ca_last_token_only=True,
                 word_token_indices=lay.overall_word_token_indices, use_ratio_based_loss=False, guidance_attn_keys=keys,
-                ref_maps=_ref_maps(sampler, saved, keys, L, T) if use_ref_ca else None, **thresholds_and_weights)
+                ref_maps=(ref_maps if ref_maps is not None else _ref_maps(sampler, saved, keys, L, T)) if use_ref_ca else None,
+                **thresholds_and_weights)
 
 
 def _stage_b(sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only,
-             use_ref_ca, overall, decode, gligen_of=lambda lay: None, overall_start=None, **denoise_kw):
+             use_ref_ca, overall, decode, gligen_of=lambda lay: None, overall_start=None, handoff="host", **denoise_kw):
     """Alignment (latents.py:107-118), composition (lmd_plus.py:398-416) and the overall generation with attention guidance
     (overall: _overall_guidance's keyword arguments) of all layouts as one batched denoising call -> (result dict per
-    layout, the denoising results).  gligen_of(layout): the GLIGEN conditioning of its job, if the method has one."""
+    layout, the denoising results).  gligen_of(layout): the GLIGEN conditioning of its job, if the method has one.
+    handoff: "host" = box by box on the host, "device" = lgd_amd.handoff, all layouts in three launches."""
     jobs, comps = [], []
+    placed = None
+    if handoff == "device":
+        with_maps = use_ref_ca and any(d["saved"] for d in per_lay)
+        hw = sampler.map_hw(L)
+        placed = device_handoff.run(
+            sampler.dev, masks=[d["masks"] for d in per_lay], histories=[d["latents_all"] for d in per_lay],
+            targets=[[lay.boxes[i] for grp in lay.overall_groups for i in grp][:len(d["masks"])] for lay, d in zip(lays, per_lay)],
+            saved=[d["saved"] for d in per_lay], bgs=[p[1] for p in prep], keys=keys, L=L, T=T, steps=comp_steps,
+            align=align_with_overall_bboxes, horizontal_shift_only=horizontal_shift_only,
+            heads=sampler.heads_of(keys[0]) if with_maps else None, max_hw=max(hw[k] for k in keys) if with_maps else None)
     for li, lay in enumerate(lays):
         d = per_lay[li]
-        _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_only)
-        composed, fg_idx = compose_latents(d["latents_all"], d["masks"], comp_steps, prep[li][1].to(sampler.dev))
+        if placed is not None:
+            composed, fg_idx = placed[li]["composed"], placed[li]["fg_idx"]
+            d["latents_all"] = placed[li]["latents_all"]
+        else:
+            _align_stage_a(d, lay, keys, align_with_overall_bboxes, horizontal_shift_only)
+            composed, fg_idx = compose_latents(d["latents_all"], d["masks"], comp_steps, prep[li][1].to(sampler.dev))
         comps.append((composed, fg_idx))
         start = composed
         if overall_start is not None:                     # rows 1.. still feed the frozen-mask blend
             start = composed.clone()
             start[0] = torch.as_tensor(overall_start[li]).to(start.device, start.dtype)
         jobs.append(Job(start, torch.cat([lay.overall_uncond, lay.overall_cond]), gligen=gligen_of(lay),
-                        guidance=_overall_guidance(sampler, lay, d["saved"], keys, L, T, use_ref_ca, **overall),
+                        guidance=_overall_guidance(sampler, lay, d["saved"], keys, L, T, use_ref_ca,
+                                                   ref_maps=placed[li]["ref_maps"] if placed is not None else None, **overall),
                         frozen_mask=(fg_idx != 0)))
     res_b = sampler.denoise_batch(jobs, T, save_all_latents=False, **denoise_kw)
     images = sampler.decode(torch.cat([r["latents"] for r in res_b])) if decode else [None] * len(lays)
@@ -261,7 +283,7 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
                             use_ref_ca=True, height=512, width=512, decode=True, guidance_attn_keys=None,
                             use_fast_schedule=False, so_center_box=False, so_horizontal_center_only=True,
                             align_with_overall_bboxes=False, horizontal_shift_only=True, mask_refiner=None,
-                            overall_first_step=0, overall_n_steps=None, overall_start=None):
+                            overall_first_step=0, overall_n_steps=None, overall_start=None, handoff=None):
     """LMD+ (generation/lmd_plus.py:193-520; per-box attention guidance is off by default there,
     max_index_step=0, :203 — with max_index_step > 0 every per-box GLIGEN generation is guided on its own box with
     the energy's default weights, lmd_plus.py:320-328) for a batch of independent layouts: the per-box generations of ALL layouts run
@@ -269,8 +291,11 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
     another (B = 2 x layouts; guidance pass B = layouts with a per-image loop exit).  Results per layout
     are independent of how layouts are batched (images only share kernel launches).
     overall_first_step / overall_n_steps / overall_start (one latent tensor per layout): run only those steps of the
-    overall generation, from the given state — the teacher-forcing hook of the parity tests."""
+    overall generation, from the given state — the teacher-forcing hook of the parity tests.
+    handoff: where alignment, composition and the reference-map gather between the two stages run — "host" (hostprep, box
+    by box), "device" (lgd_amd.handoff: three launches for the batch, no read) or None = lgd_amd.handoff.resolve's choice."""
     T, dev = num_inference_steps, sampler.dev
+    handoff = device_handoff.resolve(handoff, _batched(mask_refiner, "box"))
     L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps = _two_stage_setup(
         sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule, use_ref_ca,
         overall_max_index_step, so_center_box, horizontal_center_only=so_horizontal_center_only)
@@ -293,7 +318,7 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
         return mask_refiner.boxes(images, boxes)[0]
     per_lay = _stage_a(sampler, lays, so_boxes if use_ref_ca or frozen_steps > 0 else [[]] * len(lays), T, decode, so_job,
                        lambda image, box, r: _so_mask(mask_refiner, "box", image, box, L),
-                       so_masks if _batched(mask_refiner, "box") else None,
+                       so_masks if _batched(mask_refiner, "box") else None, handoff == "device",
                        guidance_scale=guidance_scale, use_gligen=True,
                        gligen_scheduled_sampling_beta=so_gligen_scheduled_sampling_beta,
                        saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys] if use_ref_ca else [OBJ_ATTN_KEY],
@@ -303,7 +328,7 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
         dict(loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold, max_iter=overall_max_iter,
              max_index_step=overall_max_index_step, fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p,
              fg_weight=overall_fg_weight, bg_weight=overall_bg_weight, ref_ca_loss_weight=ref_ca_loss_weight),
-        decode, overall_gligen, overall_start, guidance_scale=guidance_scale, use_gligen=True,
+        decode, overall_gligen, overall_start, handoff, guidance_scale=guidance_scale, use_gligen=True,
         gligen_scheduled_sampling_beta=overall_gligen_scheduled_sampling_beta, frozen_steps=frozen_steps,
         first_step=overall_first_step, n_steps=overall_n_steps)
     for d, r, pl in zip(out, res_b, per_lay):
@@ -325,12 +350,13 @@ def lmd_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num_inf
                        height=512, width=512, decode=True, guidance_attn_keys=None, use_fast_schedule=False,
                        so_center_box=False, so_horizontal_center_only=False, so_vertical_placement="floor_padding",
                        so_floor_padding=0.2, align_with_overall_bboxes=False, horizontal_shift_only=False,
-                       mask_refiner=None, attn_aggregation_step_start=10):
+                       mask_refiner=None, attn_aggregation_step_start=10, handoff=None):
     """Training-free LMD (generation/lmd.py:215-551) for a batch of independent layouts: per-box stage =
     generate_semantic_guidance WITH guidance (lmd.py:340-352), all boxes of all layouts in one batched
     denoising call (each image keeps its own guidance loop exit); overall stage = generate_partial_frozen
-    with the reference-attention term (lmd.py:530-542), all layouts in another."""
+    with the reference-attention term (lmd.py:530-542), all layouts in another.  handoff: as lmd_plus_generate_batch."""
     T = num_inference_steps
+    handoff = device_handoff.resolve(handoff, _batched(mask_refiner, "attn"))
     L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps = _two_stage_setup(
         sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule, use_ref_ca,
         overall_max_index_step, so_center_box, horizontal_center_only=so_horizontal_center_only,
@@ -352,14 +378,14 @@ def lmd_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num_inf
         maps = torch.stack([_token_attn(r["saved"], attn_aggregation_step_start, on_device=True) for r in res])
         return mask_refiner.attns(images, maps)[0]
     per_lay = _stage_a(sampler, lays, so_boxes, T, decode, so_job, so_mask, so_masks if _batched(mask_refiner, "attn") else None,
-                       guidance_scale=guidance_scale,
+                       handoff == "device", guidance_scale=guidance_scale,
                        saved_cross_attn_keys=[OBJ_ATTN_KEY, *keys], fast_after_steps=fast_after)
     return _stage_b(
         sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only, use_ref_ca,
         dict(loss_scale=overall_loss_scale, loss_threshold=overall_loss_threshold, max_iter=overall_max_iter,
              max_index_step=overall_max_index_step, fg_top_p=overall_fg_top_p, bg_top_p=overall_bg_top_p,
              fg_weight=overall_fg_weight, bg_weight=overall_bg_weight, ref_ca_loss_weight=ref_ca_loss_weight),
-        decode, guidance_scale=guidance_scale, frozen_steps=frozen_steps)[0]
+        decode, handoff=handoff, guidance_scale=guidance_scale, frozen_steps=frozen_steps)[0]
 
 
 def _single_shot(sampler, lays, keys, guidance_kw, *, num_inference_steps, guidance_scale, height, decode, first_step,
