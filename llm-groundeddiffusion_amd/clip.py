@@ -16,7 +16,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
+from . import ops, vit
 
 F16, F32 = torch.float16, torch.float32
 
@@ -40,7 +40,7 @@ class _Out(tuple):
     pass
 
 
-class HipCLIPTextEncoder:
+class HipCLIPTextEncoder(vit.Tower):
     def __init__(self, config: CLIPTextConfig, state_dict, device="cuda"):
         if config.hidden_act not in ("quick_gelu", "gelu"):
             raise RuntimeError(f"hidden_act={config.hidden_act!r}: quick_gelu (SD1.x, CLIP ViT-L/14) and gelu (SD2.x, "
@@ -50,28 +50,18 @@ class HipCLIPTextEncoder:
         self.cfg = config
         self.dev = torch.device(device)
         sd = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state_dict.items()}
-        h16 = lambda t: t.detach().to(self.dev, F16).contiguous()
-        f32 = lambda t: t.detach().to(self.dev, F32).contiguous()
-        self.tok_emb = f32(sd["embeddings.token_embedding.weight"])
-        self.pos_emb = f32(sd["embeddings.position_embedding.weight"])
+        w = vit.Weights(sd, self.dev)
+        self.tok_emb = w.f32(w["embeddings.token_embedding.weight"])
+        self.pos_emb = w.f32(w["embeddings.position_embedding.weight"])
         self.layers = []
         for i in range(config.num_hidden_layers):
             p = f"encoder.layers.{i}"
-            qkv_w = torch.cat([sd[f"{p}.self_attn.{n}_proj.weight"] for n in "qkv"])
-            qkv_b = torch.cat([sd[f"{p}.self_attn.{n}_proj.bias"] for n in "qkv"])
-            self.layers.append(dict(
-                ln1=(f32(sd[f"{p}.layer_norm1.weight"]), f32(sd[f"{p}.layer_norm1.bias"])),
-                qkv=(h16(qkv_w), f32(qkv_b)),
-                out=(h16(sd[f"{p}.self_attn.out_proj.weight"]), f32(sd[f"{p}.self_attn.out_proj.bias"])),
-                ln2=(f32(sd[f"{p}.layer_norm2.weight"]), f32(sd[f"{p}.layer_norm2.bias"])),
-                fc1=(h16(sd[f"{p}.mlp.fc1.weight"]), f32(sd[f"{p}.mlp.fc1.bias"])),
-                fc2=(h16(sd[f"{p}.mlp.fc2.weight"]), f32(sd[f"{p}.mlp.fc2.bias"]))))
-        self.ln_f = (f32(sd["final_layer_norm.weight"]), f32(sd["final_layer_norm.bias"]))
+            self.layers.append(vit.Layer(ln1=w.ln(f"{p}.layer_norm1"), qkv=w.qkv(f"{p}.self_attn"),
+                                         out=w.lin(f"{p}.self_attn.out_proj"), ln2=w.ln(f"{p}.layer_norm2"),
+                                         fc1=w.lin(f"{p}.mlp.fc1"), fc2=w.lin(f"{p}.mlp.fc2")))
+        self.ln_f = w.ln("final_layer_norm")
         # CLIPTextModelWithProjection (SDXL's text_encoder_2, OpenCLIP ViT-bigG/14): text_embeds = pooled @ W^T, no bias
-        self.text_projection = h16(state_dict["text_projection.weight"]) if "text_projection.weight" in state_dict else None
-
-    def to(self, *_a, **_k):            # call-surface compatibility with nn.Module users
-        return self
+        self.text_projection = w.h16(state_dict["text_projection.weight"]) if "text_projection.weight" in state_dict else None
 
     @torch.no_grad()
     def __call__(self, input_ids=None, attention_mask=None, output_hidden_states=False, **_kw):
@@ -94,16 +84,12 @@ class HipCLIPTextEncoder:
         x = (self.tok_emb[ids] + self.pos_emb[:S].unsqueeze(0)).reshape(B * S, C).to(F16).contiguous()
         eps = cfg.layer_norm_eps
         hidden = [x.float().reshape(B, S, C)] if output_hidden_states else None
-        for L in self.layers:
-            h = ops.layernorm(x, L["ln1"][0], L["ln1"][1], eps)
-            qkv = ops.linear(h, L["qkv"][0], L["qkv"][1])                          # [B*S, 3C]
+
+        def attend(qkv):                                                            # [B*S, 3C]
             o = torch.empty((B * S, C), device=self.dev, dtype=F16)
-            ops.attn_causal_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, H, S, d, d ** -0.5, view=(3 * C, S * 3 * C))
-            x = ops.linear(o, L["out"][0], L["out"][1], res=x)
-            h = ops.layernorm(x, L["ln2"][0], L["ln2"][1], eps)
-            h = ops.linear(h, L["fc1"][0], L["fc1"][1])
-            h = ops.quick_gelu(h) if cfg.hidden_act == "quick_gelu" else ops.act(h, ops.ACT_GELU)
-            x = ops.linear(h, L["fc2"][0], L["fc2"][1], res=x)
+            return ops.attn_causal_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, H, S, d, d ** -0.5, view=(3 * C, S * 3 * C))
+        for L in self.layers:
+            x = vit.block(x, L, eps, attend, cfg.hidden_act)
             if hidden is not None:
                 hidden.append(x.float().reshape(B, S, C))
         y = ops.layernorm(x, self.ln_f[0], self.ln_f[1], eps).float().reshape(B, S, C)

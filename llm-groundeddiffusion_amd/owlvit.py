@@ -28,7 +28,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
+from . import ops, vit
 from .clip import CLIPTextConfig, HipCLIPTextEncoder
 
 F16, F32 = torch.float16, torch.float32
@@ -109,20 +109,14 @@ class Detections:
         return self.boxes[b, :n], self.scores[b, :n], self.labels[b, :n]
 
 
-class HipOwlViTDetector:
+class HipOwlViTDetector(vit.Tower):
     def __init__(self, config: OwlViTConfig, state_dict, device="cuda"):
         cfg = self.cfg = config
         self.dev = dev = torch.device(device)
         sd = state_dict
-        self.consumed = set()
-
-        def get(k):
-            self.consumed.add(k)
-            return sd[k]
-        h16 = lambda t: t.detach().to(dev, F16).contiguous()
-        f32 = lambda t: t.detach().to(dev, F32).contiguous()
-        lin = lambda p: (h16(get(p + ".weight")), f32(get(p + ".bias")))
-        ln = lambda p: (f32(get(p + ".weight")), f32(get(p + ".bias")))
+        w = vit.Weights(sd, dev)
+        self.consumed = w.consumed
+        h16, f32, lin, ln = w.h16, w.f32, w.lin, w.ln
         C, NH = cfg.hidden_size, cfg.num_attention_heads
         if C % NH or (C // NH) % 8:
             raise RuntimeError("head width must be a multiple of 8")
@@ -136,8 +130,8 @@ class HipOwlViTDetector:
 
         # ---- text tower (CLIP, causal) + projection
         tp = "owlvit.text_model."
-        text_sd = {k[len("owlvit."):]: get(k) for k in list(sd) if k.startswith(tp) and not k.endswith("position_ids")}
-        text_sd["text_projection.weight"] = get("owlvit.text_projection.weight")
+        text_sd = {k[len("owlvit."):]: w[k] for k in list(sd) if k.startswith(tp) and not k.endswith("position_ids")}
+        text_sd["text_projection.weight"] = w["owlvit.text_projection.weight"]
         self.text = HipCLIPTextEncoder(CLIPTextConfig(
             vocab_size=cfg.text_vocab_size, hidden_size=cfg.text_hidden_size,
             intermediate_size=cfg.text_intermediate_size, num_hidden_layers=cfg.text_num_hidden_layers,
@@ -147,27 +141,25 @@ class HipOwlViTDetector:
 
         # ---- vision tower
         v = "owlvit.vision_model."
-        self.patch = h16(get(v + "embeddings.patch_embedding.weight").reshape(C, -1))
-        pos = f32(get(v + "embeddings.position_embedding.weight"))                      # [P + 1, C]
+        self.patch = h16(w[v + "embeddings.patch_embedding.weight"].reshape(C, -1))
+        pos = f32(w[v + "embeddings.position_embedding.weight"])                      # [P + 1, C]
         if pos.shape[0] != self.P + 1:
             raise RuntimeError("position table does not match the image grid (interpolate_pos_encoding is not implemented)")
-        self.cls_pos = f32(get(v + "embeddings.class_embedding")) + pos[0]              # row 0 of every image
+        self.cls_pos = f32(w[v + "embeddings.class_embedding"]) + pos[0]              # row 0 of every image
         self.pos = h16(pos[1:])
-        self._pos_rep = {}
         self.pre_ln, self.post_ln = ln(v + "pre_layernorm"), ln(v + "post_layernorm")
         self.layers = []
         for i in range(cfg.num_hidden_layers):
             p = f"{v}encoder.layers.{i}."
-            qkv_w = torch.cat([get(f"{p}self_attn.{n}_proj.weight") for n in "qkv"])
-            qkv_b = torch.cat([get(f"{p}self_attn.{n}_proj.bias") for n in "qkv"])
-            self.layers.append(dict(ln1=ln(p + "layer_norm1"), qkv=(h16(qkv_w), f32(qkv_b)), out=lin(p + "self_attn.out_proj"),
-                                    ln2=ln(p + "layer_norm2"), fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
+            self.layers.append(vit.Layer(ln1=ln(p + "layer_norm1"), qkv=w.qkv(p + "self_attn"),
+                                         out=lin(p + "self_attn.out_proj"), ln2=ln(p + "layer_norm2"),
+                                         fc1=lin(p + "mlp.fc1"), fc2=lin(p + "mlp.fc2")))
         self.merge_ln = ln("layer_norm")
 
         # ---- heads
         self.dense0 = lin("class_head.dense0")
-        ss_w = torch.cat([get("class_head.logit_shift.weight"), get("class_head.logit_scale.weight")])
-        ss_b = torch.cat([get("class_head.logit_shift.bias"), get("class_head.logit_scale.bias")])
+        ss_w = torch.cat([w["class_head.logit_shift.weight"], w["class_head.logit_scale.weight"]])
+        ss_b = torch.cat([w["class_head.logit_shift.bias"], w["class_head.logit_scale.bias"]])
         pad = lambda t: torch.cat([t, t.new_zeros((8 - t.shape[0],) + tuple(t.shape[1:]))])   # GEMM columns: 2 -> 8
         self.shift_scale = (h16(pad(ss_w)), f32(pad(ss_b)))
         self.box = [lin(f"box_head.dense{i}") for i in range(3)]
@@ -177,20 +169,7 @@ class HipOwlViTDetector:
         if extra:
             raise RuntimeError(f"state-dict entries the detector does not know: {extra}")
 
-    def to(self, *_a, **_k):            # call-surface compatibility with nn.Module users
-        return self
-
-    def eval(self):
-        return self
-
     # ------------------------------------------------------------------------------------------------------------
-    def _rep_pos(self, B):
-        if B not in self._pos_rep:
-            if len(self._pos_rep) > 8:
-                self._pos_rep.clear()
-            self._pos_rep[B] = self.pos.repeat(B, 1).contiguous()
-        return self._pos_rep[B]
-
     @torch.no_grad()
     def encode_image(self, pixel_values):
         """pixel_values (B, 3, S, S) -> image_embeds fp16 [B*P, C]: [ext] OwlViTVisionTransformer.forward followed by
@@ -201,24 +180,20 @@ class HipOwlViTDetector:
             raise ValueError(f"Input image size ({Hh}*{Ww}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
         ps, C, NH, eps = cfg.patch_size, cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
         S = P + 1
-        patches = (pixel_values.to(self.dev, F16).reshape(B, Cin, g, ps, g, ps).permute(0, 2, 4, 1, 3, 5)
-                   .reshape(B * P, Cin * ps * ps).contiguous())
-        emb = ops.linear(patches, self.patch, None, res=self._rep_pos(B))               # [B*P, C] + position
+        emb = ops.linear(vit.patch_rows(pixel_values, g, ps, self.dev), self.patch, None,
+                         res=self.rep_rows("pos", self.pos, B))                        # [B*P, C] + position
         x = torch.empty((B, S, C), device=self.dev, dtype=F16)
         x[:, 0] = self.cls_pos.to(F16)
         x[:, 1:] = emb.reshape(B, P, C)
         x = ops.layernorm(x.reshape(B * S, C), self.pre_ln[0], self.pre_ln[1], eps)
-        scale = d ** -0.5
-        for L in self.layers:
-            h = ops.layernorm(x, L["ln1"][0], L["ln1"][1], eps)
-            qkv = ops.linear(h, L["qkv"][0], L["qkv"][1])                               # [B*S, 3C]
+        view = (3 * C, S * 3 * C)
+
+        def attend(qkv):                                                                # [B*S, 3C]
             o = torch.empty((B * S, C), device=self.dev, dtype=F16)
-            view = (3 * C, S * 3 * C)
-            ops.attn_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, NH, S, S, d, scale, q_view=view, k_view=view, v_view=view)
-            x = ops.linear(o, L["out"][0], L["out"][1], res=x)
-            h = ops.layernorm(x, L["ln2"][0], L["ln2"][1], eps)
-            h = ops.quick_gelu(ops.linear(h, L["fc1"][0], L["fc1"][1]))
-            x = ops.linear(h, L["fc2"][0], L["fc2"][1], res=x)
+            return ops.attn_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, NH, S, S, d, d ** -0.5, q_view=view, k_view=view,
+                                v_view=view)
+        for L in self.layers:
+            x = vit.block(x, L, eps, attend, "quick_gelu")
         y = ops.layernorm(x, self.post_ln[0], self.post_ln[1], eps).reshape(B, S, C)
         merged = (y[:, 1:].float() * y[:, :1].float()).to(F16).reshape(B * P, C).contiguous()
         return ops.layernorm(merged, self.merge_ln[0], self.merge_ln[1], eps)

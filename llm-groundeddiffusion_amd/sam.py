@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, vit
 from .weightstore import pack_conv
 
 F16, F32 = torch.float16, torch.float32
@@ -92,15 +92,13 @@ def _rel_table(rel_pos, size):
     return rel_pos
 
 
-class HipSamModel:
+class HipSamModel(vit.Tower):
     def __init__(self, config: SamConfig, state_dict, device="cuda"):
         cfg = self.cfg = config
         self.dev = dev = torch.device(device)
         sd = state_dict
-        h16 = lambda t: t.detach().to(dev, F16).contiguous()
-        f32 = lambda t: t.detach().to(dev, F32).contiguous()
-        lin = lambda p: (h16(sd[p + ".weight"]), f32(sd[p + ".bias"]))
-        ln = lambda p: (f32(sd[p + ".weight"]), f32(sd[p + ".bias"]))
+        w = vit.Weights(sd, dev)
+        h16, f32, lin, ln = w.h16, w.f32, w.lin, w.ln
         self.grid = g = cfg.image_size // cfg.patch_size
         C, NH = cfg.hidden_size, cfg.num_attention_heads
         if C % NH or (C // NH) % 8:
@@ -113,8 +111,7 @@ class HipSamModel:
         v = "vision_encoder."
         self.patch = (h16(sd[v + "patch_embed.projection.weight"].reshape(C, -1)), f32(sd[v + "patch_embed.projection.bias"]))
         self.pos = h16(sd[v + "pos_embed"].reshape(g * g, C))
-        self._pos_rep = {}
-        self.blocks = []
+        self.blocks = []                # (layer, its own attention: window, S, DA, rel_h, rel_w)
         for i in range(cfg.num_hidden_layers):
             p = f"{v}layers.{i}."
             window = 0 if i in cfg.global_attn_indexes else cfg.window_size
@@ -122,10 +119,10 @@ class HipSamModel:
             DA = -(-(d + 2 * S) // 32) * 32                      # augmented head width (32-column MFMA chunks)
             if DA > 192:
                 raise RuntimeError(f"augmented head width {DA} > 192 (head {d} + 2 x {S} bias columns)")
-            self.blocks.append(dict(
-                window=window, S=S, DA=DA, ln1=ln(p + "layer_norm1"), qkv=lin(p + "attn.qkv"),
-                rel_h=f32(_rel_table(sd[p + "attn.rel_pos_h"], S)), rel_w=f32(_rel_table(sd[p + "attn.rel_pos_w"], S)),
-                proj=lin(p + "attn.proj"), ln2=ln(p + "layer_norm2"), lin1=lin(p + "mlp.lin1"), lin2=lin(p + "mlp.lin2")))
+            self.blocks.append((
+                vit.Layer(ln1=ln(p + "layer_norm1"), qkv=lin(p + "attn.qkv"), out=lin(p + "attn.proj"),
+                          ln2=ln(p + "layer_norm2"), fc1=lin(p + "mlp.lin1"), fc2=lin(p + "mlp.lin2")),
+                (window, S, DA, f32(_rel_table(sd[p + "attn.rel_pos_h"], S)), f32(_rel_table(sd[p + "attn.rel_pos_w"], S)))))
         OC = cfg.output_channels
         self.neck1 = h16(sd[v + "neck.conv1.weight"].reshape(OC, C))
         self.neck_ln1 = ln(v + "neck.layer_norm1")
@@ -155,10 +152,7 @@ class HipSamModel:
 
         def attn(p):
             q, k, vv, o = (lin(f"{p}.{n}_proj") for n in ("q", "k", "v", "out"))
-            return dict(q=q, k=k, v=vv, o=o, inner=q[0].shape[0],
-                        kv=(torch.cat([k[0], vv[0]]).contiguous(), torch.cat([k[1], vv[1]]).contiguous()),
-                        qk=(torch.cat([q[0], k[0]]).contiguous(), torch.cat([q[1], k[1]]).contiguous()),
-                        qkv=(torch.cat([q[0], k[0], vv[0]]).contiguous(), torch.cat([q[1], k[1], vv[1]]).contiguous()))
+            return dict(q=q, k=k, v=vv, o=o, inner=q[0].shape[0], kv=w.qkv(p, "kv"), qk=w.qkv(p, "qk"), qkv=w.qkv(p))
 
         def with_pe(a, which):
             """`(keys + image_pe) @ W^T` = `keys @ W^T + image_pe @ W^T`: the second term is a constant table, added in
@@ -192,13 +186,6 @@ class HipSamModel:
             return [lin(p + ".proj_in")] + [lin(f"{p}.layers.{j}") for j in range(n_mid)] + [lin(p + ".proj_out")]
         self.hyper = [ffn(f"{m}output_hypernetworks_mlps.{i}") for i in range(self.n_mask_tokens)]
         self.iou_head = ffn(m + "iou_prediction_head")
-        self._pe_rep = {}
-
-    def to(self, *_a, **_k):            # call-surface compatibility with nn.Module users
-        return self
-
-    def eval(self):
-        return self
 
     # ------------------------------------------------------------------------------------------------------------
     def _pe(self, coords01):
@@ -206,14 +193,6 @@ class HipSamModel:
         c = (2.0 * coords01.to(self.dev, F32) - 1.0) @ self.gauss
         c = 2.0 * math.pi * c
         return torch.cat([c.sin(), c.cos()], dim=-1)
-
-    def _rep(self, cache, key, t, n):
-        k = (key, n)
-        if k not in cache:
-            if len(cache) > 16:
-                cache.clear()
-            cache[k] = t.repeat(n, 1).contiguous()
-        return cache[k]
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -224,24 +203,17 @@ class HipSamModel:
         B, Cin, Hh, Ww = pixel_values.shape
         if (Cin, Hh, Ww) != (cfg.num_channels, cfg.image_size, cfg.image_size):
             raise ValueError(f"Input image size ({Hh}*{Ww}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
-        P, C, NH = cfg.patch_size, cfg.hidden_size, cfg.num_attention_heads
-        patches = (pixel_values.to(self.dev, F16).reshape(B, Cin, g, P, g, P).permute(0, 2, 4, 1, 3, 5)
-                   .reshape(B * g * g, Cin * P * P).contiguous())
-        x = ops.linear(patches, self.patch[0], self.patch[1], res=self._rep(self._pos_rep, "pos", self.pos, B))
+        NH = cfg.num_attention_heads
+        x = ops.linear(vit.patch_rows(pixel_values, g, cfg.patch_size, self.dev), self.patch[0], self.patch[1],
+                       res=self.rep_rows("pos", self.pos, B))
         scale = d ** -0.5
-        for L in self.blocks:
-            h = ops.layernorm(x, L["ln1"][0], L["ln1"][1], cfg.vision_eps)
-            qkv = ops.linear(h, L["qkv"][0], L["qkv"][1])
-            S, DA = L["S"], L["DA"]
-            qa, ka, va = ops.sam_relpos_qkv(qkv, L["qkv"][1], L["rel_h"], L["rel_w"], B, g, g, L["window"], NH, d, DA, scale)
-            nwin = qa.shape[0] // (S * S)
-            oa = torch.empty_like(qa)
-            ops.attn_fwd(qa, ka, va, oa, nwin, NH, S * S, S * S, DA, scale)
-            o = ops.sam_window_merge(oa, B, g, g, L["window"], NH, d, DA)
-            x = ops.linear(o, L["proj"][0], L["proj"][1], res=x)
-            h = ops.layernorm(x, L["ln2"][0], L["ln2"][1], cfg.vision_eps)
-            h = ops.act(ops.linear(h, L["lin1"][0], L["lin1"][1]), ops.ACT_GELU)
-            x = ops.linear(h, L["lin2"][0], L["lin2"][1], res=x)
+        for L, (window, S, DA, rel_h, rel_w) in self.blocks:
+            def attend(qkv):
+                qa, ka, va = ops.sam_relpos_qkv(qkv, L.qkv[1], rel_h, rel_w, B, g, g, window, NH, d, DA, scale)
+                oa = torch.empty_like(qa)
+                ops.attn_fwd(qa, ka, va, oa, qa.shape[0] // (S * S), NH, S * S, S * S, DA, scale)
+                return ops.sam_window_merge(oa, B, g, g, window, NH, d, DA)
+            x = vit.block(x, L, cfg.vision_eps, attend, "gelu")
         y = ops.linear(x, self.neck1)
         y = ops.layernorm(y, self.neck_ln1[0], self.neck_ln1[1], 1e-6)
         y = ops.conv3x3(y, self.neck2, B, g, g)
@@ -344,7 +316,7 @@ class HipSamModel:
         keys = (emb_dense.reshape(B, 1, HW, D).expand(B, P, HW, D).reshape(BP * HW, D).contiguous() if P > 1
                 else emb_dense)
         eps = cfg.dec_eps
-        rep = lambda name, t: self._rep(self._pe_rep, name, t, BP)
+        rep = lambda name, t: self.rep_rows(name, t, BP)
         for i, L in enumerate(self.dec):
             if i == 0:                                           # skip_first_layer_pe: the attention output REPLACES the tokens
                 queries = self._attention(L["self_attn"], queries, queries, queries, BP, T, T)

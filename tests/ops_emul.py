@@ -1,9 +1,11 @@
-"""TEST INFRASTRUCTURE — a torch restatement of the few `lgd_amd.ops` entry points that `lgd_amd/sam.py` calls, with the
-same argument conventions (flattened channels-last tokens, (ld, batch-stride) views, fp16 storage, fp32 arithmetic).
+"""TEST INFRASTRUCTURE — a torch restatement of the few `lgd_amd.ops` entry points that the towers outside the UNet call
+(`lgd_amd/sam.py`, `clip.py`, `owlvit.py` without its heads kernel, `vit.py`), with the same argument conventions
+(flattened channels-last tokens, (ld, batch-stride) views, fp16 storage, fp32 arithmetic).
 
-It exists so that the HOST algebra of the SAM port (weight re-packing, the rel-pos-bias-as-extra-head-columns trick,
-transposed convolutions as GEMMs, the nested pixel order of the mask head, pre-projected position tables) can be
-checked against the Hugging Face module on the GPU-less build container (tests/test_sam_host.py), and so that the HIP
+It exists so that the HOST algebra of the ports (weight re-packing, the rel-pos-bias-as-extra-head-columns trick,
+transposed convolutions as GEMMs, the nested pixel order of the mask head, pre-projected position tables, fused q/k/v,
+patch unfolding, pooling) can be checked against the Hugging Face modules on the GPU-less build container
+(tests/test_sam_host.py, tests/test_towers_host.py; `install` redirects a module's kernel calls), and so that the HIP
 kernels of csrc/sam.hip have an independent statement to be compared with on the GPU (tests/test_sam_gpu.py).
 The product never imports this file: `lgd_amd.ops` raises without liblgd_hip.so.
 """
@@ -12,6 +14,17 @@ import torch.nn.functional as F
 
 F16, F32 = torch.float16, torch.float32
 ACT_GELU, ACT_RELU = 1, 2
+
+
+def install(monkeypatch, *modules):
+    """Point `ops` and `F16` of every given module at this emulation with fp32 storage, so that a comparison isolates the
+    host algebra (with fp16 storage the same run differs from an fp32 module by the rounding noise of the chained ops,
+    which the GPU tests bound separately)."""
+    import sys
+    for m in modules:
+        monkeypatch.setattr(m, "ops", sys.modules[__name__])
+        monkeypatch.setattr(m, "F16", F32)
+    monkeypatch.setattr(sys.modules[__name__], "F16", F32)
 
 
 def linear(x, w, bias=None, res=None, out=None, *, out_f32=False, **_kw):
@@ -61,6 +74,20 @@ def attn_fwd(q, k, v, o, B, H, Sq, Sk, d, scale, *, lse=None, q_view=None, k_vie
     assert o_view is None
     o.copy_(out.to(F16))
     return o
+
+
+def attn_causal_fwd(q, k, v, o, B, H, S, d, scale, *, view=None):
+    vw = view or (H * d, S * H * d)
+    qh, kh, vh = (_heads(t, vw, B, S, H, d) for t in (q, k, v))
+    future = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), 1)
+    p = torch.softmax((scale * qh @ kh.transpose(-1, -2)).masked_fill(future, float("-inf")), dim=-1)
+    o.copy_((p @ vh).permute(0, 2, 1, 3).reshape(B * S, H * d).to(F16))
+    return o
+
+
+def quick_gelu(x, out=None):
+    xf = x.float()
+    return (xf * torch.sigmoid(1.702 * xf)).to(F16)
 
 
 def sam_relpos_qkv(qkv, qkv_bias, rel_h, rel_w, B, Hs, Ws, window, NH, d, DA, scale):

@@ -9,7 +9,7 @@ import torch
 import lgd_amd  # noqa: F401
 import ops_emul
 import sam_cases
-from lgd_amd import sam as lsam
+from lgd_amd import sam as lsam, vit
 
 transformers = pytest.importorskip("transformers")
 
@@ -24,9 +24,7 @@ def emulated_ops(monkeypatch):
     """Kernel calls -> torch restatement; storage dtype fp32 instead of fp16 so that the comparison isolates the algebra
     (with fp16 storage the same run differs from the fp32 Hugging Face module by the rounding noise of ~60 chained ops,
     which the GPU test bounds separately)."""
-    monkeypatch.setattr(lsam, "ops", ops_emul)
-    monkeypatch.setattr(lsam, "F16", torch.float32)
-    monkeypatch.setattr(ops_emul, "F16", torch.float32)
+    ops_emul.install(monkeypatch, lsam, vit)
 
 
 @pytest.mark.parametrize("points", [False, True])

@@ -15,7 +15,7 @@ import lgd_amd  # noqa: E402,F401
 import ops_emul  # noqa: E402
 import sam_cases  # noqa: E402
 import sam_refine_checks  # noqa: E402
-from lgd_amd import sam as lsam  # noqa: E402
+from lgd_amd import sam as lsam, vit  # noqa: E402
 
 transformers = pytest.importorskip("transformers")
 
@@ -23,9 +23,7 @@ transformers = pytest.importorskip("transformers")
 @pytest.fixture()
 def dsam(monkeypatch):
     monkeypatch.syspath_prepend(os.path.join(ROOT, "llm-groundeddiffusion_amd", "dropin"))
-    monkeypatch.setattr(lsam, "ops", ops_emul)
-    monkeypatch.setattr(lsam, "F16", torch.float32)
-    monkeypatch.setattr(ops_emul, "F16", torch.float32)
+    ops_emul.install(monkeypatch, lsam, vit)
     from models import sam as mod
     return mod
 

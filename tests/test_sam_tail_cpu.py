@@ -88,7 +88,7 @@ def test_batched_calls_equal_the_per_image_calls_with_host_stand_ins_for_the_two
     from scipy import ndimage
     import ops_emul
     import sam_tail_cases as tc
-    from lgd_amd import ops, sam as lsam
+    from lgd_amd import ops, sam as lsam, vit
 
     def host_tail(logits, iou, geom, target, grid, coarse, below_conf, below_iou, want_cand=True):
         picked = [tc.host_select(tc.host_candidates(logits[n], geom[n].tolist(), target, grid), iou[n].numpy(),
@@ -101,9 +101,7 @@ def test_batched_calls_equal_the_per_image_calls_with_host_stand_ins_for_the_two
         peaks = [np.unravel_index(s.argmax(), s.shape) for s in smooth]
         return (torch.from_numpy(np.stack([sam_refine.preprocess_mask(s, mask_th) for s in smooth]).astype(np.uint8)),
                 torch.tensor([[float(x * up_h), float(y * up_w)] for y, x in peaks]), None)
-    monkeypatch.setattr(lsam, "ops", ops_emul)
-    monkeypatch.setattr(lsam, "F16", torch.float32)
-    monkeypatch.setattr(ops_emul, "F16", torch.float32)
+    ops_emul.install(monkeypatch, lsam, vit)
     monkeypatch.setattr(ops, "sam_mask_tail", host_tail)
     monkeypatch.setattr(ops, "sam_attn_prompt", host_prompt)
     md = sam_refine.wrap_sam(sam_cases.build_refine_hf(transformers), "device", device="cpu")

@@ -19,6 +19,13 @@ the step entry points carry a hash of the CONTENTS of their coefficient table (t
 Every tensor handed to `ops._p`, `ops.gemm_desc`, `ops.copy_` or `ops.zero_` is kept alive for the whole run: otherwise
 the allocator reuses addresses and the renaming differs from run to run.
 
+The `clip`, `owlvit` and `sam` scenarios trace the towers outside the UNet: tiny configs (tests/owl_detect_cases.py,
+tests/sam_cases.py of the traced checkout) with the seeded state dicts of transformers' own modules; the CLIP forward with
+`output_hidden_states`, the OWL-ViT `__call__` (not `detect()`: its host read of the counts would read memory no kernel
+wrote) and the SAM `__call__` with box prompts and with point prompts (neither path reads a device result on the host,
+so both are traced to their end).  Without transformers they print that they were skipped.  A scenario that raises is
+reported with its exception and the run goes on.
+
 Not seen: work torch does by itself (plain `tensor.copy_` of a call's state), and graph replay; the GPU tests that compare
 graph replay with eager runs cover those.  The hashes change with every legitimate change of a plan or a tuning table:
 this is a tool for comparing two trees, not a test, and no expected hash is kept.
@@ -167,7 +174,43 @@ def scenarios(root):
         # what bench.py --full times per kernel: every launch sequence the sampler hands out, run once
         "profile_passes": lambda: [fn() for _, _, _, fn in gsm.profile_passes(32, 4, True, main_batches=(1, 2),
                                                                              guide_batches=(1, 2))],
+        **towers(root),
     }
+
+
+def towers(root):
+    """name -> callable for the CLIP, OWL-ViT and SAM towers, or name -> None without transformers."""
+    try:
+        import transformers
+    except ImportError:
+        return dict.fromkeys(("clip", "owlvit", "sam"))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import owl_detect_cases
+    import sam_cases
+    from lgd_amd import clip, owlvit, sam
+
+    def run_clip():
+        torch.manual_seed(0)
+        hf = transformers.CLIPTextModel(transformers.CLIPTextConfig(
+            vocab_size=1000, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4,
+            max_position_embeddings=16, eos_token_id=2, bos_token_id=998, pad_token_id=0))
+        ids = torch.randint(10, 998, (2, 16), generator=torch.Generator().manual_seed(1))
+        clip.from_hf(hf, "cpu")(ids, output_hidden_states=True)
+
+    def run_owlvit():
+        cfg = owl_detect_cases.tiny_hf_config()
+        torch.manual_seed(0)
+        hf = owl_detect_cases.redraw_weights(transformers.OwlViTForObjectDetection(cfg), seed=3)
+        pv, ids = owl_detect_cases.model_inputs(cfg, 2, 3, seed=4, zero_rows=(4,))
+        owlvit.from_hf(hf, "cpu")(pixel_values=pv, input_ids=ids, attention_mask=(ids > 0).long())
+
+    def run_sam():
+        cfg = sam_cases.small_config(transformers)
+        hf = sam_cases.build_hf(transformers, cfg)
+        model = sam.HipSamModel(sam.SamConfig.from_hf(cfg), hf.state_dict(), device="cpu")
+        for points in (False, True):
+            model(**sam_cases.inputs(cfg, B=2, P=2, points=points))
+    return {"clip": run_clip, "owlvit": run_owlvit, "sam": run_sam}
 
 
 def main():
@@ -183,7 +226,14 @@ def main():
     for name, fn in todo.items():
         if args.only and name not in args.only:
             continue
-        lines = rec.section(fn)
+        if fn is None:
+            print(f"{name}: skipped (needs transformers)")
+            continue
+        try:
+            lines = rec.section(fn)
+        except Exception as e:
+            print(f"{name}: raised {type(e).__name__}: {e}")
+            continue
         body = "\n".join(lines) + "\n"
         print(f"{name}: {len(lines)} lines, sha256 {hashlib.sha256(body.encode()).hexdigest()[:16]}")
         if args.dump:
