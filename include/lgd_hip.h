@@ -144,14 +144,22 @@ int lgd_gemm_tile(int index, int* code, int* bm, int* bn, char* name, int name_c
 
 /* ---------------------------------------------------------------------------------------------
  * conv_in: latents NCHW fp32 (B,4,L,L) -> [B][L*L][Cout] fp16, 3x3 pad 1 (unet_2d_condition.py:860)
- * w: [Cout][3][3][Cin] fp16, bias fp32.
+ * w: [Cout][3][3][Cin] fp16, bias fp32 [Cout] or NULL.
+ * Preconditions (else LGD_ERR_ARG, before any launch): x_nchw, w, y non-NULL; B, L >= 1; 1 <= Cin <= 8; Cout >= 1;
+ * x_nchw / bias 4-byte and w / y 2-byte aligned (scalar accesses); y overlaps none of x_nchw, w, bias (no aliasing).
+ * LGD_ERR_UNSUPPORTED when the transposed filter and the pixel patches do not fit 64 KB of LDS.
  * ------------------------------------------------------------------------------------------- */
 int lgd_conv_in_f16(const float* x_nchw, const void* w, const float* bias, void* y, int B, int Cin,
                     int L, int Cout, void* stream);
 /* conv_out: [B][L*L][Cin] fp16 (already GroupNorm+SiLU'd) -> NCHW fp32 (B,Cout,L,L), times
  * out_scale (unet_2d_condition.py:972-975).  w: [Cout][3][3][Cin] fp16.  Called with the
  * flipped/transposed conv_in weights it is also conv_in's input gradient (the latent gradient of
- * pipelines.py:56; out_scale then undoes the fp16 gradient scaling). */
+ * pipelines.py:56; out_scale then undoes the fp16 gradient scaling).
+ *   y[b][co][oy][ox] = out_scale * (bias[co] + sum_{ky,kx,ci} x[b][oy+ky-1][ox+kx-1][ci] * w[co][ky][kx][ci])
+ * (taps outside the map are zero; bias fp32 [Cout] or NULL = 0).
+ * Preconditions (else LGD_ERR_ARG, before any launch): x, w, y_nchw non-NULL; B, L >= 1; Cin >= 8 and Cin % 8 == 0;
+ * x and w 16-byte aligned (read as 8-half vectors), bias and y_nchw 4-byte; y_nchw overlaps none of x, w, bias (no
+ * aliasing).  Cout outside {4, 8}: LGD_ERR_UNSUPPORTED. */
 int lgd_conv_out_f16(const void* x, const void* w, const float* bias, float* y_nchw, int B, int Cin,
                      int L, int Cout, float out_scale, void* stream);
 
@@ -352,20 +360,37 @@ int lgd_attn_variant(int index, int* code, int* env_only, char* name, int name_c
 /* ---------------------------------------------------------------------------------------------
  * Elementwise pieces.
  * ------------------------------------------------------------------------------------------- */
-/* GEGLU backward (attention.py:333-335): h = proj(x) packed [16 value|16 gate] blocks, width 2*n;
- * gy [rows][n] -> gh [rows][2n] in the same packed layout. */
+/* The preconditions an entry point of this section can see from its arguments — NULL-ness, alignment, counts,
+ * divisibility, and the overlap of ranges whose extent the arguments give — are checked on the host, before any runtime
+ * call; a call that misses one answers LGD_ERR_ARG and launches nothing.  The rest is the caller's duty and is NOT
+ * checked: inputs are finite unless an entry point says otherwise; operands whose extent is not an argument (a
+ * coefficient table, frozen_ref, hist, the table of lgd_select_row_f32) are large enough for the row or step the device
+ * index selects and share no byte with an output (x_out, x0_prev and hist against frozen_ref and hist; out against the
+ * table).
+ * "16-byte aligned": the operand moves as vectors of 8 halfs or 4 floats.  "No aliasing": the output range, whose extent
+ * the arguments give, shares no byte with an input range.  "y may be x": the output is the input itself or a range apart
+ * from it; a partial overlap is refused. */
+/* GEGLU backward (attention.py:333-335): h = proj(x) packed [16 value|16 gate] blocks, width 2*n: value j of a row sits
+ * at h[(j / 16) * 32 + j % 16], its gate 16 elements behind;  gy [rows][n] -> gh [rows][2n] in the same packed layout:
+ *   gh_value[j] = gy[j] * gelu(gate[j]);  gh_gate[j] = gy[j] * value[j] * gelu'(gate[j])      (gelu: the erf form)
+ * rows >= 1; n >= 16 and n % 16 == 0; h, gy, gh non-NULL and 16-byte aligned; no aliasing (gh against h and gy). */
 int lgd_geglu_bwd_f16(const void* h, const void* gy, void* gh, int64_t rows, int n, void* stream);
-/* GEGLU forward on a stored packed pre-activation h [rows][2n] -> y [rows][n] (grad-enabled pass). */
+/* GEGLU forward on a stored packed pre-activation h [rows][2n] -> y [rows][n] (grad-enabled pass):
+ *   y[j] = value[j] * gelu(gate[j]).
+ * rows >= 1; n >= 16 and n % 16 == 0; h, y non-NULL and 16-byte aligned; no aliasing. */
 int lgd_geglu_fwd_f16(const void* h, void* y, int64_t rows, int n, void* stream);
-/* y = x * sigmoid(1.702 x) (fp16): CLIP text encoder MLP activation ([ext] transformers CLIPMLP, "quick_gelu"). */
+/* y = x * sigmoid(1.702 x) (fp16): CLIP text encoder MLP activation ([ext] transformers CLIPMLP, "quick_gelu").
+ * n >= 1 and n % 8 == 0; x, y non-NULL and 16-byte aligned; y may be x. */
 int lgd_quick_gelu_f16(const void* x, void* y, int64_t n, void* stream);
 /* NCHW fp32 (B, C <= 8, HW) -> channels-last fp16 [B*HW][8]: channels 0..C-1 = fp16(x), channels C..2C-1 (when 2C <= 8)
  * = fp16(x - fp16(x)), the rest zero.  Input of the UNet's conv_in (unet_2d_condition.py:860, 4 -> 320 channels) when
- * it runs as an implicit GEMM with K = 9*8 and the filter duplicated over the remainder channels. */
+ * it runs as an implicit GEMM with K = 9*8 and the filter duplicated over the remainder channels.
+ * B, HW >= 1; 1 <= C <= 8; x, y non-NULL, x 4-byte and y 16-byte aligned; no aliasing. */
 int lgd_nchw_to_nhwc8_f16(const float* x, void* y, int B, int C, int HW, void* stream);
-/* y = a + b (fp16), n elements (gradient fan-in / residual). */
+/* y = a + b (fp16, one rounding of the sum; an overflowing sum is +-inf), n elements (gradient fan-in / residual).
+ * n >= 1 and n % 8 == 0; a, b, y non-NULL and 16-byte aligned; y may be a, b or both (a and b may overlap freely). */
 int lgd_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
-/* y = alpha * x (fp16) */
+/* y = alpha * x (fp16).  n >= 1 and n % 8 == 0; x, y non-NULL and 16-byte aligned; y may be x. */
 int lgd_scale_f16(const void* x, void* y, float alpha, int64_t n, void* stream);
 /* uint8 HWC images -> the 8-channel fp16 operand of the VAE encoder's conv_in (additive export: LGD_ABI_VERSION stays
  * 12) — models/pipelines.py:99-105 of the reference (`encode`: astype(float32) / 255, transpose to NCHW, 2 x - 1)
@@ -385,9 +410,13 @@ int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, void* y, int 
 int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int B, int z, int HW, float scale,
                        void* stream);
 /* y = softmax(scale * x) over the last dim, rows x n fp16 (VAE decoder mid-block attention, [ext]
- * AutoencoderKL; pipelines.py:117-127 decode). */
+ * AutoencoderKL; pipelines.py:117-127 decode).  Elements may be -inf (masked: probability 0) as long as one element of
+ * every row is finite; +inf and NaN are not inputs.
+ * rows >= 1; n >= 8 and n % 8 == 0; x, y non-NULL and 16-byte aligned; y may be x. */
 int lgd_softmax_rows_f16(const void* x, void* y, int64_t rows, int n, float scale, void* stream);
-/* sum over the 2x2 children of a nearest-2x upsampling: gy [B][2H*2W][C] -> gx [B][H*W][C] */
+/* sum over the 2x2 children of a nearest-2x upsampling: gy [B][2H*2W][C] -> gx [B][H*W][C],
+ *   gx[b][y][x][c] = sum_{dy,dx < 2} gy[b][2y+dy][2x+dx][c]      (fp32 sum, one fp16 rounding).
+ * B, H, W >= 1; C >= 8 and C % 8 == 0; gy, gx non-NULL and 16-byte aligned; no aliasing. */
 int lgd_upsample2x_bwd_f16(const void* gy, void* gx, int B, int H, int W, int C, void* stream);
 
 /* Classifier-free guidance + DDIM (eta=0) step + frozen-mask blend + latent history in one pass
@@ -398,7 +427,11 @@ int lgd_upsample2x_bwd_f16(const void* gy, void* gx, int B, int H, int W, int C,
  *   hist[step+1] = x'  (save_all_latents) when hist != NULL.   x_out may alias x.
  * coef_table: device fp32 [T][4] = {a_t, a_prev, guidance_scale, v_prediction flag}.
  * dyn: device int32[2] = {step, frozen_steps} — read on the device so that one captured hipGraph
- * replays for every step and for both stages. */
+ * replays for every step and for both stages.
+ * Preconditions: eps, x, x_out, coef_table, dyn non-NULL; B, C, HW >= 1; frozen_ref and mask both given or both NULL
+ * (one without the other is refused, not skipped); hist optional; every pointer 4-byte aligned.  x_out may be x; x_out
+ * overlaps neither eps nor mask.  Not checked (the step count is not an argument): frozen_ref and hist hold step + 2
+ * latents and share no byte with x_out or with each other. */
 int lgd_cfg_ddim_step_f32(const float* eps, const float* x, float* x_out, const float* coef_table,
                           const int32_t* dyn, const float* frozen_ref, const float* mask, float* hist,
                           int B, int C, int HW, void* stream);
@@ -407,7 +440,9 @@ int lgd_cfg_ddim_step_f32(const float* eps, const float* x, float* x_out, const 
  * current data prediction x0 and the previous one:
  *   m = eu + gs*(ec-eu);  x0 = c0 x + c1 m;  x' = A x + B x0 + C x0_prev;  x0_prev <- x0;  blend / hist as above.
  * coef_table: device fp32 [T][8] = {c0, c1, A, B, C, guidance_scale, 0, 0} (host: scheduler.DPMSolverMultistepScheduler).
- * x0_prev: fp32 state buffer (B,C,L,L), read only when C != 0. */
+ * x0_prev: fp32 state buffer (B,C,L,L), read only when C != 0, always rewritten.
+ * Preconditions: those of lgd_cfg_ddim_step_f32, and x0_prev non-NULL, 4-byte aligned and apart from eps, x, x_out and
+ * mask. */
 int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, float* x0_prev,
                                const float* coef_table, const int32_t* dyn, const float* frozen_ref,
                                const float* mask, float* hist, int B, int C, int HW, void* stream);
@@ -477,16 +512,23 @@ int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float* latent, f
 /* Model-input scaling of sigma-space samplers — [ext] diffusers EulerDiscreteScheduler.scale_model_input, which the
  * SDXL-refiner pass applies before every UNet call (generation/sdxl_refinement.py:29 -> StableDiffusionXLImg2ImgPipeline):
  *   out[r][i] = x[i] * table[dyn[0] * row_stride + col]   for r < reps   (reps = 2: the CFG pair reads one latent).
- * The factor is read on the device, so the call sits inside a captured hipGraph that replays for every step. */
+ * The factor is read on the device, so the call sits inside a captured hipGraph that replays for every step.
+ * x, out, table, dyn non-NULL and 4-byte aligned; n, reps >= 1; 0 <= col < row_stride; no aliasing (out [reps][n]
+ * against x). */
 int lgd_scale_rows_f32(const float* x, float* out, const float* table, const int32_t* dyn, int row_stride, int col,
                        int64_t n, int reps, void* stream);
 /* guidance latent update (pipelines.py:60-69): x -= active[i/per_sample] * coef_table[*step_idx][col] * g.
  * active (device fp32 per image, or NULL = all on) emulates the per-image `while` exit of
- * pipelines.py:30 when several layouts are guided in one batch. */
+ * pipelines.py:30 when several layouts are guided in one batch.
+ * g, x, coef_table, step_idx non-NULL; active optional; every pointer 4-byte aligned; n >= 1; col in 0..3 (the table
+ * has four columns); per_sample >= 0, 0 standing for n (one image); with active, n % per_sample == 0.  x is updated in
+ * place and overlaps no byte of g. */
 int lgd_axpy_f32(const float* g, float* x, const float* coef_table, const int32_t* step_idx, int col,
                  const float* active, int64_t per_sample, int64_t n, void* stream);
 /* copy row `*idx` (device int32) of a [T][n] fp32 table into out[n] — per-step time-embedding
- * bias of every resnet without changing any kernel argument (graph-replay friendly). */
+ * bias of every resnet without changing any kernel argument (graph-replay friendly).  Bit-exact.
+ * table, idx, out non-NULL and 4-byte aligned; n >= 1.  Not checked (the table's extent is not an argument): out lies
+ * outside the table. */
 int lgd_select_row_f32(const float* table, const int32_t* idx, float* out, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -495,7 +537,8 @@ int lgd_select_row_f32(const float* table, const int32_t* idx, float* out, int n
  * ------------------------------------------------------------------------------------------- */
 #define LGD_ACT_GELU 1 /* exact (erf) GELU: SamMLPBlock of the image encoder, mask-decoder upscaling */
 #define LGD_ACT_RELU 2 /* SamMLPBlock / SamFeedForward of the mask decoder */
-/* y = act(x), fp16, n % 8 == 0. */
+/* y = act(x), fp16.  n >= 1 and n % 8 == 0; x, y non-NULL and 16-byte aligned; mode one of the two above; y may be x;
+ * inputs finite; all else LGD_ERR_ARG before any launch. */
 int lgd_act_f16(const void* x, void* y, int64_t n, int mode, void* stream);
 /* Window partition + decomposed relative-position bias of SamVisionAttention, folded into the attention operands.
  * qkv [B*Hs*Ws][3*NH*d] fp16 (fused projection, raster token order), qkv_bias fp32 [3*NH*d] (value of the zero-padded

@@ -2,6 +2,7 @@
 // NCHW fp32 <-> channels-last fp16), elementwise gradient helpers, and the fused per-step update
 // (classifier-free guidance + DDIM + frozen-mask blend).
 #include "common.h"
+#include "contract.h"
 #include "../../include/lgd_hip.h"
 
 namespace {
@@ -704,6 +705,28 @@ __global__ __launch_bounds__(256) void select_row_kernel(const float* __restrict
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = table[r * n + i];
 }
 
+using lgd_contract::misaligned;
+using lgd_contract::overlaps;
+using lgd_contract::partly_overlaps;
+
+// y = f(x) over n fp16 elements in 16-byte vectors; y is x itself or a range apart (lgd_hip.h)
+inline bool bad_unary_f16(const void* x, const void* y, int64_t n) {
+  return !x || !y || n < 1 || (n % 8) || misaligned(x, 16) || misaligned(y, 16) || partly_overlaps(y, x, n * 2);
+}
+
+// what the two fused sampler steps share (lgd_hip.h): fp32 scalars, x_out is x itself or apart, the blend takes both of
+// frozen_ref and mask; x_out overlaps none of the inputs whose extent the arguments give
+inline bool bad_step_f32(const float* eps, const float* x, const float* x_out, const float* coef_table, const int32_t* dyn,
+                         const float* frozen_ref, const float* mask, const float* hist, int B, int C, int HW) {
+  if (!eps || !x || !x_out || !coef_table || !dyn || B < 1 || C < 1 || HW < 1) return true;
+  if ((frozen_ref != nullptr) != (mask != nullptr)) return true;
+  if (misaligned(eps, 4) || misaligned(x, 4) || misaligned(x_out, 4) || misaligned(coef_table, 4) || misaligned(dyn, 4) ||
+      misaligned(frozen_ref, 4) || misaligned(mask, 4) || misaligned(hist, 4))
+    return true;
+  const int64_t nb = (int64_t)B * C * HW * 4;
+  return partly_overlaps(x_out, x, nb) || overlaps(x_out, nb, eps, 2 * nb) || overlaps(x_out, nb, mask, (int64_t)B * HW * 4);
+}
+
 inline int ew_blocks(long n) {
   long b = (n + 255) / 256;
   if (b > 2048) b = 2048;
@@ -715,11 +738,18 @@ inline int ew_blocks(long n) {
 
 extern "C" int lgd_conv_in_f16(const float* x_nchw, const void* w, const float* bias, void* y, int B,
                                int Cin, int L, int Cout, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (Cin < 1 || Cin > 8 || Cout < 1) return LGD_ERR_ARG;
+  if (!x_nchw || !w || !y || B < 1 || L < 1 || Cin < 1 || Cin > 8 || Cout < 1) return LGD_ERR_ARG;
+  if (misaligned(x_nchw, 4) || misaligned(w, 2) || misaligned(bias, 4) || misaligned(y, 2)) return LGD_ERR_ARG;
   const int K = 9 * Cin;
+  {
+    const int64_t yb = (int64_t)B * L * L * Cout * 2;
+    if (overlaps(y, yb, x_nchw, (int64_t)B * Cin * L * L * 4) || overlaps(y, yb, w, (int64_t)Cout * K * 2) ||
+        overlaps(y, yb, bias, (int64_t)Cout * 4))
+      return LGD_ERR_ARG;
+  }
   size_t smem = (size_t)((K * Cout * 2 + 15) & ~15) + (size_t)CI_PIX * K * 4;
   if (smem > 64 * 1024) return LGD_ERR_UNSUPPORTED;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   long npix = (long)B * L * L;
   hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)((npix + CI_PIX - 1) / CI_PIX)), dim3(256), smem,
                      reinterpret_cast<hipStream_t>(stream), x_nchw, (const half_t*)w, bias,
@@ -729,25 +759,32 @@ extern "C" int lgd_conv_in_f16(const float* x_nchw, const void* w, const float* 
 
 extern "C" int lgd_conv_out_f16(const void* x, const void* w, const float* bias, float* y_nchw, int B,
                                 int Cin, int L, int Cout, float out_scale, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if ((Cin % 8) || Cin < 8) return LGD_ERR_ARG;
+  if (!x || !w || !y_nchw || B < 1 || L < 1 || (Cin % 8) || Cin < 8) return LGD_ERR_ARG;
+  if (misaligned(x, 16) || misaligned(w, 16) || misaligned(bias, 4) || misaligned(y_nchw, 4)) return LGD_ERR_ARG;
   long npix = (long)B * L * L;
+  if (Cout == 4 || Cout == 8) {  // the extent of y_nchw is known
+    const int64_t yb = (int64_t)npix * Cout * 4;
+    if (overlaps(y_nchw, yb, x, (int64_t)npix * Cin * 2) || overlaps(y_nchw, yb, w, (int64_t)Cout * 9 * Cin * 2) ||
+        overlaps(y_nchw, yb, bias, (int64_t)Cout * 4))
+      return LGD_ERR_ARG;
+  }
+  if (Cout != 4 && Cout != 8) return LGD_ERR_UNSUPPORTED;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   dim3 grid((unsigned)((npix + 3) / 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (Cout == 4)
     hipLaunchKernelGGL((conv_out_kernel<4>), grid, dim3(256), 0, st, (const half_t*)x,
                        (const half_t*)w, bias, y_nchw, B, Cin, L, out_scale);
-  else if (Cout == 8)
+  else
     hipLaunchKernelGGL((conv_out_kernel<8>), grid, dim3(256), 0, st, (const half_t*)x,
                        (const half_t*)w, bias, y_nchw, B, Cin, L, out_scale);
-  else
-    return LGD_ERR_UNSUPPORTED;
   return lgd_check_launch();
 }
 
 extern "C" int lgd_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream) {
+  if (!a || !b || !y || n < 1 || (n % 8) || misaligned(a, 16) || misaligned(b, 16) || misaligned(y, 16)) return LGD_ERR_ARG;
+  if (partly_overlaps(y, a, n * 2) || partly_overlaps(y, b, n * 2)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 8) return LGD_ERR_ARG;
   hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n / 8)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)a, (const half_t*)b,
                      (half_t*)y, (long)(n / 8));
@@ -755,8 +792,8 @@ extern "C" int lgd_add_f16(const void* a, const void* b, void* y, int64_t n, voi
 }
 
 extern "C" int lgd_scale_f16(const void* x, void* y, float alpha, int64_t n, void* stream) {
+  if (bad_unary_f16(x, y, n)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 8) return LGD_ERR_ARG;
   hipLaunchKernelGGL(scale_kernel, dim3(ew_blocks(n / 8)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)x, (half_t*)y, alpha,
                      (long)(n / 8));
@@ -764,9 +801,10 @@ extern "C" int lgd_scale_f16(const void* x, void* y, float alpha, int64_t n, voi
 }
 
 extern "C" int lgd_nchw_to_nhwc8_f16(const float* x, void* y, int B, int C, int HW, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (B < 1 || C < 1 || C > 8 || HW < 1) return LGD_ERR_ARG;
+  if (!x || !y || B < 1 || C < 1 || C > 8 || HW < 1 || misaligned(x, 4) || misaligned(y, 16)) return LGD_ERR_ARG;
   const long total = (long)B * HW;
+  if (overlaps(y, (int64_t)total * 16, x, (int64_t)total * C * 4)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(ew_blocks(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
                      (half_t*)y, C, (long)HW, total);
   return lgd_check_launch();
@@ -798,16 +836,17 @@ extern "C" int lgd_vae_sample_f32(const void* moments, const float* noise, float
 }
 
 extern "C" int lgd_quick_gelu_f16(const void* x, void* y, int64_t n, void* stream) {
+  if (bad_unary_f16(x, y, n)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 8) return LGD_ERR_ARG;
   hipLaunchKernelGGL(quick_gelu_kernel, dim3(ew_blocks(n / 8)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)x, (half_t*)y, (long)(n / 8));
   return lgd_check_launch();
 }
 
 extern "C" int lgd_geglu_fwd_f16(const void* h, void* y, int64_t rows, int n, void* stream) {
+  if (!h || !y || rows < 1 || n < 16 || (n % 16) || misaligned(h, 16) || misaligned(y, 16)) return LGD_ERR_ARG;
+  if (overlaps(y, rows * n * 2, h, rows * n * 4)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 16) return LGD_ERR_ARG;
   hipLaunchKernelGGL(geglu_fwd_kernel, dim3(ew_blocks(rows * (n / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)h, (half_t*)y, (long)rows, n);
   return lgd_check_launch();
@@ -815,8 +854,10 @@ extern "C" int lgd_geglu_fwd_f16(const void* h, void* y, int64_t rows, int n, vo
 
 extern "C" int lgd_geglu_bwd_f16(const void* h, const void* gy, void* gh, int64_t rows, int n,
                                  void* stream) {
+  if (!h || !gy || !gh || rows < 1 || n < 16 || (n % 16) || misaligned(h, 16) || misaligned(gy, 16) || misaligned(gh, 16))
+    return LGD_ERR_ARG;
+  if (overlaps(gh, rows * n * 4, h, rows * n * 4) || overlaps(gh, rows * n * 4, gy, rows * n * 2)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 16) return LGD_ERR_ARG;
   hipLaunchKernelGGL(geglu_bwd_kernel, dim3(ew_blocks(rows * (n / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)h, (const half_t*)gy,
                      (half_t*)gh, (long)rows, n);
@@ -825,8 +866,12 @@ extern "C" int lgd_geglu_bwd_f16(const void* h, const void* gy, void* gh, int64_
 
 extern "C" int lgd_upsample2x_bwd_f16(const void* gy, void* gx, int B, int H, int W, int C,
                                       void* stream) {
+  if (!gy || !gx || B < 1 || H < 1 || W < 1 || C < 8 || (C % 8) || misaligned(gy, 16) || misaligned(gx, 16)) return LGD_ERR_ARG;
+  {
+    const int64_t xb = (int64_t)B * H * W * C * 2;
+    if (overlaps(gx, xb, gy, 4 * xb)) return LGD_ERR_ARG;
+  }
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (C % 8) return LGD_ERR_ARG;
   hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(ew_blocks((long)B * H * W * (C / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)gy, (half_t*)gx, B, H, W,
                      C);
@@ -835,8 +880,8 @@ extern "C" int lgd_upsample2x_bwd_f16(const void* gy, void* gx, int B, int H, in
 
 extern "C" int lgd_softmax_rows_f16(const void* x, void* y, int64_t rows, int n, float scale,
                                     void* stream) {
+  if (rows < 1 || n < 8 || (n % 8) || bad_unary_f16(x, y, rows * n)) return LGD_ERR_ARG;  // every row starts on a vector
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n % 8 || rows < 1) return LGD_ERR_ARG;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const half_t*)x, (half_t*)y, (long)rows, n,
                      scale);
@@ -847,6 +892,7 @@ extern "C" int lgd_cfg_ddim_step_f32(const float* eps, const float* x, float* x_
                                      const float* coef_table, const int32_t* dyn,
                                      const float* frozen_ref, const float* mask, float* hist, int B,
                                      int C, int HW, void* stream) {
+  if (bad_step_f32(eps, x, x_out, coef_table, dyn, frozen_ref, mask, hist, B, C, HW)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3(ew_blocks((long)B * C * HW)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), eps, x, x_out, coef_table, dyn, frozen_ref,
@@ -857,8 +903,15 @@ extern "C" int lgd_cfg_ddim_step_f32(const float* eps, const float* x, float* x_
 extern "C" int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, float* x0_prev,
                                           const float* coef_table, const int32_t* dyn, const float* frozen_ref,
                                           const float* mask, float* hist, int B, int C, int HW, void* stream) {
+  if (!x0_prev || misaligned(x0_prev, 4) || bad_step_f32(eps, x, x_out, coef_table, dyn, frozen_ref, mask, hist, B, C, HW))
+    return LGD_ERR_ARG;
+  {
+    const int64_t nb = (int64_t)B * C * HW * 4;  // the state is read and rewritten: apart from every other operand
+    if (overlaps(x0_prev, nb, x, nb) || overlaps(x0_prev, nb, x_out, nb) || overlaps(x0_prev, nb, eps, 2 * nb) ||
+        overlaps(x0_prev, nb, mask, (int64_t)B * HW * 4))
+      return LGD_ERR_ARG;
+  }
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (!eps || !x || !x_out || !x0_prev || !coef_table || !dyn) return LGD_ERR_ARG;
   hipLaunchKernelGGL(cfg_multistep_kernel, dim3(ew_blocks((long)B * C * HW)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), eps, x, x_out, x0_prev, coef_table, dyn, frozen_ref,
                      mask, hist, B, C * HW, HW);
@@ -938,8 +991,10 @@ extern "C" int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float
 
 extern "C" int lgd_scale_rows_f32(const float* x, float* out, const float* table, const int32_t* dyn, int row_stride,
                                   int col, int64_t n, int reps, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!x || !out || !table || !dyn || n < 1 || reps < 1 || col < 0 || col >= row_stride) return LGD_ERR_ARG;
+  if (misaligned(x, 4) || misaligned(out, 4) || misaligned(table, 4) || misaligned(dyn, 4) || overlaps(out, reps * n * 4, x, n * 4))
+    return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(scale_rows_kernel, dim3(ew_blocks(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, out,
                      table, dyn, row_stride, col, (long)n, reps);
   return lgd_check_launch();
@@ -948,6 +1003,11 @@ extern "C" int lgd_scale_rows_f32(const float* x, float* out, const float* table
 extern "C" int lgd_axpy_f32(const float* g, float* x, const float* coef_table,
                             const int32_t* step_idx, int col, const float* active, int64_t per_sample,
                             int64_t n, void* stream) {
+  if (!g || !x || !coef_table || !step_idx || n < 1 || col < 0 || col > 3 || per_sample < 0) return LGD_ERR_ARG;
+  if (misaligned(g, 4) || misaligned(x, 4) || misaligned(coef_table, 4) || misaligned(step_idx, 4) || misaligned(active, 4))
+    return LGD_ERR_ARG;
+  if (active && per_sample > 0 && (n % per_sample)) return LGD_ERR_ARG;  // whole images: n / per_sample entries of active
+  if (overlaps(x, n * 4, g, n * 4)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(axpy_kernel, dim3(ew_blocks(n)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), g, x, coef_table, step_idx, col, active,
@@ -957,6 +1017,7 @@ extern "C" int lgd_axpy_f32(const float* g, float* x, const float* coef_table,
 
 extern "C" int lgd_select_row_f32(const float* table, const int32_t* idx, float* out, int n,
                                   void* stream) {
+  if (!table || !idx || !out || n < 1 || misaligned(table, 4) || misaligned(idx, 4) || misaligned(out, 4)) return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(select_row_kernel, dim3(ew_blocks(n)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), table, idx, out, n);

@@ -15,6 +15,7 @@
 //  * sam_window_merge_kernel — the inverse gather: window order -> raster order, padding and extra columns dropped.
 //  * act_kernel — exact (erf) GELU and ReLU on fp16 vectors (encoder MLP / mask-decoder MLPs).
 #include "common.h"
+#include "contract.h"
 #include "../../include/lgd_hip.h"
 
 namespace {
@@ -147,8 +148,10 @@ extern "C" int lgd_sam_window_merge_f16(const void* oa, void* out, int B, int Hs
 }
 
 extern "C" int lgd_act_f16(const void* x, void* y, int64_t n, int mode, void* stream) {
+  if (!x || !y || n < 1 || (n % 8) || lgd_contract::misaligned(x, 16) || lgd_contract::misaligned(y, 16) ||
+      lgd_contract::partly_overlaps(y, x, n * 2) || (mode != LGD_ACT_GELU && mode != LGD_ACT_RELU))
+    return LGD_ERR_ARG;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n < 0 || (n % 8)) return LGD_ERR_ARG;
   long b = (n / 8 + 255) / 256;
   if (b > 2048) b = 2048;
   if (b < 1) b = 1;

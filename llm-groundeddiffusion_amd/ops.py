@@ -30,6 +30,20 @@ def _call(name, *args):
     _lib.check(rc, name)
 
 
+def _operands(fn, *specs):
+    """What the library cannot see from an address: every (name, tensor, dtype, element count) of `specs` is a contiguous
+    tensor of that dtype with that many elements (count None: any; tensor None: an optional operand left out)."""
+    for name, t, dtype, count in specs:
+        if t is None:
+            continue
+        if t.dtype != dtype:
+            raise RuntimeError(f"{fn}: {name} is {t.dtype}, the kernel reads {dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {name} is not contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+        if count is not None and t.numel() != count:
+            raise RuntimeError(f"{fn}: {name} holds {t.numel()} elements, the call addresses {count}")
+
+
 def set_option(name: str, value: int):
     """Kernel-variant switch of the library (lgd_set_option): e.g. set_option("attn32", 0 | 1 | 2)."""
     _call("lgd_set_option", name.encode(), int(value))
@@ -401,6 +415,8 @@ def conv_in(x_nchw, w, bias, out=None):
     Cout = w.shape[0]
     if out is None:
         out = torch.empty((B * L * L, Cout), device=x_nchw.device, dtype=F16)
+    _operands("conv_in", ("x", x_nchw, F32, B * Cin * L * L), ("w", w, F16, Cout * 9 * Cin), ("bias", bias, F32, Cout),
+              ("out", out, F16, B * L * L * Cout))
     _call("lgd_conv_in_f16", _p(x_nchw), _p(w), _p(bias), _p(out), B, Cin, L, Cout, _stream())
     return out
 
@@ -410,6 +426,7 @@ def nchw_to_nhwc8(x_nchw, out=None):
     B, C_, H, W = x_nchw.shape
     if out is None:
         out = torch.empty((B * H * W, 8), device=x_nchw.device, dtype=F16)
+    _operands("nchw_to_nhwc8", ("x", x_nchw, F32, None), ("out", out, F16, B * H * W * 8))
     _prof("nchw_to_nhwc8_kernel", 4.0 * x_nchw.numel() + 2.0 * out.numel(),
           lambda: _call("lgd_nchw_to_nhwc8_f16", _p(x_nchw), _p(out), B, C_, H * W, _stream()))
     return out
@@ -455,6 +472,8 @@ def conv_out(x, w, bias, B, L, out=None, out_scale=1.0):
     Cout = w.shape[0]
     if out is None:
         out = torch.empty((B, Cout, L, L), device=x.device, dtype=F32)
+    _operands("conv_out", ("x", x, F16, B * L * L * Cin), ("w", w, F16, Cout * 9 * Cin), ("bias", bias, F32, Cout),
+              ("out", out, F32, B * Cout * L * L))
     _prof("conv_out_kernel", 2.0 * x.numel() + 4.0 * out.numel(),
           lambda: _call("lgd_conv_out_f16", _p(x), _p(w), _p(bias), _p(out), B, Cin, L, Cout, float(out_scale), _stream()),
           flops=2.0 * B * L * L * Cout * 9 * Cin)
@@ -719,6 +738,7 @@ def attn_plan(op, B, H, Sq, Sk, d, *, sk_grad=None, probs=False, causal=False, p
 def quick_gelu(x, out=None):
     if out is None:
         out = torch.empty_like(x)
+    _operands("quick_gelu", ("x", x, F16, None), ("out", out, F16, x.numel()))
     _call("lgd_quick_gelu_f16", _p(x), _p(out), x.numel(), _stream())
     return out
 
@@ -730,6 +750,7 @@ def act(x, mode, out=None):
     """Exact GELU / ReLU on an fp16 tensor (SAM encoder and mask-decoder MLPs)."""
     if out is None:
         out = torch.empty_like(x)
+    _operands("act", ("x", x, F16, None), ("out", out, F16, x.numel()))
     _call("lgd_act_f16", _p(x), _p(out), x.numel(), int(mode), _stream())
     return out
 
@@ -771,6 +792,7 @@ def geglu_bwd(h, gy, gh=None):
     rows, n2 = h.shape
     if gh is None:
         gh = torch.empty_like(h)
+    _operands("geglu_bwd", ("h", h, F16, None), ("gy", gy, F16, rows * (n2 // 2)), ("gh", gh, F16, rows * n2))
     _prof("geglu_bwd_kernel", 2.0 * rows * (n2 + n2 // 2 + n2),
           lambda: _call("lgd_geglu_bwd_f16", _p(h), _p(gy), _p(gh), rows, n2 // 2, _stream()))
     return gh
@@ -780,6 +802,7 @@ def geglu_fwd(h, out=None):
     rows, n2 = h.shape
     if out is None:
         out = torch.empty((rows, n2 // 2), device=h.device, dtype=F16)
+    _operands("geglu_fwd", ("h", h, F16, None), ("out", out, F16, rows * (n2 // 2)))
     _prof("geglu_fwd_kernel", 2.0 * rows * (n2 + n2 // 2),
           lambda: _call("lgd_geglu_fwd_f16", _p(h), _p(out), rows, n2 // 2, _stream()))
     return out
@@ -789,6 +812,7 @@ def softmax_rows(x, scale=1.0, out=None):
     rows, n = x.shape
     if out is None:
         out = torch.empty_like(x)
+    _operands("softmax_rows", ("x", x, F16, None), ("out", out, F16, rows * n))
     _call("lgd_softmax_rows_f16", _p(x), _p(out), rows, n, float(scale), _stream())
     return out
 
@@ -796,6 +820,7 @@ def softmax_rows(x, scale=1.0, out=None):
 def add(a, b, out=None):
     if out is None:
         out = torch.empty_like(a)
+    _operands("add", ("a", a, F16, None), ("b", b, F16, a.numel()), ("out", out, F16, a.numel()))
     _prof("add_kernel", 6.0 * a.numel(), lambda: _call("lgd_add_f16", _p(a), _p(b), _p(out), a.numel(), _stream()))
     return out
 
@@ -803,6 +828,7 @@ def add(a, b, out=None):
 def scale(x, alpha, out=None):
     if out is None:
         out = torch.empty_like(x)
+    _operands("scale", ("x", x, F16, None), ("out", out, F16, x.numel()))
     _call("lgd_scale_f16", _p(x), _p(out), float(alpha), x.numel(), _stream())
     return out
 
@@ -810,14 +836,32 @@ def scale(x, alpha, out=None):
 def upsample2x_bwd(gy, B, H, W, C_, out=None):
     if out is None:
         out = torch.empty((B * H * W, C_), device=gy.device, dtype=F16)
+    _operands("upsample2x_bwd", ("gy", gy, F16, 4 * B * H * W * C_), ("out", out, F16, B * H * W * C_))
     _prof("upsample2x_bwd_kernel", 2.0 * 5 * B * H * W * C_,
           lambda: _call("lgd_upsample2x_bwd_f16", _p(gy), _p(out), B, H, W, C_, _stream()))
     return out
 
 
+def _step_operands(fn, eps, x, x_out, coef_table, cols, dyn, frozen_ref, mask, hist):
+    """The operands the two fused sampler steps share: x (B, C, L, L), eps its CFG pair, the table [T][cols], the mask one
+    plane per image, frozen_ref and hist whole (B, C, L, L) latents per step."""
+    n = x.numel()
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise RuntimeError(f"{fn}: x {tuple(x.shape)} is not (B, C, L, L)")
+    _operands(fn, ("eps", eps, F32, 2 * n), ("x", x, F32, None), ("x_out", x_out, F32, n), ("coef_table", coef_table, F32, None),
+              ("dyn", dyn, torch.int32, None), ("frozen_ref", frozen_ref, F32, None), ("mask", mask, F32, x.shape[0] * x.shape[2] ** 2),
+              ("hist", hist, F32, None))
+    if coef_table.numel() % cols or dyn.numel() < 2:
+        raise RuntimeError(f"{fn}: the table is not [T][{cols}] or dyn holds fewer than two entries")
+    for name, t in (("frozen_ref", frozen_ref), ("hist", hist)):
+        if t is not None and t.numel() % n:
+            raise RuntimeError(f"{fn}: {name} holds {t.numel()} elements, no whole number of latents of {n}")
+
+
 def cfg_ddim_step(eps, x, x_out, coef_table, dyn, *, frozen_ref=None, mask=None, hist=None):
     """dyn: device int32[2] = {step, frozen_steps}."""
     B, C_, L, _ = x.shape
+    _step_operands("cfg_ddim_step", eps, x, x_out, coef_table, 4, dyn, frozen_ref, mask, hist)
     _prof("cfg_ddim_kernel", 4.0 * x.numel() * 6,
           lambda: _call("lgd_cfg_ddim_step_f32", _p(eps), _p(x), _p(x_out), _p(coef_table), _p(dyn),
                         _p(frozen_ref), _p(mask), _p(hist), B, C_, L * L, _stream()))
@@ -827,6 +871,8 @@ def cfg_ddim_step(eps, x, x_out, coef_table, dyn, *, frozen_ref=None, mask=None,
 def cfg_multistep_step(eps, x, x_out, x0_prev, coef_table, dyn, *, frozen_ref=None, mask=None, hist=None):
     """CFG + one linear multistep update (DPM-Solver++ 2M); coef_table fp32 [T][8], see lgd_hip.h."""
     B, C_, L, _ = x.shape
+    _step_operands("cfg_multistep_step", eps, x, x_out, coef_table, 8, dyn, frozen_ref, mask, hist)
+    _operands("cfg_multistep_step", ("x0_prev", x0_prev, F32, x.numel()))
     _call("lgd_cfg_multistep_step_f32", _p(eps), _p(x), _p(x_out), _p(x0_prev), _p(coef_table), _p(dyn),
           _p(frozen_ref), _p(mask), _p(hist), B, C_, L * L, _stream())
     return x_out
@@ -878,6 +924,8 @@ def multidiffusion_views(eps, x_in, latent, value, count, masks, coef_table, dyn
 
 def axpy(g, x, coef_table, step_idx, col, active=None):
     per = x.numel() // x.shape[0] if active is not None else 0
+    _operands("axpy", ("g", g, F32, x.numel()), ("x", x, F32, None), ("coef_table", coef_table, F32, None),
+              ("step_idx", step_idx, torch.int32, None), ("active", active, F32, x.shape[0]))
     _prof("axpy_kernel", 12.0 * x.numel(),
           lambda: _call("lgd_axpy_f32", _p(g), _p(x), _p(coef_table), _p(step_idx), int(col), _p(active), per, x.numel(),
                         _stream()))
@@ -885,12 +933,17 @@ def axpy(g, x, coef_table, step_idx, col, active=None):
 
 def scale_rows(x, out, table, dyn, col, reps=1):
     """out[r] = x * table[dyn[0]][col], r < reps (EulerDiscrete.scale_model_input for the CFG pair; lgd_hip.h)."""
+    _operands("scale_rows", ("x", x, F32, None), ("out", out, F32, int(reps) * x.numel()), ("table", table, F32, None),
+              ("dyn", dyn, torch.int32, None))
     _call("lgd_scale_rows_f32", _p(x), _p(out), _p(table), _p(dyn), int(table.shape[1]), int(col), x.numel(), int(reps),
           _stream())
     return out
 
 
 def select_row(table, idx, out):
+    _operands("select_row", ("table", table, F32, None), ("idx", idx, torch.int32, None), ("out", out, F32, None))
+    if table.numel() % max(out.numel(), 1):
+        raise RuntimeError(f"select_row: a table of {table.numel()} elements has no rows of {out.numel()}")
     _prof("select_row_kernel", 8.0 * out.numel(),
           lambda: _call("lgd_select_row_f32", _p(table), _p(idx), _p(out), out.numel(), _stream()))
 

@@ -565,7 +565,8 @@ class Plan:
             self.latents_pair = True
             lat = lat[:B // 2]
             f_in *= 0.5
-        self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8), ops.gemm_launch(d_in, None, f_in)))
+        lat8_in = lat8[:lat.shape[0] * L * L]              # the rows the converter writes: the first half under the pair
+        self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8_in), ops.gemm_launch(d_in, None, f_in)))
         skips = [(x, L)]
         H = L
         done = False
