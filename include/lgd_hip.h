@@ -743,6 +743,64 @@ int lgd_handoff_compose_f32(const int32_t* plan, const int32_t* win, const int32
 int lgd_handoff_ref_maps_f32(const int32_t* plan, const int32_t* seg, const int32_t* lay_of, const int64_t* maps, int NB,
                              int T, int NK, int heads, int max_hw, int L, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pillow's Image.resize for 8-bit RGB images (additive exports: LGD_ABI_VERSION stays 12; csrc/resample.hip) — what
+ * generation/sdxl_refinement.py:26 (`image.resize((1024, 1024), Image.LANCZOS)`) and the [ext] OwlViTImageProcessor in
+ * front of utils/eval/eval.py:127 compute on the host: [ext] Pillow src/libImaging/Resample.c (ImagingResample for
+ * 8-bit images), bit for bit.
+ *
+ * The contract, for one axis with `in` input and `out` output samples and a filter (f, support0):
+ *   bilinear: f(x) = 1 - |x| on |x| < 1, support0 = 1;
+ *   bicubic:  a = -0.5; f(x) = ((a + 2)|x| - (a + 3)) x^2 + 1 on |x| < 1, (((|x| - 5)|x| + 8)|x| - 4) a on |x| < 2,
+ *             support0 = 2;
+ *   lanczos:  f(x) = sinc(x) sinc(x / 3) on -3 <= x < 3, sinc(x) = sin(pi x) / (pi x), sinc(0) = 1, support0 = 3;
+ *   0 elsewhere.  In fp64: scale = in / out, filterscale = max(scale, 1), support = support0 * filterscale,
+ *   ss = 1 / filterscale, row width = 2 * (int)ceil(support) + 1.  For every output index xx:
+ *     center = (xx + 0.5) * scale;  xmin = max((int)(center - support + 0.5), 0);
+ *     count = min((int)(center + support + 0.5), in) - xmin;
+ *     w[x] = f((x + xmin - center + 0.5) * ss) for x < count, each divided by their sum (summed in ascending x) when that
+ *     sum is not 0;  k[x] = (int)(w[x] * 2^22 - 0.5) when w[x] < 0, else (int)(w[x] * 2^22 + 0.5); k[x] = 0 for x >= count.
+ *   A pass computes, per channel in int32,  clip8(((1 << 21) + sum_x k[x] * pix[xmin + x]) >> 22),  clip8 clamping to
+ *   0 .. 255 after the arithmetic shift.  The horizontal pass runs first and writes uint8; the vertical pass runs on that
+ *   uint8 image.  A pass whose in == out is left out, not run with identity weights.
+ * ------------------------------------------------------------------------------------------- */
+#define LGD_FILTER_LANCZOS 1  /* Pillow's own codes (Image.Resampling) */
+#define LGD_FILTER_BILINEAR 2
+#define LGD_FILTER_BICUBIC 3
+/* The tables of one axis.  HOST ONLY: no runtime call, every pointer is a host pointer, so it answers on a host without a
+ * GPU.  *width (may be NULL when the tables are asked for) = the row width; coef: int32 [out][width], bounds: int32
+ * [out][2] = {xmin, count}.  coef and bounds both NULL: only *width is written — the query a caller sizes its tables
+ * with.  LGD_ERR_ARG: in or out <= 0, an unknown filter, one table without the other, nothing to write, a pointer not
+ * 4-byte aligned, tables that overlap each other.  LGD_ERR_UNSUPPORTED: in or out > 16384.  The Python binding reads its
+ * tables from here (ops.resample_tables) and keeps the device copy per (in, out, filter). */
+int lgd_resample_plan(int in, int out, int filter, int32_t* coef /* host */, int32_t* bounds /* host */,
+                      int* width /* host */);
+/* Output forms, folded into the last pass (no separate cast, normalise or transpose launch); v = the Pillow byte. */
+#define LGD_RESAMPLE_U8 0     /* uint8 [N][H][W][3]: Image.resize itself */
+#define LGD_RESAMPLE_AFFINE 1 /* [N][3][H][W]: (v * r - m_c) / s_c in fp32, in this order, without contraction — the
+                                 rescale and normalise steps of an [ext] transformers image processor */
+#define LGD_RESAMPLE_UNIT 2   /* [N][3][H][W]: v / 255 * 2 - 1 in fp32, in this order (models/pipelines.py:99-105) */
+/* src: uint8 [N][h][w][3] -> out [N] x (H, W) in `form`; out_f16 = 0: fp32, 1: fp16 (the fp32 value rounded once; not
+ * read for LGD_RESAMPLE_U8 beyond its range check).  r, m0..m2, s0..s2: the fp32 parameters of LGD_RESAMPLE_AFFINE, by
+ * value (not read by the other forms).
+ * (coef_x, bounds_x, width_x, rows_x): device copies of the tables lgd_resample_plan(w, W, filter) made, their row
+ * width and row count; (.._y): of lgd_resample_plan(h, H, filter).  The tables of an axis whose size does not change
+ * are not read and may be NULL.  scratch: uint8, N * h * W * 3 bytes, read and written when both axes change size, else
+ * not touched and may be NULL.
+ * Two launches (horizontal into scratch, vertical from it), one when a single axis changes, one (the form applied to the
+ * bytes) when none does.  One thread per output pixel; no atomics, every output element is written once.
+ * LGD_ERR_ARG, before any runtime call: src or out NULL; N, h, w, H or W <= 0; an unknown filter or form; out_f16 not 0 or 1;
+ * for an axis that changes size: a NULL or not 4-byte aligned table, width_* that is not the plan's row width for these
+ * sizes, rows_* that is not the output size; scratch NULL when both axes change; out not aligned to its element (1, 2 or
+ * 4 bytes — src and scratch need none: they move byte by byte); out overlapping src, scratch or a table; scratch
+ * overlapping src.  LGD_ERR_UNSUPPORTED: N > 65535 or a size > 16384.
+ * The caller's duty, not checked: the tables hold what the plan function wrote for exactly these sizes and filter (a
+ * window that leaves the input is clamped into it: wrong pixels, no fault), and share no byte with scratch. */
+int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, int W, int filter, const int32_t* coef_x,
+                    const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y, const int32_t* bounds_y,
+                    int width_y, int rows_y, uint8_t* scratch, int form, int out_f16, float r, float m0, float m1,
+                    float m2, float s0, float s1, float s2, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,8 @@ SIGNATURES = {
     "lgd_handoff_place": [_P, _P, _P] + [_I] * 6 + [_P, _P, _P],
     "lgd_handoff_compose_f32": [_P] * 5 + [_I] * 6 + [_P] * 4,
     "lgd_handoff_ref_maps_f32": [_P] * 4 + [_I] * 6 + [_P, _P],
+    "lgd_resample_plan": [_I, _I, _I, _P, _P, _P],
+    "lgd_resample_u8": [_P] + [_I] * 6 + [_P, _P, _I, _I] * 2 + [_P, _I, _I] + [_F] * 7 + [_P, _P],
 }
 
 _lib = None

@@ -80,16 +80,30 @@ def init_synthetic(config="sdxl_refiner", device="cuda", seed=0):
     return pipe
 
 
-def refine(image, spec, refine_seed, refinement_step_ratio=0.5):
-    """sdxl_refinement.py:24-30.  image: uint8 [H, W, 3], or a PIL image (what the `sd` plugin returns,
-    generate.py:383); returns a PIL image like the reference."""
+def _refine(image, spec, refine_seed, refinement_step_ratio, output):
     if pipe is None:
         raise RuntimeError("call init() (or init_synthetic()) first")
     # sdxl_refinement.py:24-29: LANCZOS resize to 1024 x 1024, the layout's own negative prompt in front of the style list
-    src = image if isinstance(image, Image.Image) else Image.fromarray(image)
-    resized = np.asarray(src.resize((REFINE_SIZE,) * 2, Image.LANCZOS))
     text = dict(prompt=spec["prompt"], negative_prompt=", ".join([spec["extra_neg_prompt"], sdxl_negative_prompt]))
     if "sdxl_prompt_embeds" in spec:          # cached text side (no tokenizer / text tower offline)
         text.update(prompt_embeds=spec["sdxl_prompt_embeds"], pooled=spec["sdxl_pooled"])
-    out = pipe.refine(resized, seed=refine_seed, strength=refinement_step_ratio, **text)
-    return Image.fromarray(out)
+    kw = dict(seed=refine_seed, strength=refinement_step_ratio, output=output, **text)
+    if torch.is_tensor(image) and image.is_cuda:
+        # the same LANCZOS arithmetic on the GPU (lgd_amd.ops.resample_u8): the image never visits the host
+        return pipe.refine(image, resize=REFINE_SIZE, **kw)
+    src = image if isinstance(image, Image.Image) else Image.fromarray(image)
+    return pipe.refine(np.asarray(src.resize((REFINE_SIZE,) * 2, Image.LANCZOS)), **kw)
+
+
+def refine(image, spec, refine_seed, refinement_step_ratio=0.5):
+    """sdxl_refinement.py:24-30.  image: uint8 [H, W, 3], or a PIL image (what the `sd` plugin returns,
+    generate.py:383); returns a PIL image like the reference.  A uint8 [H, W, 3] tensor on the GPU (a generation made with
+    decode="device") is resized there, bit for bit as Pillow would, without the download; the result is the same PIL image."""
+    return Image.fromarray(_refine(image, spec, refine_seed, refinement_step_ratio, "uint8"))
+
+
+def refine_device(image, spec, refine_seed, refinement_step_ratio=0.5):
+    """refine() for a consumer that stays on the GPU (the evaluator: utils.eval.eval_device_images): the refined image as a
+    uint8 [1024, 1024, 3] tensor on the device, the bytes refine() returns as a PIL image.  No counterpart in the reference
+    module, whose signature refine() keeps."""
+    return _refine(image, spec, refine_seed, refinement_step_ratio, "device")

@@ -3,18 +3,20 @@
 `nms` / `class_aware_nms` (eval.py:11-105) run `lgd_detect_nms_f32` in mode 1 on the host lists they are given and
 return the same numpy triples; `eval_prompt` (eval.py:120-174) with a `lgd_amd.owlvit.HipOwlViTDetector` as `model`
 runs `model.detect()` (forward + post_process + score filter + NMS on the device, one host read) and builds the same
-`det_boxes` dicts.  `eval_images` is the batched form the reference does not have.  Scores are ordered with the lower
-index first where they are equal (numpy's argsort at eval.py:45 leaves that open); arithmetic is fp32 where the
-reference's numpy runs in the precision of its inputs."""
+`det_boxes` dicts.  `eval_images` is the batched form the reference does not have, `eval_device_images` the same for
+images that are still on the GPU (lgd_amd.owl_processor.DeviceOwlProcessor in place of the processor's image half).
+Scores are ordered with the lower index first where they are equal (numpy's argsort at eval.py:45 leaves that open);
+arithmetic is fp32 where the reference's numpy runs in the precision of its inputs."""
 import numpy as np
 import torch
 from PIL import Image
 
 from lgd_amd import ops
+from lgd_amd.owl_processor import DeviceOwlProcessor
 from lgd_amd.owlvit import HipOwlViTDetector
 
 __all__ = ["get_eval_info_from_prompt", "nms", "class_aware_nms", "evaluate_with_boxes", "to_gen_box_format",
-           "eval_prompt", "eval_images"]
+           "eval_prompt", "eval_images", "eval_device_images"]
 
 
 def get_eval_info_from_prompt(prompt, prompt_type):
@@ -92,6 +94,34 @@ def eval_images(model, processor, items, score_threshold=0.1, nms_threshold=0.5,
         width, height = image.size
         boxes, scores, labels = (t.cpu().numpy() for t in det.image(b))
         out.append(_det_boxes(texts, boxes, scores, labels, width, height))
+    return out
+
+
+def eval_device_images(model, processor, images, texts, score_threshold=0.1, nms_threshold=0.5, use_class_aware_nms=False):
+    """eval_images for images that are already on the GPU: images uint8 (N, h, w, 3) on the device (a generation made with
+    decode="device", or the refiner's output="device"), texts one list of query strings per image.  processor: the
+    OwlViTProcessor, or a DeviceOwlProcessor built from it — its image half (Pillow resize, rescale, normalise) runs as
+    one ops.resample_u8 call on the device, bit for bit Pillow's resize; the token ids come from its tokenizer.  The
+    pixels never visit the host.  Returns one `det_boxes` list per image, as eval_images."""
+    if not isinstance(model, HipOwlViTDetector):
+        raise TypeError("eval_device_images needs a lgd_amd.owlvit.HipOwlViTDetector")
+    if not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4:
+        raise TypeError("eval_device_images takes a uint8 (N, h, w, 3) tensor on the GPU; eval_images takes PIL images")
+    if len(texts) != images.shape[0]:
+        raise ValueError(f"{len(texts)} query lists for {images.shape[0]} images")
+    dproc = processor if isinstance(processor, DeviceOwlProcessor) else DeviceOwlProcessor(processor)
+    Q = max(len(t) for t in texts)
+    ids = []
+    for t in texts:
+        rows = dproc.input_ids(t)
+        ids.append(torch.cat([rows, rows.new_zeros((Q - rows.shape[0], rows.shape[1]))]))
+    det = model.detect(dproc.pixel_values(images.contiguous()), torch.cat(ids), score_threshold=score_threshold,
+                       nms_threshold=nms_threshold, class_aware=use_class_aware_nms)
+    height, width = images.shape[1], images.shape[2]
+    out = []
+    for b, t in enumerate(texts):
+        boxes, scores, labels = (x.cpu().numpy() for x in det.image(b))
+        out.append(_det_boxes(t, boxes, scores, labels, width, height))
     return out
 
 

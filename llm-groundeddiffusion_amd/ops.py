@@ -1124,3 +1124,87 @@ def handoff_ref_maps(plan, seg, lay_of, maps, T, heads, max_hw, L):
         _call("lgd_handoff_ref_maps_f32", _p(plan), _p(seg), _p(lay_of), _p(maps), NB, int(T), NK, int(heads), int(max_hw),
               int(L), _p(out), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Pillow's Image.resize on the device (csrc/resample.hip)
+# ---------------------------------------------------------------------------------------------
+FILTERS = {"lanczos": 1, "bilinear": 2, "bicubic": 3}       # Pillow's Image.Resampling codes = LGD_FILTER_*
+RESAMPLE_FORMS = {"u8": 0, "affine": 1, "unit": 2}           # LGD_RESAMPLE_*
+_RESAMPLE_TABLES = {}
+
+
+def resample_filter(filter) -> int:
+    """A filter name, a Pillow Image.Resampling member or its integer code -> the LGD_FILTER_* code."""
+    code = FILTERS.get(filter.lower()) if isinstance(filter, str) else int(filter)
+    if code not in FILTERS.values():
+        raise RuntimeError(f"resample: filter {filter!r} is none of {sorted(FILTERS)} (Pillow codes 1, 2, 3)")
+    return code
+
+
+def resample_plan(n_in: int, n_out: int, filter):
+    """The tables of one axis as the library's host function makes them (lgd_resample_plan; no GPU needed): (coef int32
+    [n_out, width], bounds int32 [n_out, 2] = (first input index, taps), width) as host tensors."""
+    lib = _lib.load()
+    code = resample_filter(filter)
+    width = C.c_int(0)
+    _lib.check(lib.lgd_resample_plan(int(n_in), int(n_out), code, None, None, C.byref(width)), "lgd_resample_plan")
+    coef = torch.empty((int(n_out), width.value), dtype=torch.int32)
+    bounds = torch.empty((int(n_out), 2), dtype=torch.int32)
+    _lib.check(lib.lgd_resample_plan(int(n_in), int(n_out), code, _p(coef), _p(bounds), None), "lgd_resample_plan")
+    return coef, bounds, width.value
+
+
+def resample_tables(n_in: int, n_out: int, filter, device):
+    """resample_plan's tables on `device`, uploaded once per (n_in, n_out, filter): a launch that finds them makes no
+    host -> device copy and can be captured."""
+    key = (str(torch.device(device)), int(n_in), int(n_out), resample_filter(filter))
+    if key not in _RESAMPLE_TABLES:
+        coef, bounds, width = resample_plan(n_in, n_out, filter)
+        _RESAMPLE_TABLES[key] = (coef.to(device), bounds.to(device), width)
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_u8(images, size, filter, form="u8", *, dtype=None, rescale=1.0 / 255.0, mean=(0.0, 0.0, 0.0),
+                std=(1.0, 1.0, 1.0), out=None, scratch=None, stream=None):
+    """PIL.Image.resize of a uint8 (N, h, w, 3) batch on the device, bit for bit (lgd_resample_u8).  size = (H, W);
+    filter: "bilinear" / "bicubic" / "lanczos" or Pillow's code.  form "u8" -> uint8 (N, H, W, 3); "affine" ->
+    (v * rescale - mean[c]) / std[c] and "unit" -> v / 255 * 2 - 1, both (N, 3, H, W) in `dtype` (fp32, the default, or
+    fp16).  scratch: uint8, N * h * W * 3 elements, needed when both axes change size (allocated when left out)."""
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise RuntimeError(f"resample_u8: images is a (N, h, w, 3) batch, got shape {tuple(images.shape)}")
+    if form not in RESAMPLE_FORMS:
+        raise RuntimeError(f"resample_u8: form {form!r} is none of {sorted(RESAMPLE_FORMS)}")
+    N, h, w, _ = images.shape
+    H, W = int(size[0]), int(size[1])
+    code = resample_filter(filter)
+    if form == "u8":
+        if dtype not in (None, torch.uint8):
+            raise RuntimeError("resample_u8: form 'u8' writes uint8")
+        dtype, shape = torch.uint8, (N, H, W, 3)
+    else:
+        dtype = F32 if dtype is None else dtype
+        if dtype not in (F32, F16):
+            raise RuntimeError(f"resample_u8: form {form!r} writes fp32 or fp16, not {dtype}")
+        shape = (N, 3, H, W)
+    if len(mean) != 3 or len(std) != 3:
+        raise RuntimeError("resample_u8: mean and std hold one value per channel")
+    if min(N, h, w, H, W) <= 0:
+        raise RuntimeError(f"resample_u8: empty operand ({N} images of {h} x {w} -> {H} x {W})")
+    dev = images.device
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=dtype)
+    elif tuple(out.shape) != shape:
+        raise RuntimeError(f"resample_u8: out has shape {tuple(out.shape)}, the call writes {shape}")
+    both = h != H and w != W
+    if both and scratch is None:
+        scratch = torch.empty((N * h * W * 3,), device=dev, dtype=torch.uint8)
+    _operands("resample_u8", ("images", images, torch.uint8, None), ("out", out, dtype, N * H * W * 3),
+              ("scratch", scratch if both else None, torch.uint8, N * h * W * 3))
+    cx, bx, wx = resample_tables(w, W, code, dev) if w != W else (None, None, 0)
+    cy, by, wy = resample_tables(h, H, code, dev) if h != H else (None, None, 0)
+    st = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
+    _call("lgd_resample_u8", _p(images), N, h, w, H, W, code, _p(cx), _p(bx), wx, W, _p(cy), _p(by), wy, H,
+          _p(scratch if both else None), RESAMPLE_FORMS[form], 1 if dtype == F16 else 0, float(rescale),
+          *(float(v) for v in mean), *(float(v) for v in std), _p(out), st)
+    return out

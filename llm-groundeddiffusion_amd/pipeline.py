@@ -227,6 +227,17 @@ def _overall_guidance(sampler, lay, saved, keys, L, T, use_ref_ca, max_iter=None
                 **thresholds_and_weights)
 
 
+def _decoded(sampler, latents, decode, n):
+    """The images a generation returns.  decode=True: uint8 (n, h, w, 3) on the host (sampler.decode); decode="device": the
+    same bytes left on the GPU (sampler.decode_device), for consumers that stay there — the refiner pass and the
+    evaluator take them through ops.resample_u8; decode=False: none."""
+    if isinstance(decode, str):
+        if decode != "device":
+            raise ValueError(f"decode={decode!r}: True, False or \"device\"")
+        return sampler.decode_device(latents)
+    return sampler.decode(latents) if decode else [None] * n
+
+
 def _stage_b(sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_overall_bboxes, horizontal_shift_only,
              use_ref_ca, overall, decode, gligen_of=lambda lay: None, overall_start=None, handoff="host", **denoise_kw):
     """Alignment (latents.py:107-118), composition (lmd_plus.py:398-416) and the overall generation with attention guidance
@@ -262,7 +273,7 @@ def _stage_b(sampler, lays, per_lay, prep, keys, L, T, comp_steps, align_with_ov
                                                    ref_maps=placed[li]["ref_maps"] if placed is not None else None, **overall),
                         frozen_mask=(fg_idx != 0)))
     res_b = sampler.denoise_batch(jobs, T, save_all_latents=False, **denoise_kw)
-    images = sampler.decode(torch.cat([r["latents"] for r in res_b])) if decode else [None] * len(lays)
+    images = _decoded(sampler, torch.cat([r["latents"] for r in res_b]), decode, len(lays))
     return [dict(image=images[li], latents=r["latents"], so_images=per_lay[li]["so_images"],
                  guidance_iters=r["guidance_iters"], composed=comps[li][0], fg_idx=comps[li][1],
                  so_guidance_iters=per_lay[li]["guidance_iters"]) for li, r in enumerate(res_b)], res_b
@@ -293,7 +304,9 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
     overall_first_step / overall_n_steps / overall_start (one latent tensor per layout): run only those steps of the
     overall generation, from the given state — the teacher-forcing hook of the parity tests.
     handoff: where alignment, composition and the reference-map gather between the two stages run — "host" (hostprep, box
-    by box), "device" (lgd_amd.handoff: three launches for the batch, no read) or None = lgd_amd.handoff.resolve's choice."""
+    by box), "device" (lgd_amd.handoff: three launches for the batch, no read) or None = lgd_amd.handoff.resolve's choice.
+    decode="device": every result's `image` is the uint8 (h, w, 3) tensor on the GPU (sampler.decode_device), the bytes
+    decode=True copies to the host."""
     T, dev = num_inference_steps, sampler.dev
     handoff = device_handoff.resolve(handoff, _batched(mask_refiner, "box"))
     L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps = _two_stage_setup(
@@ -405,7 +418,7 @@ def _single_shot(sampler, lays, keys, guidance_kw, *, num_inference_steps, guida
         jobs.append(Job(lat, torch.cat([lay.overall_uncond, lay.overall_cond]), guidance=guid))
     res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, save_all_latents=False,
                                 first_step=first_step, n_steps=n_steps, trace=trace)
-    images = sampler.decode(torch.cat([r["latents"] for r in res])) if decode else [None] * len(lays)
+    images = _decoded(sampler, torch.cat([r["latents"] for r in res]), decode, len(lays))
     return [dict(image=images[i], latents=r["latents"], guidance_iters=r["guidance_iters"], guidance_iters_fuser_on=0)
             for i, r in enumerate(res)]
 
@@ -469,7 +482,8 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
 
     texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor, already scaled
     by init_noise_sigma.  Returns (final latents (N,C,L,L), uint8 images (N,8L,8L,3) from sampler.decode or None), plus
-    the per-image histories (E+1,1,C,L,L) with save_all_latents."""
+    the per-image histories (E+1,1,C,L,L) with save_all_latents.  decode="device": the images stay on the GPU
+    (sampler.decode_device), the same bytes."""
     sch = PNDMScheduler.from_config(sampler.scheduler) if scheduler is None else scheduler
     starts = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
     if len(starts) != len(texts):
@@ -478,7 +492,7 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, scheduler=sch,
                                 save_all_latents=save_all_latents)
     lat = torch.cat([r["latents"] for r in res])
-    images = sampler.decode(lat) if decode else None
+    images = _decoded(sampler, lat, decode, len(jobs)) if decode else None
     if save_all_latents:
         return lat, images, [r["latents_all"] for r in res]
     return lat, images

@@ -124,12 +124,24 @@ class SDXLRefiner:
     @torch.no_grad()
     def refine(self, image, prompt_embeds=None, pooled=None, *, prompt: Optional[str] = None,
                negative_prompt: Optional[str] = None, seed: int = 0, strength: float = 0.3,
-               num_inference_steps: int = 50, guidance_scale: float = 5.0, output: str = "uint8"):
+               num_inference_steps: int = 50, guidance_scale: float = 5.0, output: str = "uint8",
+               resize: Optional[int] = None):
         """image: uint8 [H, W, 3] (numpy) or float [1, 3, H, W] in [-1, 1]; H = W, a multiple of 8 (the reference
-        resizes to 1024 x 1024 first).  Returns uint8 [H, W, 3] (output="uint8"), the float image [1, 3, H, W] in
-        [-1, 1] before clamping ("float") or the final latents ("latent")."""
+        resizes to 1024 x 1024 first).  A uint8 [H, W, 3] TENSOR (what decode_device leaves on the GPU) goes through
+        ops.resample_u8: with resize=S Pillow's LANCZOS resize to S x S (sdxl_refinement.py:26) and v / 255 * 2 - 1 in
+        one pass, straight into the encoder's fp32 input, with no host copy — bit for bit what the numpy path computes
+        from the Pillow-resized image.  Returns uint8 [H, W, 3] (output="uint8"; "device": the same bytes as a tensor
+        left on the GPU), the float image [1, 3, H, W] in [-1, 1] before clamping ("float") or the final latents
+        ("latent")."""
         if prompt_embeds is None:
             prompt_embeds, pooled = self.encode_prompt(prompt, negative_prompt or "")
+        if torch.is_tensor(image) and image.dtype == torch.uint8:
+            if image.dim() != 3 or image.shape[2] != 3:
+                raise ValueError(f"a uint8 image tensor is [H, W, 3], got {tuple(image.shape)}")
+            side = (int(resize),) * 2 if resize is not None else tuple(image.shape[:2])
+            image = ops.resample_u8(image.to(self.dev).contiguous()[None], side, "lanczos", "unit")
+        elif resize is not None:
+            raise ValueError("resize= serves a uint8 [H, W, 3] tensor; resize numpy / float images before the call")
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image)).permute(2, 0, 1)[None].float() / 255.0 * 2.0 - 1.0
         H, W = image.shape[-2:]
@@ -151,7 +163,8 @@ class SDXLRefiner:
             raise RuntimeError("non-finite image from the VAE decoder (fp16 overflow; this VAE needs an fp32 / fp16-safe variant)")
         if output == "float":
             return img
-        return ((img[0] / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+        u8 = ((img[0] / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0)
+        return u8.contiguous() if output == "device" else u8.cpu().numpy()
 
 
 def build_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ch=(128, 256, 512, 512), vae_layers=2):
