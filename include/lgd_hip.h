@@ -800,6 +800,25 @@ int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, int W, int f
                     const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y, const int32_t* bounds_y,
                     int width_y, int rows_y, uint8_t* scratch, int form, int out_f16, float r, float m0, float m1,
                     float m2, float s0, float s1, float s2, void* out, void* stream);
+/* The same resize written into a larger canvas (additive export: LGD_ABI_VERSION stays 12) — the resize, rescale,
+ * normalise and pad steps of the [ext] transformers SamImageProcessor in front of models/sam.py:39 in one call.  Every
+ * argument up to `out` means what it means for lgd_resample_u8, except that out is
+ *   fp32 / fp16 [N][3][CH][CW] for LGD_RESAMPLE_AFFINE and LGD_RESAMPLE_UNIT,  uint8 [N][CH][CW][3] for LGD_RESAMPLE_U8,
+ * with the resized H x W image at the top-left corner (element (y, x) of the image is element (y, x) of the canvas; no
+ * offset, no cropping) and every element with y >= H or x >= W set to `pad`, in output units (after the form: a
+ * processor that pads with zeros after normalising passes 0).  fp16: pad rounded once; uint8: pad itself.
+ * The same passes as lgd_resample_u8; the LAST one to run has one thread per CANVAS pixel and stores either its pixel or
+ * the pad — no memset, no copy, no pad launch, and with both axes unchanged the call is one launch.  The pass into
+ * scratch is the dense one.  Every canvas element is written exactly once and nothing outside the canvas is written;
+ * pad pixels read neither src nor the tables.  No atomics.  CH == H and CW == W gives lgd_resample_u8's bits.
+ * LGD_ERR_ARG, before any runtime call: everything lgd_resample_u8 refuses (out's extent for the overlap checks is the
+ * canvas); CH < H or CW < W; pad not finite; for LGD_RESAMPLE_U8 a pad that is not an integer in 0 .. 255.
+ * LGD_ERR_UNSUPPORTED: what lgd_resample_u8 answers so, or CH or CW > 16384. */
+int lgd_resample_canvas_u8(const uint8_t* src, int N, int h, int w, int H, int W, int filter, const int32_t* coef_x,
+                           const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y,
+                           const int32_t* bounds_y, int width_y, int rows_y, uint8_t* scratch, int form, int out_f16,
+                           float r, float m0, float m1, float m2, float s0, float s1, float s2, void* out, int CH, int CW,
+                           float pad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,7 @@ SIGNATURES = {
     "lgd_handoff_ref_maps_f32": [_P] * 4 + [_I] * 6 + [_P, _P],
     "lgd_resample_plan": [_I, _I, _I, _P, _P, _P],
     "lgd_resample_u8": [_P] + [_I] * 6 + [_P, _P, _I, _I] * 2 + [_P, _I, _I] + [_F] * 7 + [_P, _P],
+    "lgd_resample_canvas_u8": [_P] + [_I] * 6 + [_P, _P, _I, _I] * 2 + [_P, _I, _I] + [_F] * 7 + [_P, _I, _I, _F, _P],
 }
 
 _lib = None

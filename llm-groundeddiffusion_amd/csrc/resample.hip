@@ -11,6 +11,12 @@
 //    windows of one input row.  Sums are int32, as Pillow's.  No atomics; every output element has one owner.
 //  * lgd_resample_u8 launches the horizontal pass into the caller's scratch and the vertical pass from it; when only one
 //    axis changes size that pass writes the output itself, and when none does the output form is applied to the input.
+//  * lgd_resample_canvas_u8 is the same chain with the LAST pass instantiated with CANVAS: its grid covers a CH x CW
+//    canvas, one thread per canvas pixel; a thread inside the H x W image computes its pixel as above, one outside stores
+//    the pad value.  Lanes of a wave hold neighbouring pixels of one canvas row, so each of a lane's three stores is one
+//    contiguous run per wave (256 B of fp32 per plane); whether a row lies below the image is the same for a whole
+//    workgroup, and only the one wave that straddles the image's right edge diverges.  The dense instantiations carry none
+//    of this: lgd_resample_u8 launches the kernels it launched before the canvas form existed.
 #include "common.h"
 #include "contract.h"
 
@@ -81,6 +87,8 @@ struct PassArgs {
   const int32_t* bounds;  // [out][2] = {first input index, taps}
   int ksize, in_h, in_w, out_h, out_w;
   float r, m0, m1, m2, s0, s1, s2;
+  int cv_h, cv_w;  // CANVAS only: dst is [N][3][cv_h][cv_w] (uint8: [N][cv_h][cv_w][3]), the image at its top left
+  float pad;       // CANVAS only: every element outside the out_h x out_w image
 };
 
 __device__ __forceinline__ int clip8(int acc) { return min(max(acc >> PRECISION_BITS, 0), 255); }
@@ -91,12 +99,16 @@ __device__ __forceinline__ float form_of(int v, float r, float m, float s) {
   return (float)v / 255.f * 2.f - 1.f;
 }
 
-template <int AXIS, int FORM, typename T>
+template <int AXIS, int FORM, typename T, bool CANVAS>
 __global__ __launch_bounds__(PASS_THREADS) void resample_pass_kernel(const PassArgs a) {
   const int xx = blockIdx.x * PASS_THREADS + threadIdx.x, yy = blockIdx.y, n = blockIdx.z;
-  if (xx >= a.out_w) return;
-  int v0, v1, v2;
-  if (AXIS == AXIS_NONE) {
+  const int rows = CANVAS ? a.cv_h : a.out_h, row_w = CANVAS ? a.cv_w : a.out_w;  // of dst; the grid covers them
+  if (xx >= row_w) return;
+  const bool inside = !CANVAS || (xx < a.out_w && yy < a.out_h);
+  int v0 = 0, v1 = 0, v2 = 0;
+  if (!inside) {
+    // a pad pixel reads neither the source nor the tables (their rows end at the image)
+  } else if (AXIS == AXIS_NONE) {
     const uint8_t* p = a.src + (((long)n * a.in_h + yy) * a.in_w + xx) * 3;
     v0 = p[0], v1 = p[1], v2 = p[2];
   } else {
@@ -117,31 +129,42 @@ __global__ __launch_bounds__(PASS_THREADS) void resample_pass_kernel(const PassA
     v0 = clip8(s0), v1 = clip8(s1), v2 = clip8(s2);
   }
   if (FORM == LGD_RESAMPLE_U8) {
-    uint8_t* d = static_cast<uint8_t*>(a.dst) + (((long)n * a.out_h + yy) * a.out_w + xx) * 3;
+    if (!inside) v0 = v1 = v2 = (int)a.pad;  // an integral byte: the host refused anything else
+    uint8_t* d = static_cast<uint8_t*>(a.dst) + (((long)n * rows + yy) * row_w + xx) * 3;
     d[0] = (uint8_t)v0, d[1] = (uint8_t)v1, d[2] = (uint8_t)v2;
   } else {
-    const long plane = (long)a.out_h * a.out_w;
-    T* d = static_cast<T*>(a.dst) + (long)n * 3 * plane + (long)yy * a.out_w + xx;
-    d[0] = (T)form_of<FORM>(v0, a.r, a.m0, a.s0);
-    d[plane] = (T)form_of<FORM>(v1, a.r, a.m1, a.s1);
-    d[2 * plane] = (T)form_of<FORM>(v2, a.r, a.m2, a.s2);
+    const long plane = (long)rows * row_w;
+    T* d = static_cast<T*>(a.dst) + (long)n * 3 * plane + (long)yy * row_w + xx;
+    d[0] = (T)(inside ? form_of<FORM>(v0, a.r, a.m0, a.s0) : a.pad);
+    d[plane] = (T)(inside ? form_of<FORM>(v1, a.r, a.m1, a.s1) : a.pad);
+    d[2 * plane] = (T)(inside ? form_of<FORM>(v2, a.r, a.m2, a.s2) : a.pad);
   }
 }
 
-template <int AXIS>
-void launch_pass(const PassArgs& a, int N, int form, int out_f16, hipStream_t st) {
-  const dim3 grid((unsigned)((a.out_w + PASS_THREADS - 1) / PASS_THREADS), (unsigned)a.out_h, (unsigned)N);
+template <int AXIS, bool CANVAS>
+void launch_pass_as(const PassArgs& a, int N, int form, int out_f16, hipStream_t st) {
+  const int rows = CANVAS ? a.cv_h : a.out_h, row_w = CANVAS ? a.cv_w : a.out_w;
+  const dim3 grid((unsigned)((row_w + PASS_THREADS - 1) / PASS_THREADS), (unsigned)rows, (unsigned)N);
   const dim3 block(PASS_THREADS);
   if (form == LGD_RESAMPLE_U8)
-    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_U8, uint8_t>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_U8, uint8_t, CANVAS>), grid, block, 0, st, a);
   else if (form == LGD_RESAMPLE_AFFINE && !out_f16)
-    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_AFFINE, float>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_AFFINE, float, CANVAS>), grid, block, 0, st, a);
   else if (form == LGD_RESAMPLE_AFFINE)
-    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_AFFINE, half_t>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_AFFINE, half_t, CANVAS>), grid, block, 0, st, a);
   else if (!out_f16)
-    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_UNIT, float>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_UNIT, float, CANVAS>), grid, block, 0, st, a);
   else
-    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_UNIT, half_t>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((resample_pass_kernel<AXIS, LGD_RESAMPLE_UNIT, half_t, CANVAS>), grid, block, 0, st, a);
+}
+
+// canvas: only the pass that writes `out` is asked for it; the pass into scratch is always dense
+template <int AXIS>
+void launch_pass(const PassArgs& a, int N, int form, int out_f16, bool canvas, hipStream_t st) {
+  if (canvas)
+    launch_pass_as<AXIS, true>(a, N, form, out_f16, st);
+  else
+    launch_pass_as<AXIS, false>(a, N, form, out_f16, st);
 }
 
 }  // namespace
@@ -191,11 +214,13 @@ extern "C" int lgd_resample_plan(int in, int out, int filter, int32_t* coef, int
   return LGD_OK;
 }
 
-extern "C" int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, int W, int filter, const int32_t* coef_x,
-                               const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y,
-                               const int32_t* bounds_y, int width_y, int rows_y, uint8_t* scratch, int form,
-                               int out_f16, float r, float m0, float m1, float m2, float s0, float s1, float s2,
-                               void* out, void* stream) {
+namespace {
+
+// Both entries: canvas = false is lgd_resample_u8 (CH, CW and pad are H, W and 0 and are not read by a kernel).
+int resample_run(const uint8_t* src, int N, int h, int w, int H, int W, int filter, const int32_t* coef_x,
+                 const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y, const int32_t* bounds_y,
+                 int width_y, int rows_y, uint8_t* scratch, int form, int out_f16, float r, float m0, float m1, float m2,
+                 float s0, float s1, float s2, void* out, bool canvas, int CH, int CW, float pad, void* stream) {
   using lgd_contract::misaligned;
   using lgd_contract::overlaps;
   if (!src || !out) return LGD_ERR_ARG;
@@ -203,7 +228,12 @@ extern "C" int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, i
   if (support_of(filter) == 0.0) return LGD_ERR_ARG;
   if (form != LGD_RESAMPLE_U8 && form != LGD_RESAMPLE_AFFINE && form != LGD_RESAMPLE_UNIT) return LGD_ERR_ARG;
   if (out_f16 != 0 && out_f16 != 1) return LGD_ERR_ARG;
+  if (canvas) {
+    if (CH < H || CW < W || !isfinite(pad)) return LGD_ERR_ARG;
+    if (form == LGD_RESAMPLE_U8 && !(pad >= 0.f && pad <= 255.f && pad == (float)(int)pad)) return LGD_ERR_ARG;
+  }
   if (N > MAX_N || h > MAX_SIDE || w > MAX_SIDE || H > MAX_SIDE || W > MAX_SIDE) return LGD_ERR_UNSUPPORTED;
+  if (canvas && (CH > MAX_SIDE || CW > MAX_SIDE)) return LGD_ERR_UNSUPPORTED;
   const bool need_h = W != w, need_v = H != h;
   if (need_h) {
     if (!coef_x || !bounds_x || misaligned(coef_x, 4) || misaligned(bounds_x, 4)) return LGD_ERR_ARG;
@@ -216,7 +246,7 @@ extern "C" int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, i
   if (need_h && need_v && !scratch) return LGD_ERR_ARG;
   const int64_t in_bytes = (int64_t)N * h * w * 3, mid_bytes = (int64_t)N * h * W * 3;
   const int elem = form == LGD_RESAMPLE_U8 ? 1 : (out_f16 ? 2 : 4);
-  const int64_t out_bytes = (int64_t)N * H * W * 3 * elem;
+  const int64_t out_bytes = (int64_t)N * CH * CW * 3 * elem;
   if (misaligned(out, elem)) return LGD_ERR_ARG;
   if (overlaps(out, out_bytes, src, in_bytes)) return LGD_ERR_ARG;
   if (need_h && need_v && (overlaps(out, out_bytes, scratch, mid_bytes) || overlaps(scratch, mid_bytes, src, in_bytes)))
@@ -231,21 +261,42 @@ extern "C" int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, i
   a.r = r, a.m0 = m0, a.m1 = m1, a.m2 = m2, a.s0 = s0, a.s1 = s1, a.s2 = s2;
   a.src = src, a.in_h = h, a.in_w = w;
   a.coef = nullptr, a.bounds = nullptr, a.ksize = 0;
+  a.cv_h = CH, a.cv_w = CW, a.pad = pad;
   if (need_h) {
     a.coef = coef_x, a.bounds = bounds_x, a.ksize = width_x;
     a.out_h = h, a.out_w = W;
     a.dst = need_v ? static_cast<void*>(scratch) : out;
-    launch_pass<AXIS_H>(a, N, need_v ? LGD_RESAMPLE_U8 : form, out_f16, st);
+    launch_pass<AXIS_H>(a, N, need_v ? LGD_RESAMPLE_U8 : form, out_f16, canvas && !need_v, st);
     a.src = scratch, a.in_w = W;
   }
   if (need_v) {
     a.coef = coef_y, a.bounds = bounds_y, a.ksize = width_y;
     a.out_h = H, a.out_w = W, a.dst = out;
-    launch_pass<AXIS_V>(a, N, form, out_f16, st);
+    launch_pass<AXIS_V>(a, N, form, out_f16, canvas, st);
   }
   if (!need_h && !need_v) {
     a.out_h = H, a.out_w = W, a.dst = out;
-    launch_pass<AXIS_NONE>(a, N, form, out_f16, st);
+    launch_pass<AXIS_NONE>(a, N, form, out_f16, canvas, st);
   }
   return lgd_check_launch();
+}
+
+}  // namespace
+
+extern "C" int lgd_resample_u8(const uint8_t* src, int N, int h, int w, int H, int W, int filter, const int32_t* coef_x,
+                               const int32_t* bounds_x, int width_x, int rows_x, const int32_t* coef_y,
+                               const int32_t* bounds_y, int width_y, int rows_y, uint8_t* scratch, int form,
+                               int out_f16, float r, float m0, float m1, float m2, float s0, float s1, float s2,
+                               void* out, void* stream) {
+  return resample_run(src, N, h, w, H, W, filter, coef_x, bounds_x, width_x, rows_x, coef_y, bounds_y, width_y, rows_y,
+                      scratch, form, out_f16, r, m0, m1, m2, s0, s1, s2, out, false, H, W, 0.f, stream);
+}
+
+extern "C" int lgd_resample_canvas_u8(const uint8_t* src, int N, int h, int w, int H, int W, int filter,
+                                      const int32_t* coef_x, const int32_t* bounds_x, int width_x, int rows_x,
+                                      const int32_t* coef_y, const int32_t* bounds_y, int width_y, int rows_y,
+                                      uint8_t* scratch, int form, int out_f16, float r, float m0, float m1, float m2,
+                                      float s0, float s1, float s2, void* out, int CH, int CW, float pad, void* stream) {
+  return resample_run(src, N, h, w, H, W, filter, coef_x, bounds_x, width_x, rows_x, coef_y, bounds_y, width_y, rows_y,
+                      scratch, form, out_f16, r, m0, m1, m2, s0, s1, s2, out, true, CH, CW, pad, stream);
 }

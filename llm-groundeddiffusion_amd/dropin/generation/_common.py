@@ -101,15 +101,24 @@ def build_layout(spec, bg_seed, fg_seed_start, so_negative_prompt, overall_negat
                         bg_seed=bg_seed, fg_seed_start=fg_seed_start)
 
 
-def sam_refiner(model_dict, height, width, **kw):
+def sam_refiner(model_dict, height, width, sam_resize=None, **kw):
     """The SAM mask refiner of the plugin when `model_dict` carries a SAM model (generate.py:126-127 merges
-    `sam.load_sam()` into it), else None = box masks."""
+    `sam.load_sam()` into it), else None = box masks.  sam_resize: None (the default) keeps the processor `model_dict`
+    carries; "torch" or "pillow" asks for that resize of `DeviceSamProcessor` — a device processor of the other kind is
+    rebuilt with it, the Hugging Face host processor has no such choice and is refused."""
     has = ("sam_model" in model_dict) if isinstance(model_dict, dict) else hasattr(model_dict, "sam_model")
     if not has:
         return None
-    from lgd_amd.sam_refine import SamRefiner
+    from lgd_amd.sam_refine import DeviceSamProcessor, SamRefiner
     md = model_dict if isinstance(model_dict, dict) else vars(model_dict)
-    return SamRefiner(dict(sam_model=md["sam_model"], sam_processor=md["sam_processor"]), height=height, width=width, **kw)
+    processor = md["sam_processor"]
+    if sam_resize is not None:
+        if not isinstance(processor, DeviceSamProcessor):
+            raise ValueError(f"sam_resize={sam_resize!r} chooses the resize of the device processor "
+                             "(wrap_sam(..., 'device') or 'device-pillow'); model_dict carries the host processor")
+        if processor.resize != sam_resize:
+            processor = DeviceSamProcessor(processor.dev, processor.target, resize=sam_resize)
+    return SamRefiner(dict(sam_model=md["sam_model"], sam_processor=processor), height=height, width=width, **kw)
 
 
 _PRECISION_NOTED = set()

@@ -1166,11 +1166,14 @@ def resample_tables(n_in: int, n_out: int, filter, device):
 
 
 def resample_u8(images, size, filter, form="u8", *, dtype=None, rescale=1.0 / 255.0, mean=(0.0, 0.0, 0.0),
-                std=(1.0, 1.0, 1.0), out=None, scratch=None, stream=None):
+                std=(1.0, 1.0, 1.0), out=None, scratch=None, stream=None, canvas=None, pad=0.0):
     """PIL.Image.resize of a uint8 (N, h, w, 3) batch on the device, bit for bit (lgd_resample_u8).  size = (H, W);
     filter: "bilinear" / "bicubic" / "lanczos" or Pillow's code.  form "u8" -> uint8 (N, H, W, 3); "affine" ->
     (v * rescale - mean[c]) / std[c] and "unit" -> v / 255 * 2 - 1, both (N, 3, H, W) in `dtype` (fp32, the default, or
-    fp16).  scratch: uint8, N * h * W * 3 elements, needed when both axes change size (allocated when left out)."""
+    fp16).  scratch: uint8, N * h * W * 3 elements, needed when both axes change size (allocated when left out).
+    canvas = (CH, CW): the result has CH x CW in place of H x W, the resized image at its top left and `pad` (in output
+    units; an integral byte for "u8") everywhere else, written by the last resize pass itself
+    (lgd_resample_canvas_u8); None: the dense call, `pad` not read."""
     if images.dim() != 4 or images.shape[3] != 3:
         raise RuntimeError(f"resample_u8: images is a (N, h, w, 3) batch, got shape {tuple(images.shape)}")
     if form not in RESAMPLE_FORMS:
@@ -1178,15 +1181,18 @@ def resample_u8(images, size, filter, form="u8", *, dtype=None, rescale=1.0 / 25
     N, h, w, _ = images.shape
     H, W = int(size[0]), int(size[1])
     code = resample_filter(filter)
+    CH, CW = (H, W) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if CH < H or CW < W:
+        raise RuntimeError(f"resample_u8: canvas {CH} x {CW} does not hold the {H} x {W} image")
     if form == "u8":
         if dtype not in (None, torch.uint8):
             raise RuntimeError("resample_u8: form 'u8' writes uint8")
-        dtype, shape = torch.uint8, (N, H, W, 3)
+        dtype, shape = torch.uint8, (N, CH, CW, 3)
     else:
         dtype = F32 if dtype is None else dtype
         if dtype not in (F32, F16):
             raise RuntimeError(f"resample_u8: form {form!r} writes fp32 or fp16, not {dtype}")
-        shape = (N, 3, H, W)
+        shape = (N, 3, CH, CW)
     if len(mean) != 3 or len(std) != 3:
         raise RuntimeError("resample_u8: mean and std hold one value per channel")
     if min(N, h, w, H, W) <= 0:
@@ -1199,12 +1205,16 @@ def resample_u8(images, size, filter, form="u8", *, dtype=None, rescale=1.0 / 25
     both = h != H and w != W
     if both and scratch is None:
         scratch = torch.empty((N * h * W * 3,), device=dev, dtype=torch.uint8)
-    _operands("resample_u8", ("images", images, torch.uint8, None), ("out", out, dtype, N * H * W * 3),
+    _operands("resample_u8", ("images", images, torch.uint8, None), ("out", out, dtype, N * CH * CW * 3),
               ("scratch", scratch if both else None, torch.uint8, N * h * W * 3))
     cx, bx, wx = resample_tables(w, W, code, dev) if w != W else (None, None, 0)
     cy, by, wy = resample_tables(h, H, code, dev) if h != H else (None, None, 0)
     st = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
-    _call("lgd_resample_u8", _p(images), N, h, w, H, W, code, _p(cx), _p(bx), wx, W, _p(cy), _p(by), wy, H,
-          _p(scratch if both else None), RESAMPLE_FORMS[form], 1 if dtype == F16 else 0, float(rescale),
-          *(float(v) for v in mean), *(float(v) for v in std), _p(out), st)
+    args = (_p(images), N, h, w, H, W, code, _p(cx), _p(bx), wx, W, _p(cy), _p(by), wy, H,
+            _p(scratch if both else None), RESAMPLE_FORMS[form], 1 if dtype == F16 else 0, float(rescale),
+            *(float(v) for v in mean), *(float(v) for v in std), _p(out))
+    if canvas is None:
+        _call("lgd_resample_u8", *args, st)
+    else:
+        _call("lgd_resample_canvas_u8", *args, CH, CW, float(pad), st)
     return out

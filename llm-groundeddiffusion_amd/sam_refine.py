@@ -33,16 +33,35 @@ class _Encoding(dict):
 
 
 class DeviceSamProcessor:
-    """The Hugging Face `SamProcessor` + `SamImageProcessor` defaults restated with torch ops on the model's device, for
-    generation loops where the host-side PIL path (resize of every decoded single-object image on the CPU) would stall
-    the GPU: longest edge -> 1024 (bilinear, half-pixel centres, result rounded to the 8-bit grid as PIL does), 1/255,
-    ImageNet mean / std, zero padding bottom / right; prompts scaled by new/old size ([ext] processing_sam.py
-    `_normalize_coordinates`); `post_process_masks` = interpolate to the padded size, crop, interpolate to the original
-    size, threshold ([ext] image_processing_sam.py).  Differs from the PIL path by the 8-bit rounding of ties only."""
-    MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    """The Hugging Face `SamProcessor` + `SamImageProcessor` defaults on the model's device, for generation loops where
+    the host-side PIL path (resize of every decoded single-object image on the CPU) would stall the GPU: longest edge ->
+    1024 (bilinear), 1/255, ImageNet mean / std, zero padding bottom / right; prompts scaled by new/old size ([ext]
+    processing_sam.py `_normalize_coordinates`); `post_process_masks` = interpolate to the padded size, crop,
+    interpolate to the original size, threshold ([ext] image_processing_sam.py).
 
-    def __init__(self, device="cuda", longest_edge=1024):
-        self.dev, self.target = torch.device(device), int(longest_edge)
+    resize="torch" (the default: existing results and goldens stay as they are) approximates Pillow's resize with
+    `F.interpolate` (half-pixel centres, antialias when shrinking) rounded to the 8-bit grid, then divides, subtracts,
+    divides and pads in separate torch launches.  That is NOT Pillow's arithmetic — Pillow resamples in two passes with
+    22-bit integer weights and an 8-bit image between them — and the share of SAM input pixels that come out one full
+    8-bit level away from `SamImageProcessor`'s (transformers 5.15, Pillow backend), measured on the CPU, is
+        512 x 512 -> 1024 x 1024, random image                        26.5 %
+        512 x 512 -> 1024 x 1024, first image of tests/sam_cases      27.3 %
+        1200 x 900                                                    13.7 %
+        512 x 2048                                                     4.1 %
+    resize="pillow" is the exact path: one `ops.resample_u8` call per batch of equal-sized images (csrc/resample.hip:
+    Pillow's BILINEAR bit for bit, (v * fp32(1/255) - mean) / std and the zero padding written by the last resize pass
+    itself), within 1e-6 absolute of `SamImageProcessor`'s pixel_values.  It needs the HIP library and a GPU."""
+    MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    RESIZES = ("torch", "pillow")
+
+    def __init__(self, device="cuda", longest_edge=1024, resize="torch"):
+        if resize not in self.RESIZES:
+            raise ValueError(f"DeviceSamProcessor: resize {resize!r} is none of {self.RESIZES}")
+        self.dev, self.target, self.resize = torch.device(device), int(longest_edge), resize
+        if resize == "pillow" and self.dev.type != "cuda":
+            raise RuntimeError(f"DeviceSamProcessor(resize='pillow') runs the HIP resampler (ops.resample_u8) and needs a "
+                               f"GPU, not device {self.dev}: there is no torch fallback for it (resize='torch' is the "
+                               "other processor, with other results)")
         self.image_processor = self
         self.on_device = True
         self._mean = torch.tensor(self.MEAN, device=self.dev).view(1, 3, 1, 1)
@@ -56,6 +75,11 @@ class DeviceSamProcessor:
         """uint8 (n, h, w, 3) on the device -> normalised, padded fp32 (n, 3, target, target) and the resized size."""
         h, w = int(t.shape[1]), int(t.shape[2])
         nh, nw = self._shape(h, w)
+        if self.resize == "pillow":
+            from . import ops
+            px = ops.resample_u8(t.contiguous(), (nh, nw), "bilinear", "affine", rescale=1.0 / 255.0, mean=self.MEAN,
+                                 std=self.STD, canvas=(self.target, self.target), pad=0.0)
+            return px, (nh, nw)
         r = F.interpolate(t.permute(0, 3, 1, 2).float(), (nh, nw), mode="bilinear", align_corners=False,
                           antialias=(nh < h or nw < w)).round().clamp(0, 255)
         r = (r / 255.0 - self._mean) / self._std
@@ -132,6 +156,8 @@ def wrap_sam(hf_sam_model, sam_processor=None, device="cuda"):
         sam_processor = transformers.SamProcessor(transformers.SamImageProcessor())
     elif sam_processor == "device":
         sam_processor = DeviceSamProcessor(device)
+    elif sam_processor == "device-pillow":                        # Pillow-exact resize (DeviceSamProcessor's docstring)
+        sam_processor = DeviceSamProcessor(device, resize="pillow")
     model = HipSamModel(SamConfig.from_hf(hf_sam_model.config), hf_sam_model.state_dict(), device=device)
     return dict(sam_model=model, sam_processor=sam_processor)
 
