@@ -564,7 +564,7 @@ class LMDSampler:
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, latents: torch.Tensor):
-        """pipelines.py:117-127: VAE decode -> uint8 HWC (the VAE is [ext] and stays PyTorch/MIOpen)."""
+        """pipelines.py:117-127: VAE decode -> uint8 HWC on the host (the VAE is vae.HipVAEDecoder, on the HIP kernels)."""
         return self.decode_device(latents).cpu().numpy()
 
     @torch.no_grad()

@@ -1,16 +1,14 @@
-"""VAE decoder ([ext] diffusers AutoencoderKL, SD 1.x / 2.x config).  It sits inside the images/s window
-because pipelines.decode (models/pipelines.py:117-127, 588-595) runs once per box and once per image
-(SURVEY.md §8a P7, §8f rank 1).
+"""The VAE ([ext] diffusers AutoencoderKL, SD 1.x / 2.x / SDXL config) on the lgd_hip kernels: implicit-GEMM convolutions,
+GroupNorm+SiLU, and for the single mid-block attention three batched GEMM launches + a row softmax for the whole batch.
+HipVAEDecoder sits inside the images/s window because pipelines.decode (models/pipelines.py:117-127, 588-595) runs once
+per box and once per image; HipVAEEncoder serves the refiner, the inversion and the
+MultiDiffusion background passes; HipVAE is the `vae` of `model_dict`: the decoder, with its encoder built on first use.
+Both halves pack their parameters through _Pack and run the blocks of _Blocks.
 
-  * HipVAEDecoder   — runs an AutoencoderKL DECODER state dict (`AutoencoderKL.state_dict()` of a real checkpoint,
-                      models/models.py:41, or the seeded `synth_aekl_state_dict()`) on the engine's own kernels:
-                      implicit-GEMM convolutions, GroupNorm+SiLU, and for the single 512-wide mid-block attention
-                      three batched GEMM launches + a row softmax for the whole batch.
-  * the plain PyTorch fp32 restatement the tests compare it with lives in oracle/restate_vae.py (test infrastructure).
-
-Parity note: AutoencoderKL itself (diffusers 0.18.0) is absent from the sandbox, so the torch module below is a
-restatement from the published architecture — "parity unpinned" at that boundary; what the tests pin is
-HipVAEDecoder against the fp32 restatement of oracle/restate_vae.py at the full SD size, through the AutoencoderKL key map.
+Parity note: AutoencoderKL itself (diffusers 0.18.0) is absent from the sandbox, so the checkers are plain PyTorch fp32
+restatements from the published architecture (oracle/restate_vae.py, oracle/restate_sdxl.py: test infrastructure) —
+"parity unpinned" at that boundary; what the tests pin is this module against those restatements at the
+full SD size, through the AutoencoderKL key map.
 
 Architecture (SD config: block_out_channels (128,256,512,512), layers_per_block 2, 32 groups, eps 1e-6):
 post_quant_conv 4->4 (1x1), conv_in 4->512, mid (resnet, 1-head attention, resnet), 4 up blocks
@@ -21,35 +19,130 @@ import re
 import torch
 
 
-class HipVAEDecoder:
+def _state_dict(source):
+    """An AutoencoderKL state dict, or a module that hands one out through `aekl_state_dict()`."""
+    return source.aekl_state_dict() if hasattr(source, "aekl_state_dict") else source
+
+
+class _Pack:
+    """The `part` half ("decoder" | "encoder") of an AutoencoderKL state dict, with the 1x1 convolution `extra` next to
+    it, packed for the kernels: fp16 weights (3x3 as pack_conv lays them out, 1x1 as [Cout, Cin]), fp32 biases and norms."""
+
+    def __init__(self, state_dict, device, part, extra):
+        from .weightstore import pack_conv
+        self.pack_conv = pack_conv
+        self.h16 = lambda t: t.to(device, torch.float16).contiguous()
+        self.f32 = lambda t: t.to(device, torch.float32).contiguous()
+        self.sd = {k: v.detach().float().cpu() for k, v in dict(state_dict).items() if k.startswith((part + ".", extra + "."))}
+        if f"{part}.conv_in.weight" not in self.sd:
+            raise RuntimeError(f"not an AutoencoderKL state dict: {part}.conv_in.weight is missing")
+
+    def conv(self, n):
+        return self.h16(self.pack_conv(self.sd[f"{n}.weight"])), self.f32(self.sd[f"{n}.bias"])
+
+    def lin(self, n):
+        w = self.sd[f"{n}.weight"]
+        return self.h16(w.reshape(w.shape[0], -1)), self.f32(self.sd[f"{n}.bias"])
+
+    def norm(self, n):
+        return self.f32(self.sd[f"{n}.weight"]), self.f32(self.sd[f"{n}.bias"])
+
+    def res(self, n):
+        return dict(n1=self.norm(f"{n}.norm1"), c1=self.conv(f"{n}.conv1"), n2=self.norm(f"{n}.norm2"), c2=self.conv(f"{n}.conv2"),
+                    sc=self.lin(f"{n}.conv_shortcut") if f"{n}.conv_shortcut.weight" in self.sd else None)
+
+    def attn(self, a):
+        sd = self.sd
+        legacy = f"{a}.query.weight" in sd
+        nq, nk, nv, no = ("query", "key", "value", "proj_attn") if legacy else ("to_q", "to_k", "to_v", "to_out.0")
+        C = sd[f"{a}.group_norm.weight"].shape[0]
+        # the softmax scale C^-1/2 is split over the q and k projections, so the fp16 score matrix holds scaled logits
+        # (raw 512-term dot products of a real VAE can leave the fp16 range)
+        s4 = float(C) ** -0.25
+        wq, wk = sd[f"{a}.{nq}.weight"].reshape(C, -1) * s4, sd[f"{a}.{nk}.weight"].reshape(C, -1) * s4
+        return dict(n=self.norm(f"{a}.group_norm"),
+                    qk=(self.h16(torch.cat([wq, wk])), self.f32(torch.cat([sd[f"{a}.{nq}.bias"], sd[f"{a}.{nk}.bias"]]) * s4)),
+                    v=self.h16(sd[f"{a}.{nv}.weight"].reshape(C, -1)), vb=self.f32(sd[f"{a}.{nv}.bias"]), o=self.lin(f"{a}.{no}"))
+
+    def in8(self, w, what):
+        """conv_in over the 8-channel operand of lgd_nchw_to_nhwc8_f16 / lgd_image_u8_to_nhwc8_f16: channels 0..ci-1 =
+        fp16 value, ci..2ci-1 = its rounding remainder, rest zero."""
+        ci = w.shape[1]
+        if ci > 4:
+            raise RuntimeError(f"{what} = {ci}: the 8-channel conv_in operand holds value + remainder of <= 4 channels")
+        return self.h16(self.pack_conv(torch.cat([w, w, w.new_zeros(w.shape[0], 8 - 2 * ci, 3, 3)], dim=1)))
+
+    def count(self, prefix):
+        """1 + the largest i among the keys `<prefix>.<i>.`: how many blocks or resnets there are."""
+        return 1 + max(int(m.group(1)) for k in self.sd for m in [re.match(re.escape(prefix) + r"\.(\d+)\.", k)] if m)
+
+    def blocks(self, prefix, sampler):
+        """[(resnets, conv of `<sampler>.0.conv` | None)] of `<prefix>.<i>`: the shape is read off the keys."""
+        out = []
+        for i in range(self.count(prefix)):
+            b, s = f"{prefix}.{i}", f"{prefix}.{i}.{sampler}.0.conv"
+            out.append(([self.res(f"{b}.resnets.{j}") for j in range(self.count(f"{b}.resnets"))],
+                        self.conv(s) if f"{s}.weight" in self.sd else None))
+        return out
+
+
+class _Blocks:
+    """What the decoder and the encoder share at run time: the kernels, the device, the GroupNorm constants and the two
+    blocks over a channels-last fp16 map x [B*H*W, C]."""
+
+    def __init__(self, device, groups, eps):
+        from . import ops
+        self.ops = ops
+        self.dev = torch.device(device)
+        self.groups, self.eps = groups, eps
+
+    def _res(self, p, x, B, H, W):
+        ops = self.ops
+        HW = H * W
+        h = ops.groupnorm(x, B, HW, self.groups, self.eps, p["n1"][0], p["n1"][1], True)
+        h = ops.conv3x3(h, p["c1"][0], B, H, W, bias=p["c1"][1])
+        h = ops.groupnorm(h, B, HW, self.groups, self.eps, p["n2"][0], p["n2"][1], True)
+        sc = x if p["sc"] is None else ops.linear(x, p["sc"][0], p["sc"][1])
+        return ops.conv3x3(h, p["c2"][0], B, H, W, bias=p["c2"][1], res=sc)
+
+    def _attn(self, p, x, B, H, W):
+        """Single-head attention over the H*W positions at width C (512): the head is wider than the flash kernels'
+        160, so the batch runs as three BATCHED GEMM launches + one row softmax:
+            scores[b] = q[b] k[b]^T      ->  P = softmax(scores)      (q, k carry C^-1/4 each)
+            vt[b]     = Wv n[b]^T        (V^T directly from the projection: no transpose pass)
+            out[b]    = P[b] vt[b]^T + bv   (rows of P sum to 1, so V's bias is added once, behind the product)"""
+        ops = self.ops
+        S = H * W
+        C = x.shape[1]
+        F16 = torch.float16
+        n = ops.groupnorm(x, B, S, self.groups, self.eps, p["n"][0], p["n"][1], False)
+        qk = ops.linear(n, p["qk"][0], p["qk"][1])                                  # [B*S, 2C]
+        sc = torch.empty((B * S, S), device=self.dev, dtype=F16)
+        ops.gemm_launch(ops.gemm_desc(qk, qk[:, C:], sc, S, S, C, lda0=2 * C, ldw=2 * C, ldc=S, nb_o=B,
+                                      a_bs=(S * 2 * C, 0), w_bs=(S * 2 * C, 0), c_bs=(S * S, 0)))
+        pr = ops.softmax_rows(sc, 1.0, out=sc)
+        vt = torch.empty((B * C, S), device=self.dev, dtype=F16)
+        ops.gemm_launch(ops.gemm_desc(p["v"], n, vt, C, S, C, lda0=C, ldw=C, ldc=S, nb_o=B,
+                                      a_bs=(0, 0), w_bs=(S * C, 0), c_bs=(C * S, 0)))
+        a = torch.empty((B * S, C), device=self.dev, dtype=F16)
+        ops.gemm_launch(ops.gemm_desc(pr, vt, a, S, C, S, lda0=S, ldw=S, ldc=C, bias=p["vb"], nb_o=B,
+                                      a_bs=(S * S, 0), w_bs=(C * S, 0), c_bs=(S * C, 0)))
+        return ops.linear(a, p["o"][0], p["o"][1], res=x)
+
+
+class HipVAEDecoder(_Blocks):
     """AutoencoderKL.decode (the `.sample` tensor) on the lgd_hip kernels: channels-last fp16, fp32 accumulate.
 
     HipVAEDecoder(state_dict | module with `aekl_state_dict()`, device).  The state dict is AutoencoderKL's (encoder keys are ignored);
     the decoder's shape (channels per up block, resnets per block, which blocks upsample) is read off the keys."""
 
     def __init__(self, source, device, groups: int = 32, eps: float = 1e-6):
-        from . import ops
-        from .weightstore import pack_conv
-        self.ops = ops
-        self.dev = torch.device(device)
-        self.groups, self.eps = groups, eps
-        sd = source.aekl_state_dict() if hasattr(source, "aekl_state_dict") else dict(source)
-        sd = {k: v.detach().float().cpu() for k, v in sd.items() if k.startswith(("decoder.", "post_quant_conv."))}
-        if "decoder.conv_in.weight" not in sd:
-            raise RuntimeError("not an AutoencoderKL state dict: decoder.conv_in.weight is missing")
-        h16 = lambda t: t.to(self.dev, torch.float16).contiguous()
-        f32 = lambda t: t.to(self.dev, torch.float32).contiguous()
-        conv = lambda n: (h16(pack_conv(sd[f"{n}.weight"])), f32(sd[f"{n}.bias"]))
-        lin = lambda n: (h16(sd[f"{n}.weight"].reshape(sd[f"{n}.weight"].shape[0], -1)), f32(sd[f"{n}.bias"]))
-        norm = lambda n: (f32(sd[f"{n}.weight"]), f32(sd[f"{n}.bias"]))
-
-        def res(n):
-            return dict(n1=norm(f"{n}.norm1"), c1=conv(f"{n}.conv1"), n2=norm(f"{n}.norm2"), c2=conv(f"{n}.conv2"),
-                        sc=lin(f"{n}.conv_shortcut") if f"{n}.conv_shortcut.weight" in sd else None)
-
+        super().__init__(device, groups, eps)
+        pk = _Pack(_state_dict(source), self.dev, "decoder", "post_quant_conv")
+        sd = pk.sd
         # post_quant_conv (1x1, 4 -> 4) folded into conv_in: conv_in(W1 z + b1) = conv_in'(z) + border-aware bias map
         # (the zero padding of conv_in does not carry b1, so the folded bias depends on which taps lie inside the image)
-        w_in, b_in = sd["decoder.conv_in.weight"], sd["decoder.conv_in.bias"]
+        w_in, self._b_in = sd["decoder.conv_in.weight"], sd["decoder.conv_in.bias"]
         if "post_quant_conv.weight" in sd:
             w1 = sd["post_quant_conv.weight"].reshape(sd["post_quant_conv.weight"].shape[0], -1)
             b1 = sd["post_quant_conv.bias"]
@@ -57,39 +150,16 @@ class HipVAEDecoder:
             w_in = torch.einsum("ockl,cd->odkl", w_in, w1)
         else:
             self._tap_bias = torch.zeros(w_in.shape[0], 3, 3)
-        self._b_in = b_in
-        ci = w_in.shape[1]
-        if ci > 4:
-            raise RuntimeError(f"latent_channels = {ci}: the 8-channel conv_in operand holds value + remainder of <= 4 channels")
-        # 8-channel operand of lgd_nchw_to_nhwc8_f16: channels 0..ci-1 = fp16 value, ci..2ci-1 = its rounding remainder
-        self.conv_in_w8 = h16(pack_conv(torch.cat([w_in, w_in, w_in.new_zeros(w_in.shape[0], 8 - 2 * ci, 3, 3)], dim=1)))
+        self.conv_in_w8 = pk.in8(w_in, "latent_channels")
         self.c_mid = w_in.shape[0]
         self._bias_maps = {}
-
-        a = "decoder.mid_block.attentions.0"
-        legacy = f"{a}.query.weight" in sd
-        nq, nk, nv, no = ("query", "key", "value", "proj_attn") if legacy else ("to_q", "to_k", "to_v", "to_out.0")
-        # the softmax scale C^-1/2 is split over the q and k projections, so the fp16 score matrix holds scaled logits
-        # (raw 512-term dot products of a real VAE can leave the fp16 range)
-        s4 = float(self.c_mid) ** -0.25
-        wq, wk = sd[f"{a}.{nq}.weight"].reshape(self.c_mid, -1) * s4, sd[f"{a}.{nk}.weight"].reshape(self.c_mid, -1) * s4
-        self.attn = dict(n=norm(f"{a}.group_norm"),
-                         qk=(h16(torch.cat([wq, wk])), f32(torch.cat([sd[f"{a}.{nq}.bias"], sd[f"{a}.{nk}.bias"]]) * s4)),
-                         v=h16(sd[f"{a}.{nv}.weight"].reshape(self.c_mid, -1)), vb=f32(sd[f"{a}.{nv}.bias"]),
-                         o=(h16(sd[f"{a}.{no}.weight"].reshape(self.c_mid, -1)), f32(sd[f"{a}.{no}.bias"])))
-        self.mid = [res("decoder.mid_block.resnets.0"), res("decoder.mid_block.resnets.1")]
-        n_up = 1 + max(int(m.group(1)) for k in sd for m in [re.match(r"decoder\.up_blocks\.(\d+)\.", k)] if m)
-        self.ups = []
-        for i in range(n_up):
-            n_res = 1 + max(int(m.group(1)) for k in sd
-                            for m in [re.match(rf"decoder\.up_blocks\.{i}\.resnets\.(\d+)\.", k)] if m)
-            up = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-            self.ups.append(([res(f"decoder.up_blocks.{i}.resnets.{j}") for j in range(n_res)],
-                             conv(up) if f"{up}.weight" in sd else None))
-        self.norm_out = norm("decoder.conv_norm_out")
-        w = pack_conv(sd["decoder.conv_out.weight"])                                 # [3, 9*C]
-        self.conv_out = (h16(torch.cat([w, torch.zeros(1, w.shape[1])])),              # pad to 4 output channels
-                         f32(torch.cat([sd["decoder.conv_out.bias"], torch.zeros(1)])))
+        self.attn = pk.attn("decoder.mid_block.attentions.0")
+        self.mid = [pk.res("decoder.mid_block.resnets.0"), pk.res("decoder.mid_block.resnets.1")]
+        self.ups = pk.blocks("decoder.up_blocks", "upsamplers")
+        self.norm_out = pk.norm("decoder.conv_norm_out")
+        w = pk.pack_conv(sd["decoder.conv_out.weight"])                              # [3, 9*C]
+        self.conv_out = (pk.h16(torch.cat([w, torch.zeros(1, w.shape[1])])),          # pad to 4 output channels
+                         pk.f32(torch.cat([sd["decoder.conv_out.bias"], torch.zeros(1)])))
 
     @classmethod
     def from_state_dict(cls, state_dict, device, **kw):
@@ -108,41 +178,6 @@ class HipVAEDecoder:
             self._bias_maps = {key: m.reshape(1, H * W, -1).expand(B, -1, -1).reshape(B * H * W, -1)
                                .to(self.dev, torch.float16).contiguous()}
         return self._bias_maps[key]
-
-    def _res(self, p, x, B, H, W=None):
-        """W=None: a square H x H map (the encoder's)."""
-        ops = self.ops
-        W = H if W is None else W
-        HW = H * W
-        h = ops.groupnorm(x, B, HW, self.groups, self.eps, p["n1"][0], p["n1"][1], True)
-        h = ops.conv3x3(h, p["c1"][0], B, H, W, bias=p["c1"][1])
-        h = ops.groupnorm(h, B, HW, self.groups, self.eps, p["n2"][0], p["n2"][1], True)
-        sc = x if p["sc"] is None else ops.linear(x, p["sc"][0], p["sc"][1])
-        return ops.conv3x3(h, p["c2"][0], B, H, W, bias=p["c2"][1], res=sc)
-
-    def _attn(self, p, x, B, H, W=None):
-        """Single-head attention over the H*W positions at width C (512): the head is wider than the flash kernels'
-        160, so the batch runs as three BATCHED GEMM launches + one row softmax:
-            scores[b] = q[b] k[b]^T      ->  P = softmax(scores)      (q, k carry C^-1/4 each)
-            vt[b]     = Wv n[b]^T        (V^T directly from the projection: no transpose pass)
-            out[b]    = P[b] vt[b]^T + bv   (rows of P sum to 1, so V's bias is added once, behind the product)"""
-        ops = self.ops
-        S = H * (H if W is None else W)
-        C = x.shape[1]
-        F16 = torch.float16
-        n = ops.groupnorm(x, B, S, self.groups, self.eps, p["n"][0], p["n"][1], False)
-        qk = ops.linear(n, p["qk"][0], p["qk"][1])                                  # [B*S, 2C]
-        sc = torch.empty((B * S, S), device=self.dev, dtype=F16)
-        ops.gemm_launch(ops.gemm_desc(qk, qk[:, C:], sc, S, S, C, lda0=2 * C, ldw=2 * C, ldc=S, nb_o=B,
-                                      a_bs=(S * 2 * C, 0), w_bs=(S * 2 * C, 0), c_bs=(S * S, 0)))
-        pr = ops.softmax_rows(sc, 1.0, out=sc)
-        vt = torch.empty((B * C, S), device=self.dev, dtype=F16)
-        ops.gemm_launch(ops.gemm_desc(p["v"], n, vt, C, S, C, lda0=C, ldw=C, ldc=S, nb_o=B,
-                                      a_bs=(0, 0), w_bs=(S * C, 0), c_bs=(C * S, 0)))
-        a = torch.empty((B * S, C), device=self.dev, dtype=F16)
-        ops.gemm_launch(ops.gemm_desc(pr, vt, a, S, C, S, lda0=S, ldw=S, ldc=C, bias=p["vb"], nb_o=B,
-                                      a_bs=(S * S, 0), w_bs=(C * S, 0), c_bs=(S * C, 0)))
-        return ops.linear(a, p["o"][0], p["o"][1], res=x)
 
     @torch.no_grad()
     def decode(self, z):
@@ -243,7 +278,7 @@ def fold_pointwise_after(w, b, w1, b1):
     return torch.einsum("pc,cdkl->pdkl", m, w), m @ b + b1
 
 
-class HipVAEEncoder(HipVAEDecoder):
+class HipVAEEncoder(_Blocks):
     """AutoencoderKL.encode(image).latent_dist on the lgd_hip kernels — the first half of the SDXL-refiner img2img
     pass (generation/sdxl_refinement.py:29 -> [ext] StableDiffusionXLImg2ImgPipeline.prepare_latents): conv_in 3 -> C0,
     down blocks (resnets without time embedding, Downsample2D = pad right/bottom by one + 3x3 stride 2), mid block
@@ -255,56 +290,20 @@ class HipVAEEncoder(HipVAEDecoder):
     once per image."""
 
     def __init__(self, state_dict, device, groups: int = 32, eps: float = 1e-6):
-        from . import ops
-        from .weightstore import pack_conv
-        self.ops = ops
-        self.dev = torch.device(device)
-        self.groups, self.eps = groups, eps
-        sd = {k: v.detach().float().cpu() for k, v in dict(state_dict).items() if k.startswith(("encoder.", "quant_conv."))}
-        if "encoder.conv_in.weight" not in sd:
-            raise RuntimeError("not an AutoencoderKL state dict: encoder.conv_in.weight is missing")
-        h16 = lambda t: t.to(self.dev, torch.float16).contiguous()
-        f32 = lambda t: t.to(self.dev, torch.float32).contiguous()
-        conv = lambda n: (h16(pack_conv(sd[f"{n}.weight"])), f32(sd[f"{n}.bias"]))
-        lin = lambda n: (h16(sd[f"{n}.weight"].reshape(sd[f"{n}.weight"].shape[0], -1)), f32(sd[f"{n}.bias"]))
-        norm = lambda n: (f32(sd[f"{n}.weight"]), f32(sd[f"{n}.bias"]))
-
-        def res(n):
-            return dict(n1=norm(f"{n}.norm1"), c1=conv(f"{n}.conv1"), n2=norm(f"{n}.norm2"), c2=conv(f"{n}.conv2"),
-                        sc=lin(f"{n}.conv_shortcut") if f"{n}.conv_shortcut.weight" in sd else None)
-        w_in = sd["encoder.conv_in.weight"]                                          # [C0, 3, 3, 3]
-        ci = w_in.shape[1]
-        if 2 * ci > 8:
-            raise RuntimeError(f"{ci} image channels: the 8-channel conv_in operand holds value + remainder of <= 4")
-        # lgd_nchw_to_nhwc8_f16: channels 0..ci-1 = fp16 value, ci..2ci-1 = its rounding remainder, rest zero
-        self.conv_in = (h16(pack_conv(torch.cat([w_in, w_in, w_in.new_zeros(w_in.shape[0], 8 - 2 * ci, 3, 3)], dim=1))),
-                        f32(sd["encoder.conv_in.bias"]))
-        n_down = 1 + max(int(m.group(1)) for k in sd for m in [re.match(r"encoder\.down_blocks\.(\d+)\.", k)] if m)
-        self.downs = []
-        for i in range(n_down):
-            n_res = 1 + max(int(m.group(1)) for k in sd
-                            for m in [re.match(rf"encoder\.down_blocks\.{i}\.resnets\.(\d+)\.", k)] if m)
-            dn = f"encoder.down_blocks.{i}.downsamplers.0.conv"
-            self.downs.append(([res(f"encoder.down_blocks.{i}.resnets.{j}") for j in range(n_res)],
-                               conv(dn) if f"{dn}.weight" in sd else None))
-        self.mid = [res("encoder.mid_block.resnets.0"), res("encoder.mid_block.resnets.1")]
-        a = "encoder.mid_block.attentions.0"
-        c_mid = sd[f"{a}.group_norm.weight"].shape[0]
-        legacy = f"{a}.query.weight" in sd
-        nq, nk, nv, no = ("query", "key", "value", "proj_attn") if legacy else ("to_q", "to_k", "to_v", "to_out.0")
-        s4 = float(c_mid) ** -0.25
-        wq, wk = sd[f"{a}.{nq}.weight"].reshape(c_mid, -1) * s4, sd[f"{a}.{nk}.weight"].reshape(c_mid, -1) * s4
-        self.attn = dict(n=norm(f"{a}.group_norm"),
-                         qk=(h16(torch.cat([wq, wk])), f32(torch.cat([sd[f"{a}.{nq}.bias"], sd[f"{a}.{nk}.bias"]]) * s4)),
-                         v=h16(sd[f"{a}.{nv}.weight"].reshape(c_mid, -1)), vb=f32(sd[f"{a}.{nv}.bias"]),
-                         o=(h16(sd[f"{a}.{no}.weight"].reshape(c_mid, -1)), f32(sd[f"{a}.{no}.bias"])))
-        self.norm_out = norm("encoder.conv_norm_out")
+        super().__init__(device, groups, eps)
+        pk = _Pack(state_dict, self.dev, "encoder", "quant_conv")
+        sd = pk.sd
+        self.conv_in = (pk.in8(sd["encoder.conv_in.weight"], "image channels"), pk.f32(sd["encoder.conv_in.bias"]))
+        self.downs = pk.blocks("encoder.down_blocks", "downsamplers")
+        self.mid = [pk.res("encoder.mid_block.resnets.0"), pk.res("encoder.mid_block.resnets.1")]
+        self.attn = pk.attn("encoder.mid_block.attentions.0")
+        self.norm_out = pk.norm("encoder.conv_norm_out")
         # conv_out (C -> 2z) followed by quant_conv (1x1, 2z -> 2z): composed exactly into one 3x3 convolution
         w_o, b_o = sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"]
         if "quant_conv.weight" in sd:
             w_o, b_o = fold_pointwise_after(w_o, b_o, sd["quant_conv.weight"], sd["quant_conv.bias"])
         self.n_moments = w_o.shape[0]
-        self.conv_out = (h16(pack_conv(w_o)), f32(b_o))
+        self.conv_out = (pk.h16(pk.pack_conv(w_o)), pk.f32(b_o))
 
     @torch.no_grad()
     def moments_nhwc(self, x8, B, H):
@@ -318,15 +317,15 @@ class HipVAEEncoder(HipVAEDecoder):
                                       hin=H, win=H, hout=H, wout=H, bias=self.conv_in[1], ldc=c0, splits=1))
         for blk, down in self.downs:
             for r in blk:
-                h = self._res(r, h, B, H)
+                h = self._res(r, h, B, H, H)
             if down is not None:
                 full = ops.conv3x3(h, down[0], B, H, H, bias=down[1])
                 C = full.shape[1]
                 h = full.view(B, H, H, C)[:, 1::2, 1::2].reshape(B * (H // 2) * (H // 2), C).contiguous()
                 H //= 2
-        h = self._res(self.mid[0], h, B, H)
-        h = self._attn(self.attn, h, B, H)
-        h = self._res(self.mid[1], h, B, H)
+        h = self._res(self.mid[0], h, B, H, H)
+        h = self._attn(self.attn, h, B, H, H)
+        h = self._res(self.mid[1], h, B, H, H)
         h = ops.groupnorm(h, B, H * H, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
         return ops.conv3x3(h, self.conv_out[0], B, H, H, bias=self.conv_out[1])       # [B*H*H, 2z] fp16
 
@@ -343,9 +342,6 @@ class HipVAEEncoder(HipVAEDecoder):
         m = m.view(B, H, H, self.n_moments).permute(0, 3, 1, 2).float()
         mean, logvar = m.chunk(2, dim=1)
         return mean.contiguous(), logvar.clamp(-30.0, 20.0).contiguous()
-
-    def decode(self, z):
-        raise RuntimeError("HipVAEEncoder encodes; use HipVAEDecoder for decode")
 
 
 class _Config(dict):
@@ -396,8 +392,8 @@ class HipVAE(HipVAEDecoder):
     packs it)."""
 
     def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215):
-        super().__init__(source, device, groups, eps)
-        sd = source.aekl_state_dict() if hasattr(source, "aekl_state_dict") else dict(source)
+        sd = _state_dict(source)
+        super().__init__(sd, device, groups, eps)
         self._encoder_sd = {k: v for k, v in sd.items() if k.startswith(("encoder.", "quant_conv."))}
         self._encoder = None
         self.config = _Config(scaling_factor=scaling_factor)

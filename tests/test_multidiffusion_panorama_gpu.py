@@ -365,12 +365,12 @@ def _square_decode(hip, z):
     o.gemm_launch(o.gemm_desc(o.nchw_to_nhwc8(z), hip.conv_in_w8, h, B * L * L, hip.c_mid, 72, c0=8, lda0=8, taps=9,
                               hin=L, win=L, hout=L, wout=L, res=bias, ldr=hip.c_mid, ldc=hip.c_mid, splits=1))
     H = L
-    h = hip._res(hip.mid[0], h, B, H)
-    h = hip._attn(hip.attn, h, B, H)
-    h = hip._res(hip.mid[1], h, B, H)
+    h = hip._res(hip.mid[0], h, B, H, H)
+    h = hip._attn(hip.attn, h, B, H, H)
+    h = hip._res(hip.mid[1], h, B, H, H)
     for blk, up in hip.ups:
         for r in blk:
-            h = hip._res(r, h, B, H)
+            h = hip._res(r, h, B, H, H)
         if up is not None:
             h = o.conv3x3(h, up[0], B, H, H, bias=up[1], ups=1)
             H *= 2

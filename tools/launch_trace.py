@@ -26,6 +26,9 @@ wrote) and the SAM `__call__` with box prompts and with point prompts (neither p
 so both are traced to their end).  Without transformers they print that they were skipped.  A scenario that raises is
 reported with its exception and the run goes on.
 
+The four `vae_*` scenarios trace the AutoencoderKL blocks on a small seeded `synth_aekl_state_dict`: `HipVAEDecoder.decode`
+on a square and on a rectangular latent, `HipVAEEncoder.encode_moments`, and `HipVAE.encode` on a uint8 image.
+
 Not seen: work torch does by itself (plain `tensor.copy_` of a call's state), and graph replay; the GPU tests that compare
 graph replay with eager runs cover those.  The hashes change with every legitimate change of a plan or a tuning table:
 this is a tool for comparing two trees, not a test, and no expected hash is kept.
@@ -111,7 +114,7 @@ def scenarios(root):
     """name -> callable, in a fixed order; engines and samplers are shared like a process would share them."""
     sys.path.insert(0, root)
     import lgd_amd  # noqa: F401
-    from lgd_amd import multidiffusion, ops, pipeline, sdxl, weights
+    from lgd_amd import multidiffusion, ops, pipeline, sdxl, vae, weights
     from lgd_amd.sampler import Job, LMDSampler
     from lgd_amd.scheduler import DPMSolverMultistepScheduler, PNDMScheduler
     from lgd_amd.unet import UNetEngine
@@ -152,6 +155,10 @@ def scenarios(root):
     lay = pipeline.CachedLayout.synthetic(cfg, boxes, height=256, width=256)
     small = dict(num_inference_steps=4, height=256, width=256, decode=False)
 
+    vsd = vae.synth_aekl_state_dict((32, 32, 64, 64), 1, seed=1)
+    vdec, venc, vpair = vae.HipVAEDecoder(vsd, dev), vae.HipVAEEncoder(vsd, dev), vae.HipVAE(vsd, dev)
+    vimg = torch.randint(0, 256, (1, 32, 32, 3), generator=torch.Generator().manual_seed(10), dtype=torch.uint8)
+
     return rec, {
         "ddim": lambda: sm.denoise_batch([Job(lat, text)], 4),
         "pndm": lambda: sm.denoise_batch([Job(lat, text)], 4, scheduler=PNDMScheduler()),
@@ -174,6 +181,10 @@ def scenarios(root):
         # what bench.py --full times per kernel: every launch sequence the sampler hands out, run once
         "profile_passes": lambda: [fn() for _, _, _, fn in gsm.profile_passes(32, 4, True, main_batches=(1, 2),
                                                                              guide_batches=(1, 2))],
+        "vae_decode": lambda: vdec.decode(rnd(7, (2, 4, 8, 8))),
+        "vae_decode_rect": lambda: vdec.decode(rnd(8, (1, 4, 8, 16))),
+        "vae_encode_moments": lambda: venc.encode_moments(rnd(9, (2, 3, 32, 32))),
+        "vae_encode_u8": lambda: vpair.encode(vimg),
         **towers(root),
     }
 
