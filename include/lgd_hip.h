@@ -578,6 +578,16 @@ int lgd_sam_window_merge_f16(const void* oa, void* out, int B, int Hs, int Ws, i
  *   undone by the out_scale of the final conv_in dgrad).
  *   max_hw <= 4096 (ABI v9; 1024 before): guidance keys at the 64x64 level of a 512^2 SD 1.x network are legal, as
  *   utils/guidance.py accepts any `guidance_attn_keys`; larger maps return LGD_ERR_ARG.
+ * Masks may be any fp32 in [0, 1] (M weighs the inside, 1 - M the outside); map_hw[m] <= max_hw is the row stride of
+ * masks and refs, and elements of a row past map_hw[m] are not read.
+ * Top-k (kind 0) takes the k largest of A*M (and of A*(1-M)) by exact ranking; among equal values THE LOWEST INDEX WINS.
+ * Stored: loss[0 .. n_samples) (0 for an image without items), partial[item*H + h], and, with gmaps, the map_hw
+ * positions of every group's (map, image, head, token) column — element ((image*H + h)*HW + i)*T + token, the sum over
+ * the column's items in table order.  No other element of a gmaps buffer is touched; with n_items = 0 none is.
+ * Refused with LGD_ERR_ARG before any launch: NULL loss; with n_items > 0 a NULL maps, map_hw, items, coefs, masks,
+ * partial or groups, or n_groups < 1; refs without dyn; n_items < 0, n_groups < 0, n_samples < 1, H < 1, T < 1,
+ * max_hw < 1 or > 4096, refs_step_stride < 0; a pointer table (maps, gmaps) off 8 bytes or any other table off 4 bytes.
+ * gmaps is optional; refs and dyn are optional together when no item is of kind 1.
  * ------------------------------------------------------------------------------------------- */
 int lgd_ca_energy_f32(const float* const* maps, float* const* gmaps, const int32_t* map_hw,
                       const int32_t* items, const float* coefs, const float* masks, const float* refs,
@@ -601,7 +611,16 @@ int lgd_ca_energy_f32(const float* const* maps, float* const* gmaps, const int32
  *          corner_mask_y[side] (:64-67); row 2 gt_proj_x[side] | gt_proj_y[side] (:90-91)
  *   smooth: 9 fp32 weights of GaussianSmoothing(kernel_size 3, sigma) (utils/attn.py:92-110) or NULL (no smoothing)
  *   loss: fp32 [n_samples] = loss_scale * energy; the map gradients carry loss_scale * grad_scale.
- * Returns LGD_ERR_UNSUPPORTED for side > 32, T > 128 or more items per image than fit the LDS (70 at 16x16).
+ * Item tokens satisfy 1 <= token <= T-2 (the soft-max runs over those tokens only).  Box masks may be any fp32 in [0, 1].
+ * Top-k takes the k largest of the smoothed image times M (times 1 - M) by exact ranking, and the corner terms the maximum
+ * of every row and column of the smoothed image; among equal values THE LOWEST INDEX WINS in both.
+ * Stored: loss[0 .. n_samples) (0 for an image without items) and, with gmaps, tokens 1 .. T-2 of every (map, image,
+ * head, position) row (zero for an image without items); tokens 0 and T-1 and everything else of a gmaps buffer are
+ * not touched.
+ * Returns LGD_ERR_ARG for a NULL maps, items, masks, groups or loss, n_maps < 1, n_samples < 1, H < 1, max_items < 0, a
+ * pointer table (maps, gmaps) off 8 bytes or another table off 4 bytes; LGD_ERR_UNSUPPORTED for side < 2 or > 32,
+ * T < 3 or > 128, or more items per image than fit the LDS: (7 + 2 max_items) * side*side * 4 bytes <= 150 KB
+ * (71 items at 16x16).  gmaps and smooth are optional.
  * ------------------------------------------------------------------------------------------- */
 int lgd_boxdiff_energy_f32(const float* const* maps, float* const* gmaps, int n_maps, int side, const int32_t* items,
                            const float* masks, const float* smooth, const int32_t* groups, int n_samples,

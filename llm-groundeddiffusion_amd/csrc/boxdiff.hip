@@ -17,7 +17,10 @@
 // Python's `max(0, 1 - v)` of (int, tensor) (:107-109) keeps the tensor only if `tensor > 0`; a top-k of k = 0 elements
 // (a box of fewer than 1 / P pixels) has mean NaN and therefore drops out — reproduced by skipping terms with k = 0.
 #include "common.h"
+#include "contract.h"
 #include "../../include/lgd_hip.h"
+
+using lgd_contract::misaligned;
 
 namespace {
 
@@ -237,9 +240,13 @@ extern "C" int lgd_boxdiff_energy_f32(const float* const* maps, float* const* gm
                                       float loss_scale, float grad_scale, float* loss, void* stream) {
   (void)hipGetLastError();
   if (!maps || !items || !masks || !groups || !loss || n_maps < 1 || n_samples < 1 || H < 1 || max_items < 0) return LGD_ERR_ARG;
+  if (misaligned(maps, 8) || misaligned(gmaps, 8) || misaligned(items, 4) || misaligned(masks, 4) || misaligned(smooth, 4) ||
+      misaligned(groups, 4) || misaligned(loss, 4))
+    return LGD_ERR_ARG;
   if (side < 2 || side > BD_MAXSIDE || side * side > BD_MAXHW || T < 3 || T > 128) return LGD_ERR_UNSUPPORTED;
+  // item images live in LDS: (7 + 2 max_items) side^2 * 4 bytes <= 150 KB (side 16: up to 71 items per image)
   const size_t bytes = (size_t)(7 + 2 * (size_t)max_items) * side * side * sizeof(float);
-  if (bytes > 150 * 1024) return LGD_ERR_UNSUPPORTED;     // item images live in LDS: HW = 256 allows 70 items per image
+  if (bytes > 150 * 1024) return LGD_ERR_UNSUPPORTED;
   // the attribute is per DEVICE and a failure must not stick: set it whenever the launch needs more than the default
   // 64 KB (a host call per launch of an eager-only kernel that runs once per denoising step)
   if (bytes > 64 * 1024 &&

@@ -17,7 +17,10 @@
 // Every normalisation of the reference (1/len(tokens), 1/(n_obj*n_keys), mean over heads for the
 // reference term, loss_scale) is folded into the per-item coefficients by the host.
 #include "common.h"
+#include "contract.h"
 #include "../../include/lgd_hip.h"
+
+using lgd_contract::misaligned;
 
 namespace {
 
@@ -157,8 +160,17 @@ extern "C" int lgd_ca_energy_f32(const float* const* maps, float* const* gmaps,
                                  int n_samples, int H, int T, int max_hw, float grad_scale, float* partial,
                                  float* loss, void* stream) {
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (n_items < 0 || n_groups < 0 || n_samples < 1 || H < 1 || max_hw > E_MAXHW) return LGD_ERR_ARG;
-  if (n_items > 0 && (n_groups < 1 || !groups)) return LGD_ERR_ARG;
+  // everything the host can see from the arguments is answered here, before any other runtime call
+  if (!loss || n_items < 0 || n_groups < 0 || n_samples < 1 || H < 1 || T < 1 || max_hw < 1 || max_hw > E_MAXHW ||
+      refs_step_stride < 0)
+    return LGD_ERR_ARG;
+  if (refs && !dyn) return LGD_ERR_ARG;                  // the step slice of refs is chosen by dyn[0]
+  if (n_items > 0 && (n_groups < 1 || !maps || !map_hw || !items || !coefs || !masks || !partial || !groups))
+    return LGD_ERR_ARG;
+  if (misaligned(maps, 8) || misaligned(gmaps, 8) || misaligned(map_hw, 4) || misaligned(items, 4) || misaligned(coefs, 4) ||
+      misaligned(masks, 4) || misaligned(refs, 4) || misaligned(dyn, 4) || misaligned(groups, 4) || misaligned(partial, 4) ||
+      misaligned(loss, 4))
+    return LGD_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (n_items > 0)
     hipLaunchKernelGGL(ca_energy_kernel, dim3(H, n_groups), dim3(256), 0, st, maps, gmaps, map_hw,

@@ -950,6 +950,26 @@ def select_row(table, idx, out):
 
 def ca_energy(map_ptrs, gmap_ptrs, map_hw, items, coefs, masks, refs, refs_step_stride, dyn, groups, n_groups,
               n_items, H, T, max_hw, partial, loss, grad_scale=1.0, n_samples=1):
+    """Cross-attention energy + map gradients (lgd_ca_energy_f32, include/lgd_hip.h).  With n_items = 0 the tables are
+    placeholders of any size; otherwise their element counts follow from the integer arguments."""
+    some = n_items > 0
+    I32, I64 = torch.int32, torch.int64
+    if refs is not None and dyn is None:
+        raise RuntimeError("ca_energy: refs without dyn (the step slice of refs is chosen by dyn[0])")
+    _operands("ca_energy", ("map_ptrs", map_ptrs, I64, None), ("gmap_ptrs", gmap_ptrs, I64, map_ptrs.numel()),
+              ("map_hw", map_hw, I32, map_ptrs.numel()), ("items", items, I32, 8 * n_items if some else None),
+              ("coefs", coefs, F32, 4 * n_items if some else None), ("masks", masks, F32, None), ("refs", refs, F32, None),
+              ("dyn", dyn, I32, None), ("groups", groups, I32, 2 * n_groups if some else None),
+              ("partial", partial, F32, n_items * H if some else None), ("loss", loss, F32, n_samples))
+    if masks.numel() % max(int(max_hw), 1):
+        raise RuntimeError(f"ca_energy: masks of {masks.numel()} elements are no rows of max_hw = {max_hw}")
+    if dyn is not None and dyn.numel() < 1:
+        raise RuntimeError("ca_energy: dyn holds no element, the kernel reads dyn[0]")
+    if refs is not None and refs.numel() < int(H) * int(max_hw):
+        raise RuntimeError(f"ca_energy: refs holds {refs.numel()} elements, one reference is [H = {H}][max_hw = {max_hw}]")
+    tensors = [t for t in (map_ptrs, gmap_ptrs, map_hw, items, coefs, masks, refs, dyn, groups, partial, loss) if t is not None]
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"ca_energy: operands on different devices: {sorted({str(t.device) for t in tensors})}")
     _prof("ca_energy_kernel + energy_sum_kernel", 4.0 * n_groups * H * max_hw * 2,
           lambda: _call("lgd_ca_energy_f32", _p(map_ptrs), _p(gmap_ptrs), _p(map_hw), _p(items), _p(coefs),
                         _p(masks), _p(refs), int(refs_step_stride), _p(dyn), _p(groups), n_groups, n_items, n_samples, H, T,
@@ -959,6 +979,16 @@ def ca_energy(map_ptrs, gmap_ptrs, map_hw, items, coefs, masks, refs, refs_step_
 def boxdiff_energy(map_ptrs, gmap_ptrs, n_maps, side, items, masks, smooth, groups, n_samples, max_items, H, T,
                    loss_scale, grad_scale, loss):
     """BoxDiff energy + map gradients (lgd_boxdiff_energy_f32, include/lgd_hip.h; utils/boxdiff.py:20-196)."""
+    I32, I64 = torch.int32, torch.int64
+    _operands("boxdiff_energy", ("map_ptrs", map_ptrs, I64, int(n_maps)), ("gmap_ptrs", gmap_ptrs, I64, int(n_maps)),
+              ("items", items, I32, None), ("masks", masks, F32, None), ("smooth", smooth, F32, 9),
+              ("groups", groups, I32, 2 * int(n_samples)), ("loss", loss, F32, int(n_samples)))
+    if items.numel() % 8 or masks.numel() % max(3 * int(side) * int(side), 1):
+        raise RuntimeError(f"boxdiff_energy: items of {items.numel()} elements are no [n][8] table, or masks of {masks.numel()} "
+                           f"no [n][3][{side}*{side}] table")
+    tensors = [t for t in (map_ptrs, gmap_ptrs, items, masks, smooth, groups, loss) if t is not None]
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f"boxdiff_energy: operands on different devices: {sorted({str(t.device) for t in tensors})}")
     _prof("boxdiff_energy_kernel", 4.0 * 2 * n_maps * n_samples * H * side * side * T * 2,
           lambda: _call("lgd_boxdiff_energy_f32", _p(map_ptrs), _p(gmap_ptrs), int(n_maps), int(side), _p(items), _p(masks),
                         _p(smooth), _p(groups), int(n_samples), int(max_items), int(H), int(T), float(loss_scale),

@@ -150,6 +150,11 @@ def _wrapper_faults():
         ("scale_rows: dtype", lambda: ops.scale_rows(h(8), f(8), f(3, 5), i(4), 3)),
         ("select_row: no rows of that length", lambda: ops.select_row(f(4, 300), i(1), f(299))),
         ("select_row: idx dtype", lambda: ops.select_row(f(4, 300), torch.zeros(1, dtype=torch.int64), f(300))),
+        # the two guidance energies: tests/test_energy_kernels_cpu.py holds the full list
+        ("ca_energy: partial count", lambda: ops.ca_energy(torch.zeros(1, dtype=torch.int64), None, i(1), i(3, 8), f(3, 4), f(2, 256), None, 0,
+                                                           None, i(2, 2), 2, 3, 3, 77, 256, f(3), f(1))),
+        ("boxdiff_energy: smooth count", lambda: ops.boxdiff_energy(torch.zeros(2, dtype=torch.int64), None, 2, 16, i(4, 8), f(2, 3, 256), f(3),
+                                                                    i(1, 2), 1, 4, 2, 77, 1.0, 1.0, f(1))),
     ]
 
 
@@ -166,7 +171,8 @@ def test_wrapper_check_raises_before_the_library(what, call, monkeypatch):
 def test_every_wrapper_has_a_check():
     heads = {w.split(":")[0] for w, _ in _FAULTS}
     assert heads == {"add", "scale", "quick_gelu", "act", "geglu_fwd", "geglu_bwd", "softmax_rows", "upsample2x_bwd", "nchw_to_nhwc8",
-                     "conv_out", "conv_in", "cfg_ddim_step", "cfg_multistep_step", "axpy", "scale_rows", "select_row"}
+                     "conv_out", "conv_in", "cfg_ddim_step", "cfg_multistep_step", "axpy", "scale_rows", "select_row", "ca_energy",
+                     "boxdiff_energy"}
 
 
 # ---------------------------------------------------------------------------------------------
