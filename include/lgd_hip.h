@@ -360,13 +360,14 @@ int lgd_attn_variant(int index, int* code, int* env_only, char* name, int name_c
 /* ---------------------------------------------------------------------------------------------
  * Elementwise pieces.
  * ------------------------------------------------------------------------------------------- */
-/* The preconditions an entry point of this section can see from its arguments — NULL-ness, alignment, counts,
+/* The preconditions an entry point of this section — and lgd_act_f16, lgd_sam_relpos_qkv_f16 and
+ * lgd_sam_window_merge_f16 of the SAM section behind it — can see from its arguments — NULL-ness, alignment, counts,
  * divisibility, and the overlap of ranges whose extent the arguments give — are checked on the host, before any runtime
  * call; a call that misses one answers LGD_ERR_ARG and launches nothing.  The rest is the caller's duty and is NOT
  * checked: inputs are finite unless an entry point says otherwise; operands whose extent is not an argument (a
- * coefficient table, frozen_ref, hist, the table of lgd_select_row_f32) are large enough for the row or step the device
- * index selects and share no byte with an output (x_out, x0_prev and hist against frozen_ref and hist; out against the
- * table).
+ * coefficient table, frozen_ref, hist, picks, the table of lgd_select_row_f32) are large enough for the row or step the
+ * device index selects and share no byte with an output (x_out, x0_prev and hist against frozen_ref and hist; out against
+ * the table).
  * "16-byte aligned": the operand moves as vectors of 8 halfs or 4 floats.  "No aliasing": the output range, whose extent
  * the arguments give, shares no byte with an input range.  "y may be x": the output is the input itself or a range apart
  * from it; a partial overlap is refused. */
@@ -397,16 +398,18 @@ int lgd_scale_f16(const void* x, void* y, float alpha, int64_t n, void* stream);
  * followed by lgd_nchw_to_nhwc8_f16's layout, in one pass over the bytes:
  *   x = table[u];  y[pixel] = {fp16(x_r), fp16(x_g), fp16(x_b), fp16(x_r - fp16(x_r)), ..g, ..b, 0, 0}
  * img: uint8 [B][HW][3]; table: device fp32 [256], written by the host as 2 * (u / 255) - 1 in fp32 with true division
- * (what numpy computes at :101-104, exactly); y: fp16 [B*HW][8].  B*HW % 4 == 0, img and table 4-byte and y 16-byte
- * aligned, else LGD_ERR_ARG. */
+ * (what numpy computes at :101-104, exactly); y: fp16 [B*HW][8].  Bit-exact.
+ * B, HW >= 1 and B*HW % 4 == 0 (four pixels are three whole words); img, table, y non-NULL, img and table 4-byte and y
+ * 16-byte aligned; no aliasing (y against the 3*B*HW bytes of img and the 1024 bytes of table). */
 int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, void* y, int B, int HW, void* stream);
 /* Sample of the VAE posterior, scaled (additive export, ABI v12) — models/pipelines.py:110-112 of the reference:
  * vae.encode(image).latent_dist.sample(generator) ([ext] diffusers DiagonalGaussianDistribution: chunk the moments,
  * clamp logvar to [-30, 20], std = exp(0.5 logvar), mean + std * noise) times vae.config.scaling_factor:
  *   out = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise)
  * moments: fp16 [B*HW][2z] as the encoder's last convolution writes them (z means, then z log-variances per pixel);
- * noise, out: NCHW fp32 (B, z, HW).  z % 4 == 0, HW % 4 == 0, moments 8-byte and noise / out 16-byte aligned, else
- * LGD_ERR_ARG. */
+ * noise, out: NCHW fp32 (B, z, HW).  The log-variance may be any finite fp16 value (the clamp is part of the definition).
+ * B >= 1; z, HW >= 4 with z % 4 == 0 and HW % 4 == 0; moments, noise, out non-NULL, moments 8-byte and noise / out 16-byte
+ * aligned; no aliasing (out against moments and against noise). */
 int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int B, int z, int HW, float scale,
                        void* stream);
 /* y = softmax(scale * x) over the last dim, rows x n fp16 (VAE decoder mid-block attention, [ext]
@@ -459,7 +462,13 @@ int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, f
  * a, b fold PNDMScheduler._get_prev_sample (and, for v_prediction, m <- sqrt(a_t) m + sqrt(1-a_t) src) into one affine map.
  * coef_table: device fp32 [E][16] = {w_m, w_0, w_1, w_2, a, b, guidance_scale, push slot (-1 = none), from_cur, save_cur,
  * 0...} (host: scheduler.PNDMScheduler.plms_table); dyn: device int32 {evaluation index, ...}.
- * ets: fp32 [3][B,C,L,L]; cur_sample: fp32 (B,C,L,L).  B*C*HW % 4 == 0 and 16-byte aligned buffers, else LGD_ERR_ARG. */
+ * ets: fp32 [3][B,C,L,L]; cur_sample: fp32 (B,C,L,L).  A ring slot is read only where its weight is not 0 and before the
+ * push, cur_sample only with from_cur; nothing else of ets and cur_sample is written.
+ * Preconditions: eps, x, x_out, ets, cur_sample, coef_table, dyn non-NULL, hist optional; B, C, HW >= 1 and
+ * B*C*HW % 4 == 0; eps, x, x_out, ets, cur_sample, hist 16-byte aligned, coef_table and dyn 4-byte aligned.  x_out may be
+ * x; no aliasing otherwise: x_out is apart from eps, ets and cur_sample, ets (three latents) from eps, x, x_out and
+ * cur_sample, cur_sample from eps, x and x_out.  Not checked (the evaluation count is not an argument): coef_table holds
+ * row dyn[0], hist holds dyn[0] + 2 latents and shares no byte with another operand. */
 int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
                           const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW, void* stream);
 /* One MultiDiffusion step (additive export: LGD_ABI_VERSION stays 12) — generation/multidiffusion.py:226-289 of the
@@ -475,8 +484,14 @@ int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float*
  * eps: fp32 [2Pp][C][HW] = [uncond rows; cond rows]; x_in: fp32 [2Pp][C][HW]; latent, noise: fp32 [C][HW];
  * masks: fp32 [>= P][HW] (broadcast over channels); bg: fp32 [n_boot][C][HW]; picks: device int32 [n_steps][P-1]
  * (rows >= n_boot unused; indices clamped to [0, n_boot)); coef_table: lgd_cfg_ddim_step_f32's fp32 [n_steps][4]
- * {alpha_bar_t, alpha_bar_prev, guidance_scale, v_pred}; dyn: device int32 {step, ...}.  HW % 4 == 0 and 16-byte
- * aligned buffers, else LGD_ERR_ARG. */
+ * {alpha_bar_t, alpha_bar_prev, guidance_scale, v_pred}; dyn: device int32 {step, ...}.  A step outside [0, n_steps)
+ * writes nothing; the last step writes latent and hist and leaves x_in as it is.
+ * Preconditions: x_in, latent, masks, coef_table, dyn non-NULL; eps non-NULL unless prep = 1 (not read then); bg, noise
+ * and picks non-NULL when n_boot > 0 and P > 1 (not read otherwise); hist optional; 1 <= P <= Pp; C, HW, n_steps >= 1;
+ * HW % 4 == 0; n_boot >= 0; prep 0 or 1; eps, x_in, latent, masks, bg, noise, hist 16-byte aligned, picks, coef_table and
+ * dyn 4-byte aligned.  No aliasing: the outputs x_in (2*Pp rows) and latent are apart from each other and from eps
+ * (2*Pp rows), masks (P planes), and, when bootstrapping, bg (n_boot latents) and noise.  Not checked: the extents of
+ * picks, coef_table and hist ([n_steps+1] latents), and hist against the other operands. */
 int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float* latent, const float* masks, const float* bg,
                                 const float* noise, const int32_t* picks, const float* coef_table, const int32_t* dyn,
                                 float* hist, int P, int Pp, int C, int HW, int n_steps, int n_boot, int prep,
@@ -501,9 +516,16 @@ int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float* latent, co
  *     and the result does not depend on how the V views are split into chunks.
  * eps, x_in: fp32 [2*nvc*Pp][C][64*64]; latent, value, count, noise: fp32 [C][Hp][Wp]; masks: fp32 [>= P][Hp][Wp];
  * bg: fp32 [n_boot][C][64*64]; picks: device int32 [n_steps][V][P-1] (indices clamped to [0, n_boot)); hist: fp32
- * [n_steps+1][C][Hp][Wp] or NULL; coef_table, dyn: as lgd_multidiffusion_step_f32.  value / count may be NULL when one
- * chunk holds all views (count also without normalization).  Hp, Wp >= 64, Wp % 4 == 0, P <= Pp, the view range inside
- * V = nbh*nbw, nv <= nvc, 16-byte aligned buffers, bg / noise / picks present when bootstrapping: else LGD_ERR_ARG. */
+ * [n_steps+1][C][Hp][Wp] or NULL; coef_table, dyn: as lgd_multidiffusion_step_f32.  A step outside [0, n_steps) writes
+ * nothing; x_in rows of views outside [v0, v0+nv) are not written.
+ * Preconditions: x_in, latent, masks, coef_table, dyn non-NULL; eps non-NULL unless prep = 1; value non-NULL, and count
+ * with normalization, unless prep = 1 or one chunk holds all views (v0 == 0 and nv == V); bg, noise and picks non-NULL
+ * when prep = 1, n_boot > 0 and P > 1; hist optional; 1 <= P <= Pp; 1 <= C <= 64; 64 <= Hp, Wp <= 4096; Wp % 4 == 0;
+ * V == nbh*nbw; v0 >= 0, nv >= 1, v0 + nv <= V, nv <= nvc, nvc*Pp <= 2^20; n_steps >= 1; n_boot >= 0; prep 0 or 1; eps, x_in,
+ * latent, value, count, masks, bg, noise, hist 16-byte aligned, picks, coef_table and dyn 4-byte aligned.  No aliasing:
+ * with prep = 1 the output x_in (2*nvc*Pp rows) is apart from latent, masks (P planes) and, when bootstrapping, bg (n_boot
+ * rows) and noise; with prep = 0 the outputs latent, value and count are apart from each other and from eps, x_in and
+ * masks.  Not checked: the extents of picks, coef_table and hist, and hist against the other operands. */
 int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float* latent, float* value, float* count,
                                  const float* masks, const float* bg, const float* noise, const int32_t* picks,
                                  const float* coef_table, const int32_t* dyn, float* hist, int P, int Pp, int C, int Hp,
@@ -547,12 +569,19 @@ int lgd_act_f16(const void* x, void* y, int64_t n, int mode, void* stream);
  *   qa = [q | q.Rh[qy-j+S-1]/scale, j<S | q.Rw[qx-j+S-1]/scale, j<S | 0],  ka = [k | onehot(ky) | onehot(kx) | 0],
  *   va = [v | 0],   DA >= d + 2*S, DA % 8 == 0,
  * so that lgd_attn_fwd_f16(qa, ka, va, d = DA, scale) computes softmax(scale*q.k + rel_h + rel_w) v in columns 0..d-1
- * of every head. */
+ * of every head.  Rows of padded window positions are written too: q, k, v = fp16(qkv_bias), the rel columns from the
+ * fp32 bias.  The rel columns are fp32 dot products of d terms times 1/scale, rounded once to fp16; the rest is copied.
+ * Preconditions: all seven pointers non-NULL; qkv, qa, ka, va 2-byte and qkv_bias, rel_h, rel_w 4-byte aligned (scalar
+ * accesses); B, Hs, Ws, NH >= 1; d >= 8 and d % 8 == 0; DA % 8 == 0 and DA >= d + 2*S; window >= 0, window == 0 only
+ * with Hs == Ws; scale > 0 (NaN is refused).  No aliasing: qa, ka and va are apart from each other and from qkv, qkv_bias,
+ * rel_h and rel_w.  LGD_ERR_UNSUPPORTED: more than 2^31 - 1 window rows, or NH*(d + 2*S) floats past 64 KB of LDS. */
 int lgd_sam_relpos_qkv_f16(const void* qkv, const float* qkv_bias, const float* rel_h, const float* rel_w, int B,
                            int Hs, int Ws, int window, int NH, int d, int DA, float scale, void* qa, void* ka,
                            void* va, void* stream);
 /* Inverse gather (SamVisionLayer.window_unpartition): oa [B*nwin*S*S][NH*DA] in window order -> out [B*Hs*Ws][NH*d]
- * in raster order, padding positions and the DA-d extra columns dropped. */
+ * in raster order, padding positions and the DA-d extra columns dropped (they are not read).  Bit-exact.
+ * oa, out non-NULL and 16-byte aligned; B, Hs, Ws, NH >= 1; d >= 8 and d % 8 == 0; DA % 8 == 0 and DA >= d; window >= 0,
+ * window == 0 only with Hs == Ws; no aliasing.  LGD_ERR_UNSUPPORTED: more than 2^31 - 1 tokens. */
 int lgd_sam_window_merge_f16(const void* oa, void* out, int B, int Hs, int Ws, int window, int NH, int d, int DA,
                              void* stream);
 

@@ -1,4 +1,4 @@
-// Host-side precondition helpers of the small-kernel entry points (misc.hip, lgd_act_f16 of sam.hip): alignment and
+// Host-side precondition helpers of the small-kernel entry points (misc.hip, sam.hip): alignment and
 // the overlap of operand ranges.  Plain pointer arithmetic: everything here is answered before any runtime call.
 #pragma once
 #include <stdint.h>

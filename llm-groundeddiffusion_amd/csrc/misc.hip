@@ -811,12 +811,12 @@ extern "C" int lgd_nchw_to_nhwc8_f16(const float* x, void* y, int B, int C, int 
 }
 
 extern "C" int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, void* y, int B, int HW, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!img || !table || !y || B < 1 || HW < 1) return LGD_ERR_ARG;
   const long npix = (long)B * HW;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if ((npix & 3) || misaligned(img, 4) || misaligned(table, 4) || misaligned(y, 16))
     return LGD_ERR_ARG;  // four pixels = three whole 4-byte words in, four 16-byte vectors out
+  if (overlaps(y, (int64_t)npix * 16, img, (int64_t)npix * 3) || overlaps(y, (int64_t)npix * 16, table, 256 * 4)) return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(image_u8_to_nhwc8_kernel, dim3(ew_blocks(npix / 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), (const uint32_t*)img, table, (half_t*)y, npix / 4);
   return lgd_check_launch();
@@ -824,11 +824,14 @@ extern "C" int lgd_image_u8_to_nhwc8_f16(const void* img, const float* table, vo
 
 extern "C" int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int B, int z, int HW, float scale,
                                   void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!moments || !noise || !out || B < 1 || z < 4 || HW < 4) return LGD_ERR_ARG;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if ((z & 3) || (HW & 3) || misaligned(moments, 8) || misaligned(noise, 16) || misaligned(out, 16))
     return LGD_ERR_ARG;  // 8-byte vectors of 4 moments, 16-byte vectors of 4 pixels
+  {
+    const int64_t ob = (int64_t)B * z * HW * 4;
+    if (overlaps(out, ob, moments, ob) || overlaps(out, ob, noise, ob)) return LGD_ERR_ARG;  // moments: 2z halfs per pixel
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const long total = (long)B * (z / 4) * (HW / 4);
   hipLaunchKernelGGL(vae_sample_kernel, dim3(ew_blocks(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      (const half_t*)moments, noise, out, z, (long)HW, scale, total);
@@ -921,14 +924,22 @@ extern "C" int lgd_cfg_multistep_step_f32(const float* eps, const float* x, floa
 extern "C" int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
                                      const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW,
                                      void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!eps || !x || !x_out || !ets || !cur_sample || !coef_table || !dyn || B < 1 || C < 1 || HW < 1)
     return LGD_ERR_ARG;
   const long n = (long)B * C * HW;
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-  if ((n & 3) || misaligned(eps) || misaligned(x) || misaligned(x_out) || misaligned(ets) || misaligned(cur_sample) ||
-      misaligned(hist))
+  if ((n & 3) || misaligned(eps, 16) || misaligned(x, 16) || misaligned(x_out, 16) || misaligned(ets, 16) ||
+      misaligned(cur_sample, 16) || misaligned(hist, 16) || misaligned(coef_table, 4) || misaligned(dyn, 4))
     return LGD_ERR_ARG;  // 16-byte vectors: every plane starts on a vector boundary
+  {
+    const int64_t nb = (int64_t)n * 4;  // x_out is x itself or apart; the ring and the saved sample are read and rewritten
+    if (partly_overlaps(x_out, x, nb) || overlaps(x_out, nb, eps, 2 * nb) || overlaps(x_out, nb, ets, 3 * nb) ||
+        overlaps(x_out, nb, cur_sample, nb))
+      return LGD_ERR_ARG;
+    if (overlaps(ets, 3 * nb, eps, 2 * nb) || overlaps(ets, 3 * nb, x, nb) || overlaps(ets, 3 * nb, cur_sample, nb))
+      return LGD_ERR_ARG;
+    if (overlaps(cur_sample, nb, eps, 2 * nb) || overlaps(cur_sample, nb, x, nb)) return LGD_ERR_ARG;
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(cfg_plms_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eps,
                      x, x_out, ets, cur_sample, coef_table, dyn, hist, n);
   return lgd_check_launch();
@@ -938,16 +949,26 @@ extern "C" int lgd_multidiffusion_step_f32(const float* eps, float* x_in, float*
                                            const float* bg, const float* noise, const int32_t* picks,
                                            const float* coef_table, const int32_t* dyn, float* hist, int P, int Pp,
                                            int C, int HW, int n_steps, int n_boot, int prep, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!x_in || !latent || !masks || !coef_table || !dyn || P < 1 || Pp < P || C < 1 || HW < 1 || n_steps < 1 ||
       n_boot < 0 || (prep != 0 && prep != 1) || (!prep && !eps))
     return LGD_ERR_ARG;
-  if (n_boot > 0 && P > 1 && (!bg || !noise || !picks)) return LGD_ERR_ARG;
+  const bool boots = n_boot > 0 && P > 1;
+  if (boots && (!bg || !noise || !picks)) return LGD_ERR_ARG;
   const long n = (long)C * HW;
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-  if ((HW & 3) || misaligned(eps) || misaligned(x_in) || misaligned(latent) || misaligned(masks) || misaligned(bg) ||
-      misaligned(noise) || misaligned(hist))
+  if ((HW & 3) || misaligned(eps, 16) || misaligned(x_in, 16) || misaligned(latent, 16) || misaligned(masks, 16) ||
+      misaligned(bg, 16) || misaligned(noise, 16) || misaligned(hist, 16) || misaligned(picks, 4) ||
+      misaligned(coef_table, 4) || misaligned(dyn, 4))
     return LGD_ERR_ARG;  // 16-byte vectors: every plane and mask row starts on a vector boundary
+  {
+    const int64_t nb = (int64_t)n * 4, rows = 2 * (int64_t)Pp * nb, mb = (int64_t)P * HW * 4;
+    if (overlaps(x_in, rows, latent, nb) || overlaps(x_in, rows, eps, rows) || overlaps(latent, nb, eps, rows) ||
+        overlaps(x_in, rows, masks, mb) || overlaps(latent, nb, masks, mb))
+      return LGD_ERR_ARG;
+    if (boots && (overlaps(x_in, rows, bg, n_boot * nb) || overlaps(latent, nb, bg, n_boot * nb) ||
+                  overlaps(x_in, rows, noise, nb) || overlaps(latent, nb, noise, nb)))
+      return LGD_ERR_ARG;
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const long nv = n / 4;
   hipLaunchKernelGGL(multidiffusion_step_kernel, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0,
                      reinterpret_cast<hipStream_t>(stream), eps, x_in, latent, masks, bg, noise, picks, coef_table,
@@ -961,7 +982,6 @@ extern "C" int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float
                                             float* hist, int P, int Pp, int C, int Hp, int Wp, int V, int v0, int nv,
                                             int nvc, int n_steps, int n_boot, int indep_uncond, int normalization,
                                             int prep, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   if (!x_in || !latent || !masks || !coef_table || !dyn || P < 1 || Pp < P || C < 1 || n_steps < 1 || n_boot < 0 ||
       (prep != 0 && prep != 1) || (!prep && !eps))
     return LGD_ERR_ARG;
@@ -970,11 +990,29 @@ extern "C" int lgd_multidiffusion_views_f32(const float* eps, float* x_in, float
   if (V != nbh * nbw || v0 < 0 || nv < 1 || v0 + nv > V || nvc < nv || (long)nvc * Pp > (1 << 20)) return LGD_ERR_ARG;
   const bool single = v0 == 0 && nv == V;
   if (!prep && !single && (!value || (normalization && !count))) return LGD_ERR_ARG;
-  if (prep && n_boot > 0 && P > 1 && (!bg || !noise || !picks)) return LGD_ERR_ARG;
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-  if (misaligned(eps) || misaligned(x_in) || misaligned(latent) || misaligned(value) || misaligned(count) ||
-      misaligned(masks) || misaligned(bg) || misaligned(noise) || misaligned(hist))
+  const bool boots = prep && n_boot > 0 && P > 1;
+  if (boots && (!bg || !noise || !picks)) return LGD_ERR_ARG;
+  if (misaligned(eps, 16) || misaligned(x_in, 16) || misaligned(latent, 16) || misaligned(value, 16) ||
+      misaligned(count, 16) || misaligned(masks, 16) || misaligned(bg, 16) || misaligned(noise, 16) ||
+      misaligned(hist, 16) || misaligned(picks, 4) || misaligned(coef_table, 4) || misaligned(dyn, 4))
     return LGD_ERR_ARG;  // 16-byte vectors: every plane, window row and mask row starts on a vector boundary
+  {
+    const int64_t wb = (int64_t)C * MD_WHW * 4, rows = 2 * (int64_t)nvc * Pp * wb, pb = (int64_t)C * Hp * Wp * 4,
+                  mb = (int64_t)P * Hp * Wp * 4;
+    if (prep) {
+      if (overlaps(x_in, rows, latent, pb) || overlaps(x_in, rows, masks, mb)) return LGD_ERR_ARG;
+      if (boots && (overlaps(x_in, rows, bg, n_boot * wb) || overlaps(x_in, rows, noise, pb))) return LGD_ERR_ARG;
+    } else {
+      const float* outs[3] = {latent, value, count};
+      for (int i = 0; i < 3; ++i) {
+        if (overlaps(outs[i], pb, eps, rows) || overlaps(outs[i], pb, x_in, rows) || overlaps(outs[i], pb, masks, mb))
+          return LGD_ERR_ARG;
+        for (int j = i + 1; j < 3; ++j)
+          if (overlaps(outs[i], pb, outs[j], pb)) return LGD_ERR_ARG;
+      }
+    }
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (prep) {
     const long nt = (long)nv * C * (MD_WHW / 4);

@@ -116,9 +116,14 @@ __global__ __launch_bounds__(256) void act_kernel(const half_t* a, half_t* y, lo
 extern "C" int lgd_sam_relpos_qkv_f16(const void* qkv, const float* qkv_bias, const float* rel_h, const float* rel_w,
                                       int B, int Hs, int Ws, int window, int NH, int d, int DA, float scale, void* qa,
                                       void* ka, void* va, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (B < 1 || Hs < 1 || Ws < 1 || NH < 1 || d < 8 || (d % 8) || (DA % 8) || window < 0 || scale <= 0.f) return LGD_ERR_ARG;
+  using lgd_contract::misaligned;
+  using lgd_contract::overlaps;
+  if (!qkv || !qkv_bias || !rel_h || !rel_w || !qa || !ka || !va) return LGD_ERR_ARG;
+  if (B < 1 || Hs < 1 || Ws < 1 || NH < 1 || d < 8 || (d % 8) || (DA % 8) || window < 0 || !(scale > 0.f)) return LGD_ERR_ARG;
   if (window == 0 && Hs != Ws) return LGD_ERR_ARG;  // global attention: one window = the whole (square) grid
+  if (misaligned(qkv, 2) || misaligned(qa, 2) || misaligned(ka, 2) || misaligned(va, 2) || misaligned(qkv_bias, 4) ||
+      misaligned(rel_h, 4) || misaligned(rel_w, 4))
+    return LGD_ERR_ARG;  // scalar accesses: halfs and floats
   RelposArgs a;
   a.S = window ? window : Hs;
   if (DA < d + 2 * a.S) return LGD_ERR_ARG;
@@ -128,22 +133,40 @@ extern "C" int lgd_sam_relpos_qkv_f16(const void* qkv, const float* qkv_bias, co
   a.nwy = (Hs + a.S - 1) / a.S; a.nwx = (Ws + a.S - 1) / a.S;
   a.inv_scale = 1.f / scale;
   const long blocks = (long)B * a.nwy * a.nwx * a.S * a.S;
-  const size_t lds = (size_t)(NH * d + NH * 2 * a.S) * sizeof(float);
+  const size_t lds = (size_t)((long)NH * d + (long)NH * 2 * a.S) * sizeof(float);
   if (blocks > 0x7fffffffL || lds > 64 * 1024) return LGD_ERR_UNSUPPORTED;
+  {
+    const int64_t ob = (int64_t)blocks * NH * DA * 2, rb = (int64_t)(2 * a.S - 1) * d * 4;
+    const void* in[4] = {qkv, qkv_bias, rel_h, rel_w};
+    const int64_t inb[4] = {(int64_t)B * Hs * Ws * 3 * NH * d * 2, (int64_t)3 * NH * d * 4, rb, rb};
+    const void* out[3] = {qa, ka, va};
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 4; ++j)
+        if (overlaps(out[i], ob, in[j], inb[j])) return LGD_ERR_ARG;
+      for (int j = i + 1; j < 3; ++j)
+        if (overlaps(out[i], ob, out[j], ob)) return LGD_ERR_ARG;
+    }
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(sam_relpos_qkv_kernel, dim3((unsigned)blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
   return lgd_check_launch();
 }
 
 extern "C" int lgd_sam_window_merge_f16(const void* oa, void* out, int B, int Hs, int Ws, int window, int NH, int d,
                                         int DA, void* stream) {
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (B < 1 || Hs < 1 || Ws < 1 || NH < 1 || d < 8 || (d % 8) || (DA % 8) || DA < d || window < 0) return LGD_ERR_ARG;
+  if (!oa || !out || B < 1 || Hs < 1 || Ws < 1 || NH < 1 || d < 8 || (d % 8) || (DA % 8) || DA < d || window < 0)
+    return LGD_ERR_ARG;
   if (window == 0 && Hs != Ws) return LGD_ERR_ARG;
+  if (lgd_contract::misaligned(oa, 16) || lgd_contract::misaligned(out, 16)) return LGD_ERR_ARG;  // vectors of 8 halfs
   const int S = window ? window : Hs;
+  const int nwy = (Hs + S - 1) / S, nwx = (Ws + S - 1) / S;
   const long blocks = (long)B * Hs * Ws;
   if (blocks > 0x7fffffffL) return LGD_ERR_UNSUPPORTED;
+  if (lgd_contract::overlaps(out, (int64_t)blocks * NH * d * 2, oa, (int64_t)B * nwy * nwx * S * S * NH * DA * 2))
+    return LGD_ERR_ARG;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(sam_window_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     (const half_t*)oa, (half_t*)out, B, Hs, Ws, S, (Hs + S - 1) / S, (Ws + S - 1) / S, NH, d, DA);
+                     (const half_t*)oa, (half_t*)out, B, Hs, Ws, S, nwy, nwx, NH, d, DA);
   return lgd_check_launch();
 }
 

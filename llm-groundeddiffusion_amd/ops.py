@@ -447,22 +447,25 @@ def u8_table(device) -> torch.Tensor:
 
 def image_u8_to_nhwc8(img_u8, out=None):
     """uint8 (B, H, W, 3) on the device -> [B*H*W, 8] fp16: value, rounding remainder, zeros (lgd_hip.h)."""
-    B, H, W, C_ = img_u8.shape
-    if C_ != 3 or img_u8.dtype != torch.uint8 or not img_u8.is_contiguous():
-        raise RuntimeError("image_u8_to_nhwc8 takes a contiguous uint8 (B, H, W, 3) tensor")
+    if img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise RuntimeError(f"image_u8_to_nhwc8: img {tuple(img_u8.shape)} is not (B, H, W, 3)")
+    B, H, W, _ = img_u8.shape
     if out is None:
         out = torch.empty((B * H * W, 8), device=img_u8.device, dtype=F16)
+    _operands("image_u8_to_nhwc8", ("img", img_u8, torch.uint8, None), ("out", out, F16, B * H * W * 8))
     _call("lgd_image_u8_to_nhwc8_f16", _p(img_u8), _p(u8_table(img_u8.device)), _p(out), B, H * W, _stream())
     return out
 
 
 def vae_sample(moments, noise, scale, out=None):
     """moments fp16 [B*HW, 2z] (channels-last), noise fp32 (B, z, H, W) -> scale * (mean + std * noise), NCHW fp32."""
+    if noise.dim() != 4:
+        raise RuntimeError(f"vae_sample: noise {tuple(noise.shape)} is not (B, z, H, W)")
     B, z, H, W = noise.shape
-    if tuple(moments.shape) != (B * H * W, 2 * z) or moments.dtype != F16 or noise.dtype != F32:
-        raise RuntimeError(f"vae_sample: moments {tuple(moments.shape)} {moments.dtype} for noise {tuple(noise.shape)}")
     if out is None:
         out = torch.empty_like(noise)
+    _operands("vae_sample", ("moments", moments, F16, B * H * W * 2 * z), ("noise", noise, F32, None),
+              ("out", out, F32, noise.numel()))
     _call("lgd_vae_sample_f32", _p(moments), _p(noise), _p(out), B, z, H * W, float(scale), _stream())
     return out
 
@@ -755,19 +758,29 @@ def act(x, mode, out=None):
     return out
 
 
-def sam_relpos_qkv(qkv, qkv_bias, rel_h, rel_w, B, Hs, Ws, window, NH, d, DA, scale):
+def _sam_rows(B, Hs, Ws, window):
+    S = window or Hs
+    return B * (-(-Hs // S)) * (-(-Ws // S)) * S * S, S
+
+
+def sam_relpos_qkv(qkv, qkv_bias, rel_h, rel_w, B, Hs, Ws, window, NH, d, DA, scale, qa=None, ka=None, va=None):
     """Window partition + decomposed rel-pos bias folded into the attention operands (csrc/sam.hip).
     Returns qa, ka, va [B*nwin*S*S, NH*DA] fp16."""
-    S = window or Hs
-    rows = B * (-(-Hs // S)) * (-(-Ws // S)) * S * S
-    qa, ka, va = (torch.empty((rows, NH * DA), device=qkv.device, dtype=F16) for _ in range(3))
+    rows, S = _sam_rows(B, Hs, Ws, window)
+    qa, ka, va = (torch.empty((rows, NH * DA), device=qkv.device, dtype=F16) if t is None else t for t in (qa, ka, va))
+    _operands("sam_relpos_qkv", ("qkv", qkv, F16, B * Hs * Ws * 3 * NH * d), ("qkv_bias", qkv_bias, F32, 3 * NH * d),
+              ("rel_h", rel_h, F32, (2 * S - 1) * d), ("rel_w", rel_w, F32, (2 * S - 1) * d), ("qa", qa, F16, rows * NH * DA),
+              ("ka", ka, F16, rows * NH * DA), ("va", va, F16, rows * NH * DA))
     _call("lgd_sam_relpos_qkv_f16", _p(qkv), _p(qkv_bias), _p(rel_h), _p(rel_w), B, Hs, Ws, window, NH, d, DA,
           float(scale), _p(qa), _p(ka), _p(va), _stream())
     return qa, ka, va
 
 
-def sam_window_merge(oa, B, Hs, Ws, window, NH, d, DA):
-    out = torch.empty((B * Hs * Ws, NH * d), device=oa.device, dtype=F16)
+def sam_window_merge(oa, B, Hs, Ws, window, NH, d, DA, out=None):
+    rows, _ = _sam_rows(B, Hs, Ws, window)
+    if out is None:
+        out = torch.empty((B * Hs * Ws, NH * d), device=oa.device, dtype=F16)
+    _operands("sam_window_merge", ("oa", oa, F16, rows * NH * DA), ("out", out, F16, B * Hs * Ws * NH * d))
     _call("lgd_sam_window_merge_f16", _p(oa), _p(out), B, Hs, Ws, window, NH, d, DA, _stream())
     return out
 
@@ -878,25 +891,66 @@ def cfg_multistep_step(eps, x, x_out, x0_prev, coef_table, dyn, *, frozen_ref=No
     return x_out
 
 
+def _at_least(fn, name, t, count):
+    if t is not None and t.numel() < count:
+        raise RuntimeError(f"{fn}: {name} holds {t.numel()} elements, the call addresses {count}")
+
+
 def cfg_plms_step(eps, x, x_out, ets, cur_sample, coef_table, dyn, *, hist=None):
     """CFG + one PLMS evaluation (PNDMScheduler, skip_prk_steps); coef_table fp32 [E][16], ets fp32 [3, *x.shape],
     see lgd_hip.h."""
-    B, C_, L, _ = x.shape
+    if x.dim() != 4:
+        raise RuntimeError(f"cfg_plms_step: x {tuple(x.shape)} is not (B, C, H, W)")
+    B, C_, H, W = x.shape
+    n = x.numel()
+    _operands("cfg_plms_step", ("eps", eps, F32, 2 * n), ("x", x, F32, None), ("x_out", x_out, F32, n), ("ets", ets, F32, 3 * n),
+              ("cur_sample", cur_sample, F32, n), ("coef_table", coef_table, F32, None), ("dyn", dyn, torch.int32, None),
+              ("hist", hist, F32, None))
+    if coef_table.numel() % 16 or dyn.numel() < 1:
+        raise RuntimeError("cfg_plms_step: the table is not [E][16] or dyn is empty")
+    if hist is not None and hist.numel() % n:
+        raise RuntimeError(f"cfg_plms_step: hist holds {hist.numel()} elements, no whole number of latents of {n}")
     _prof("cfg_plms_kernel", 4.0 * x.numel() * 7,
           lambda: _call("lgd_cfg_plms_step_f32", _p(eps), _p(x), _p(x_out), _p(ets), _p(cur_sample), _p(coef_table),
-                        _p(dyn), _p(hist), B, C_, L * L, _stream()))
+                        _p(dyn), _p(hist), B, C_, H * W, _stream()))
     return x_out
+
+
+def _md_operands(fn, eps, x_in, latent, masks, coef_table, dyn, bg, noise, picks, hist, P, plane, bg_plane, n_picks,
+                 n_steps, n_boot, prep):
+    """The operands the two MultiDiffusion entry points share: eps the size of x_in (not read with prep), masks at least P
+    planes, bg at least n_boot latents, picks at least n_picks indices, hist whole latents; plane = Hp * Wp elements."""
+    n = latent.numel()
+    _operands(fn, ("eps", None if prep else eps, F32, x_in.numel()), ("x_in", x_in, F32, None), ("latent", latent, F32, None),
+              ("masks", masks, F32, None), ("coef_table", coef_table, F32, None), ("dyn", dyn, torch.int32, None),
+              ("bg", bg, F32, None), ("noise", noise, F32, n), ("picks", picks, torch.int32, None), ("hist", hist, F32, None))
+    if not prep and eps is None:
+        raise RuntimeError(f"{fn}: eps is missing")
+    _at_least(fn, "masks", masks, P * plane)
+    _at_least(fn, "coef_table", coef_table, 4 * n_steps)
+    _at_least(fn, "dyn", dyn, 1)
+    if n_boot > 0 and P > 1:
+        _at_least(fn, "bg", bg, n_boot * bg_plane)
+        _at_least(fn, "picks", picks, n_picks)
+    if hist is not None and hist.numel() % n:
+        raise RuntimeError(f"{fn}: hist holds {hist.numel()} elements, no whole number of latents of {n}")
 
 
 def multidiffusion_step(eps, x_in, latent, masks, coef_table, dyn, *, n_prompts, n_steps, bg=None, noise=None,
                         picks=None, n_boot=0, hist=None, prep=False):
     """One MultiDiffusion step (CFG + P DDIM steps + masked sum) and the next step's UNet input rows, or with prep=True
-    only the input rows of step dyn[0] from `latent`; x_in / eps fp32 (2Pp, C, L, L), see lgd_hip.h."""
-    Pp2, C_, L, _ = x_in.shape
+    only the input rows of step dyn[0] from `latent`; x_in / eps fp32 (2Pp, C, H, W), see lgd_hip.h."""
+    if x_in.dim() != 4 or x_in.shape[0] % 2:
+        raise RuntimeError(f"multidiffusion_step: x_in {tuple(x_in.shape)} is not (2 Pp, C, H, W)")
+    Pp2, C_, H, W = x_in.shape
     P = int(n_prompts)
+    if latent.numel() != C_ * H * W:
+        raise RuntimeError(f"multidiffusion_step: latent {tuple(latent.shape)} is no row of x_in {tuple(x_in.shape)}")
+    _md_operands("multidiffusion_step", eps, x_in, latent, masks, coef_table, dyn, bg, noise, picks, hist, P, H * W,
+                 C_ * H * W, int(n_steps) * (P - 1), int(n_steps), int(n_boot), prep)
     _prof("multidiffusion_step_kernel", 4.0 * latent.numel() * (2 + (0 if prep else 3 * P) + Pp2),
           lambda: _call("lgd_multidiffusion_step_f32", _p(None if prep else eps), _p(x_in), _p(latent), _p(masks),
-                        _p(bg), _p(noise), _p(picks), _p(coef_table), _p(dyn), _p(hist), P, Pp2 // 2, C_, L * L,
+                        _p(bg), _p(noise), _p(picks), _p(coef_table), _p(dyn), _p(hist), P, Pp2 // 2, C_, H * W,
                         int(n_steps), int(n_boot), 1 if prep else 0, _stream()))
     return latent
 
@@ -907,11 +961,18 @@ def multidiffusion_views(eps, x_in, latent, value, count, masks, coef_table, dyn
     """MultiDiffusion over overlapping 64x64 views of the panorama `latent` (C, Hp, Wp) for the chunk of views
     [v0, v0 + nv): with prep=True the chunk's UNet input rows of step dyn[0], else the chunk's share of value / count
     and, behind the last view, the blended latent; x_in / eps fp32 (2 * nvc * rows_per_view, C, 64, 64), see lgd_hip.h."""
+    if x_in.dim() != 4 or latent.dim() != 3:
+        raise RuntimeError(f"multidiffusion_views: x_in {tuple(x_in.shape)}, latent {tuple(latent.shape)}: want 4 and 3 dimensions")
     rows, C_, L, _ = x_in.shape
     P, Pp = int(n_prompts), int(rows_per_view)
     _, Hp, Wp = latent.shape
     if L != 64 or rows % (2 * Pp) or tuple(x_in.shape[2:]) != (64, 64) or (eps is not None and eps.shape != x_in.shape):
         raise RuntimeError(f"multidiffusion_views: x_in {tuple(x_in.shape)} is not (2 * views * {Pp}, C, 64, 64)")
+    if latent.shape[0] != C_:
+        raise RuntimeError(f"multidiffusion_views: latent {tuple(latent.shape)} for x_in {tuple(x_in.shape)}")
+    _md_operands("multidiffusion_views", eps, x_in, latent, masks, coef_table, dyn, bg, noise, picks, hist, P, Hp * Wp,
+                 C_ * 4096, int(n_steps) * int(n_views) * (P - 1), int(n_steps), int(n_boot) if prep else 0, prep)
+    _operands("multidiffusion_views", ("value", value, F32, latent.numel()), ("count", count, F32, latent.numel()))
     nvc = rows // (2 * Pp)
     nbytes = 4.0 * C_ * 4096 * nv * (1 + 2 * Pp) if prep else 4.0 * (C_ * 4096 * nv * 3 * P + latent.numel() * 6)
     _prof("multidiffusion_views_prep_kernel" if prep else "multidiffusion_views_accum_kernel", nbytes,

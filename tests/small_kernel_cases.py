@@ -1,4 +1,4 @@
-"""The launch contract of the small kernels (csrc/misc.hip, lgd_act_f16 of csrc/sam.hip) as test data.
+"""The launch contract of the small kernels (csrc/misc.hip, csrc/sam.hip) as test data.
 
 A ROW is (entry point, shape, form).  `row.data(pass_name)` holds the logical operands on the host, `reference(row, d)` the
 fp64 result and the derived bound of every output element, `emulate(row, d)` an fp32 rendering of the kernel's arithmetic
@@ -42,6 +42,21 @@ a zero is not checked.
   conv_in        acc = bias, then K = 9 Cin sequential x w products (one rounding each, one per add):
                  e = (2 K + 1) w (|bias| + sum |x w|); R16
   cfg_ddim, cfg_multistep, axpy, scale_rows: the header's formulas through V, fp32 outputs.
+  cfg_plms       m = eu + gs (ec - eu); comb = w_m m + w_0 ets[0] + w_1 ets[1] + w_2 ets[2] in slot order, zero weights skipped;
+                 x' = a src + b comb, all through V with the fp32 coefficients of PNDMScheduler.plms_table; the pushed slot is m
+                 within m's bound; the saved sample and every other slot bit for bit
+  md_step        per prompt the cfg_ddim formula through V, times the mask, summed in prompt order; x_in rows are that latent
+                 (bound carried over; the copies among them bit for bit), bootstrapped rows sqrt(a) bg + sqrt(1 - a) noise through V
+                 where mask < 0.5 (the blend with b in {0, 1} is exact)
+  md_views       the same per view: sum over prompts first, then into the panorama in ascending view order, through V; count
+                 likewise; value / count through V's division where count > 0; uncovered elements exactly 0
+  image_u8       bit-exact from the table: fp16(x), fp16(x - fp16(x)), zeros: bound 0;  sam_window_merge  a gather: bound 0
+  vae_sample     0.5 lv and the clamp exact; expf at 1 ulp (2 w |v|), the accuracy the HIP documentation's table of math
+                 functions publishes for expf — the published figure, not measured here: the GPU suite prints what the row with
+                 every finite fp16 log-variance observes, for information; then scale (mean + sd noise) through V
+  sam_relpos_qkv q, k, v at valid positions and the one-hot and zero columns: bound 0; at padded positions fp16 of the fp32 bias:
+                 u |b| + 2^-25; a rel column: a sequential fp32 fma chain of d terms, e = d w sum |q R|, times fl(1 / scale)
+                 carried as V(1 / scale, w / scale), then R16
 Nothing above is fitted to kernel output."""
 import functools
 import math
@@ -736,7 +751,481 @@ class ScaleRows:
         return {"out": (d["x"] * d["table"][1, row.col]).expand(row.reps, -1).contiguous()}
 
 
-ENTRIES = {"add": Elementwise("add"), "scale": Elementwise("scale"), "quick_gelu": Elementwise("quick_gelu"),
+# ---- one arithmetic for the reference (V) and the emulation (fp32 tensors) --------------------------
+def _as(mode):
+    return V if mode == "ref" else (lambda t: _t(t).to(F32))
+
+
+def _sel(b, x, y):
+    return V(torch.where(b, x.v, y.v), torch.where(b, x.e, y.e)) if isinstance(x, V) else torch.where(b, x, y)
+
+
+def _res(x):
+    return (x.v, x.e) if isinstance(x, V) else x
+
+
+def _get(x, idx):
+    return V(x.v[idx], x.e[idx]) if isinstance(x, V) else x[idx]
+
+
+def _put(x, idx, y):
+    if isinstance(x, V):
+        x.v[idx], x.e[idx] = y.v, y.e
+    else:
+        x[idx] = y
+
+
+def _ddim(m, x, vp, sa, sb, pa, pb):
+    """cfg_ddim_kernel's step on the combined prediction m (lgd_hip.h)"""
+    if vp:
+        x0, e = sa * x - sb * m, sa * m + sb * x
+    else:
+        e = m
+        x0 = (x - sb * e) / sa
+    return pa * x0 + pb * e
+
+
+# ---- PLMS ------------------------------------------------------------------------------------------
+PLMS_EVALS = 7                                           # six steps make seven evaluations
+
+
+@functools.lru_cache(maxsize=None)
+def plms_table(vpred):
+    from lgd_amd.scheduler import PNDMScheduler
+    s = PNDMScheduler(prediction_type="v_prediction" if vpred else "epsilon")
+    s.set_timesteps(PLMS_EVALS - 1)
+    t = s.plms_table(7.5, "cpu")
+    assert tuple(t.shape) == (PLMS_EVALS, 16)
+    return t
+
+
+class Plms:
+    """form: k the evaluation (row of plms_table), vpred, hist, inplace (x_out is x).  A ring slot whose weight is 0 holds
+    NaN, cur_sample holds NaN unless the row reads it.  Output `ets` is the pushed slot, `cur_sample` the saved sample."""
+    outputs = {"x_out": F32, "hist": F32, "ets": F32, "cur_sample": F32}
+
+    def data(self, row, ps, g):
+        B, C, HW = row.B, row.C, row.HW
+        tab = plms_table(row.vpred).clone()
+        c = tab[row.k]
+        ets = _randn(g, 3, B, C, HW, 1)
+        for s in range(3):
+            if float(c[1 + s]) == 0.0:
+                ets[s] = NAN
+        return {"eps": _randn(g, 2 * B, C, HW, 1), "x": _randn(g, B, C, HW, 1), "table": tab, "ets": ets,
+                "cur_sample": _randn(g, B, C, HW, 1) if float(c[8]) != 0.0 else torch.full((B, C, HW, 1), NAN),
+                "dyn": torch.tensor([row.k, 0, 0, 0], dtype=I32)}
+
+    def _math(self, row, d, mode, push_first=False, ignore_cur=False):
+        A, B = _as(mode), row.B
+        c = [float(v) for v in d["table"][row.k]]
+        eu, ec = A(d["eps"][:B]), A(d["eps"][B:])
+        m = eu + c[6] * (ec - eu)
+        push = int(c[7])
+        comb = c[0] * m
+        for s in range(3):
+            if c[1 + s] != 0.0:
+                comb = comb + c[1 + s] * (m if (push_first and s == push) else A(d["ets"][s]))
+        src = A(d["cur_sample"]) if (c[8] != 0.0 and not ignore_cur) else A(d["x"])
+        xn = c[4] * src + c[5] * comb
+        out = {"x_out": _res(xn), "hist": _res(xn)}
+        if push >= 0:
+            out["ets"] = _res(m)
+        if c[9] != 0.0:
+            out["cur_sample"] = (d["x"].to(F64), torch.zeros_like(d["x"], dtype=F64)) if mode == "ref" else d["x"].clone()
+        return out
+
+    def reference(self, row, d, **wrong):
+        return self._math(row, d, "ref", **wrong)
+
+    def emulate(self, row, d):
+        return self._math(row, d, "emu")
+
+
+# ---- MultiDiffusion, one view ------------------------------------------------------------------------
+MD_STEPS, MD_BOOT = 4, 2
+MASK_BELOW_HALF = 0.49999997                             # the fp32 value in front of 0.5
+
+
+def md_table(vpred):
+    i = torch.arange(MD_STEPS, dtype=F32)
+    return torch.stack([0.5 + 0.1 * i, 0.6 + 0.1 * i, 7.5 + 0 * i, (1.0 if vpred else 0.0) + 0 * i], 1).contiguous()
+
+
+def _md_coefs(A, tab, step):
+    c = tab[step]
+    a_t, a_p = A(c[0]), A(c[1])
+    return float(c[2]), float(c[3]) != 0.0, a_t.sqrt(), (1.0 - a_t).sqrt(), a_p.sqrt(), (1.0 - a_p).sqrt()
+
+
+def _pick(pick, n_boot):
+    return min(max(int(pick), 0), n_boot - 1)
+
+
+class MdStep:
+    """form: prep, step (dyn[0]; outside [0, MD_STEPS) nothing is written), vpred, hist.  Rows of eps and x_in the kernel has no
+    business reading (k >= P, the cond half of x_in) hold NaN; with P = 1 bg, noise and picks are left out (NULL)."""
+    outputs = {"x_in": F32, "latent": F32, "hist": F32}
+
+    def data(self, row, ps, g):
+        P, Pp, C, HW = row.P, row.Pp, row.C, row.HW
+        masks = torch.rand(P, HW, generator=g)
+        masks[:, 0], masks[:, 1] = 0.5, MASK_BELOW_HALF
+        d = {"table": md_table(row.vpred), "dyn": torch.tensor([row.step, 0, 0, 0], dtype=I32), "masks": masks,
+             "bg": None, "noise": None, "picks": None, "eps": None, "latent": None}
+        if P > 1:
+            d["bg"], d["noise"] = _randn(g, MD_BOOT, C, HW, 1), _randn(g, C, HW, 1)
+            picks = torch.randint(0, MD_BOOT, (MD_STEPS, P - 1), generator=g).to(I32)
+            picks[0, 0], picks[1, 0] = -3, MD_BOOT + 2       # clamped to 0 and to MD_BOOT - 1
+            d["picks"] = picks
+        x_in = torch.full((2 * Pp, C, HW, 1), NAN)
+        if row.prep:
+            d["latent"] = _randn(g, C, HW, 1)
+        else:
+            x_in[:P] = _randn(g, P, C, HW, 1)
+            eps = torch.full((2 * Pp, C, HW, 1), NAN)
+            eps[:P], eps[Pp:Pp + P] = _randn(g, P, C, HW, 1), _randn(g, P, C, HW, 1)
+            d["eps"] = eps
+        d["x_in"] = x_in
+        return d
+
+    def _math(self, row, d, mode, gt=False, picks_of_step=False, cond_at_P=False):
+        A = _as(mode)
+        P, Pp, C, HW, step = row.P, row.Pp, row.C, row.HW, row.step
+        if step < 0 or step >= MD_STEPS:
+            return {}
+        tab, mk = d["table"], d["masks"]
+        out = {}
+        if row.prep:
+            lat, nxt = A(d["latent"].reshape(C, HW)), step
+        else:
+            gs, vp, sa, sb, pa, pb = _md_coefs(A, tab, step)
+            eps, xin = d["eps"].reshape(2 * Pp, C, HW), d["x_in"].reshape(2 * Pp, C, HW)
+            lat = None
+            for k in range(P):
+                eu, ec = A(eps[k]), A(eps[(P if cond_at_P else Pp) + k])
+                t = A(mk[k].view(1, HW)) * _ddim(eu + gs * (ec - eu), A(xin[k]), vp, sa, sb, pa, pb)
+                lat = t if k == 0 else lat + t
+            out["latent"] = out["hist"] = _res(lat)
+            nxt = step + 1
+        if nxt >= MD_STEPS:
+            return out
+        boot = nxt < MD_BOOT and P > 1
+        rows = []
+        for k in range(Pp):
+            x = lat
+            if boot and 1 <= k < P:
+                pk = _pick(d["picks"][step if (picks_of_step and not row.prep) else nxt][k - 1], MD_BOOT)
+                a_n = A(tab[nxt][0])
+                noisy = a_n.sqrt() * A(d["bg"][pk].reshape(C, HW)) + (1.0 - a_n).sqrt() * A(d["noise"].reshape(C, HW))
+                b = ((mk[k] > 0.5) if gt else (mk[k] >= 0.5)).view(1, HW).expand(C, HW)
+                x = _sel(b, lat, noisy)                  # acc b + noisy (1 - b) with b in {0, 1}: exact
+            rows.append(x)
+        if mode == "ref":
+            v, e = torch.stack([r.v for r in rows]), torch.stack([r.e for r in rows])
+            out["x_in"] = (torch.cat([v, v]), torch.cat([e, e]))
+        else:
+            out["x_in"] = torch.cat([torch.stack(rows)] * 2)
+        return out
+
+    def reference(self, row, d, **wrong):
+        return self._math(row, d, "ref", **wrong)
+
+    def emulate(self, row, d):
+        return self._math(row, d, "emu")
+
+
+# ---- MultiDiffusion over views -----------------------------------------------------------------------
+def md_views(Hp, Wp):
+    """nbh, nbw, V of get_views (lgd_hip.h): 64 x 64 windows at stride 8"""
+    nbh, nbw = (Hp - 64) // 8 + 1, (Wp - 64) // 8 + 1
+    return nbh, nbw, nbh * nbw
+
+
+def md_chunks(V_, nvc):
+    return [(v0, min(nvc, V_ - v0)) for v0 in range(0, V_, nvc)]
+
+
+class MdViews:
+    """form: prep, step, nvc (views per UNet call), indep, norm, vpred, hist, nullvc (value = count = NULL).  A row is the
+    launches of ALL chunks of one step, in order.  The data of a row does not depend on nvc: different chunkings see the same
+    panorama.  eps / x_in hold one buffer [2 nvc Pp][C][64 x 64] per chunk; rows nobody may read hold NaN.  With several
+    chunks value and count come in as NaN (the chunk with v0 == 0 starts from zero) and go out as the sums behind the last
+    non-final chunk (the final chunk stores neither)."""
+    outputs = {"x_in": F32, "latent": F32, "hist": F32, "value": F32, "count": F32}
+
+    def key(self, row):
+        return row.name.replace(f"nvc={row.nvc},", "")
+
+    def data(self, row, ps, g):
+        C, Hp, Wp, P, Pp, nvc = row.C, row.Hp, row.Wp, row.P, row.Pp, row.nvc
+        g = torch.Generator().manual_seed(9000 + sum(map(ord, self.key(row))) % 1000)
+        _, _, V_ = md_views(Hp, Wp)
+        chunks = md_chunks(V_, nvc)
+        masks = torch.rand(P, Hp, Wp, generator=g)
+        masks[:, 10, 8:12] = 0.0                             # a covered element whose mask sum is exactly 0
+        masks[:, 20, 8], masks[:, 20, 9] = 0.5, MASK_BELOW_HALF
+        d = {"table": md_table(row.vpred), "dyn": torch.tensor([row.step, 0, 0, 0], dtype=I32), "masks": masks}
+        for n in ("bg", "noise", "picks", "eps", "latent", "value", "count", "x_in"):
+            d[n] = None
+        if row.prep:
+            d["latent"] = _randn(g, C, Hp, Wp)
+            if P > 1:
+                d["bg"], d["noise"] = _randn(g, MD_BOOT, C, 64, 64), _randn(g, C, Hp, Wp)
+                picks = torch.randint(0, MD_BOOT, (MD_STEPS, V_, P - 1), generator=g).to(I32)
+                picks[0, 0, 0], picks[0, V_ - 1, P - 2] = -3, MD_BOOT + 2
+                d["picks"] = picks
+            return d
+        eps_l, xin_l = torch.full((V_, 2, Pp, C, 64, 64), NAN), torch.full((V_, Pp, C, 64, 64), NAN)
+        eps_l[:, :, :P], xin_l[:, :P] = _randn(g, V_, 2, P, C, 64, 64), _randn(g, V_, P, C, 64, 64)
+        eps = torch.full((len(chunks), 2 * nvc * Pp, C, 64, 64), NAN)
+        x_in = torch.full((len(chunks), 2 * nvc * Pp, C, 64, 64), NAN)
+        for ci, (v0, nv) in enumerate(chunks):
+            for j in range(nv):
+                eps[ci, j * Pp:(j + 1) * Pp] = eps_l[v0 + j, 0]
+                eps[ci, (nvc + j) * Pp:(nvc + j + 1) * Pp] = eps_l[v0 + j, 1]
+                x_in[ci, j * Pp:(j + 1) * Pp] = xin_l[v0 + j]
+        d.update(eps=eps, x_in=x_in, eps_l=eps_l, xin_l=xin_l)
+        if len(chunks) > 1:
+            d["value"], d["count"] = torch.full((C, Hp, Wp), NAN), torch.full((C, Hp, Wp), NAN)
+        return d
+
+    def _math(self, row, d, mode, eu_k=False, div0=False, swap_origin=False, reread=False):
+        A = _as(mode)
+        C, Hp, Wp, P, Pp, step = row.C, row.Hp, row.Wp, row.P, row.Pp, row.step
+        _, nbw, V_ = md_views(Hp, Wp)
+        chunks = md_chunks(V_, row.nvc)
+        tab, mk = d["table"], d["masks"]
+        origin = (lambda v: ((v % nbw) * 8, (v // nbw) * 8)) if swap_origin else (lambda v: ((v // nbw) * 8, (v % nbw) * 8))
+        if row.prep:
+            boot = step < MD_BOOT and P > 1
+            views = []
+            for v in range(V_):
+                hs, ws = origin(v)
+                win = (slice(None), slice(hs, hs + 64), slice(ws, ws + 64))
+                lat, rows = A(d["latent"][win]), []
+                for k in range(Pp):
+                    x = lat
+                    if boot and 1 <= k < P:
+                        pk = _pick(d["picks"][step][v][k - 1], MD_BOOT)
+                        a_n = A(tab[step][0])
+                        noisy = a_n.sqrt() * A(d["bg"][pk]) + (1.0 - a_n).sqrt() * A(d["noise"][win])
+                        x = _sel((mk[k][win[1:]] >= 0.5).expand(C, 64, 64), lat, noisy)
+                    rows.append(x)
+                views.append(rows)
+            if mode == "ref":
+                v_ = torch.stack([torch.stack([r.v for r in rows]) for rows in views])
+                e_ = torch.stack([torch.stack([r.e for r in rows]) for rows in views])
+                return {"x_in": (torch.stack([v_, v_], 1), torch.stack([e_, e_], 1))}     # [V][half][Pp][C][64][64]
+            x = torch.stack([torch.stack(rows) for rows in views])
+            return {"x_in": torch.stack([x, x], 1)}
+        gs, vp, sa, sb, pa, pb = _md_coefs(A, tab, step)
+        zero = torch.zeros(C, Hp, Wp, dtype=F64, device=mk.device)
+        val, cnt = A(zero.clone()), A(zero.clone())
+        if reread:
+            val = A(d["value"].clone())
+        snap = None
+        for v in range(V_):
+            hs, ws = origin(v)
+            win = (slice(None), slice(hs, min(hs + 64, Hp)), slice(ws, min(ws + 64, Wp)))
+            h_, w_ = win[1].stop - hs, win[2].stop - ws
+            eu0 = A(d["eps_l"][v, 0, 0])
+            vs = cs = None
+            for k in range(P):
+                eu, ec = A(d["eps_l"][v, 0, k]), A(d["eps_l"][v, 1, k])
+                m = (eu + gs * (ec - eu)) if row.indep else (gs * (ec - eu) + (eu if eu_k else eu0))
+                dd = _get(_ddim(m, A(d["xin_l"][v, k]), vp, sa, sb, pa, pb), (slice(None), slice(0, h_), slice(0, w_)))
+                mw = A(mk[k][win[1:]].expand(C, h_, w_))
+                vs, cs = (mw * dd, mw) if k == 0 else (vs + mw * dd, cs + mw)
+            _put(val, win, _get(val, win) + vs)
+            _put(cnt, win, _get(cnt, win) + cs)
+            if len(chunks) > 1 and v == chunks[-1][0] - 1:   # behind the last non-final chunk
+                snap = tuple(V(s.v.clone(), s.e.clone()) if mode == "ref" else s.clone() for s in (val, cnt))
+        if row.norm:
+            cv = cnt.v if mode == "ref" else cnt
+            pos = torch.ones_like(cv, dtype=torch.bool) if div0 else cv > 0
+            val = _sel(pos, val / _sel(pos, cnt, A(torch.ones_like(zero))), val)
+        out = {"latent": _res(val), "hist": _res(val)}
+        if snap is not None:
+            out["value"] = _res(snap[0])
+            if row.norm:
+                out["count"] = _res(snap[1])
+        return out
+
+    def reference(self, row, d, **wrong):
+        return self._math(row, d, "ref", **wrong)
+
+    def emulate(self, row, d):
+        return self._math(row, d, "emu")
+
+
+# ---- uint8 images, the VAE posterior sample ------------------------------------------------------------
+def u8_table():
+    u = torch.arange(256, dtype=F32)
+    return 2.0 * (u / 255.0) - 1.0                           # the table of lgd_hip.h: fp32, true division
+
+
+class ImageU8:
+    outputs = {"y": H16}
+
+    def data(self, row, ps, g):
+        n = row.B * row.HW * 3
+        img = torch.randint(0, 256, (n,), generator=g).to(torch.uint8)
+        if n >= 256:
+            img[:256] = torch.arange(256).to(torch.uint8)   # every byte value
+        return {"img": img.reshape(row.B, row.HW, 3)}
+
+    def reference(self, row, d, reverse=False, wrong_word=False):
+        img = d["img"].reshape(-1, 12).clone()
+        if wrong_word:                                       # byte 4 of a quad (word 1) taken from word 0
+            img[:, 4] = img[:, 0]
+        x = u8_table().to(img.device)[img.reshape(-1, 3).long()]
+        if reverse:
+            x = x.flip(-1)
+        hi = x.to(H16)
+        y = torch.zeros(x.shape[0], 8, dtype=F64, device=x.device)
+        y[:, :3], y[:, 3:6] = hi.to(F64), (x - hi.to(F32)).to(H16).to(F64)
+        return {"y": (y, torch.zeros_like(y))}
+
+    def emulate(self, row, d):
+        return {"y": self.reference(row, d)["y"][0].to(H16)}
+
+
+def all_finite_f16():
+    """every finite fp16 value once: 63 488 of them"""
+    return torch.cat([torch.arange(0, 0x7C00), torch.arange(0x8000, 0xFC00) - 0x10000]).to(torch.int16).view(H16)
+
+
+class VaeSample:
+    """form: scale, sweep (the log-variances are every finite fp16 value once; mean 0 and noise 1, so that out is expf itself)"""
+    outputs = {"out": F32}
+
+    def data(self, row, ps, g):
+        B, z, HW = row.B, row.z, row.HW
+        mom = _randn(g, B * HW, 2 * z, dtype=H16)
+        mom[:, z:] = (4.0 * torch.randn(B * HW, z, generator=g)).to(H16)
+        noise = _randn(g, B, z, HW, 1)
+        if row.sweep:
+            assert B * HW * z == 63488
+            mom[:, :z], noise = 0.0, torch.ones(B, z, HW, 1)
+            mom[:, z:] = all_finite_f16()[torch.randperm(63488, generator=g)].reshape(B * HW, z)
+        else:
+            mom[0, z:z + 4] = torch.tensor([-30.0, -30.02, 20.0, 20.02], dtype=H16)      # both clamp edges
+        return {"moments": mom, "noise": noise}
+
+    def _math(self, row, d, mode, no_clamp=False, swap=False):
+        B, z, HW = row.B, row.z, row.HW
+        mom = d["moments"].reshape(B, HW, 2 * z).transpose(1, 2)       # [B][2z][HW]
+        mean, lv = (mom[:, z:], mom[:, :z]) if swap else (mom[:, :z], mom[:, z:])
+        h = 0.5 * (lv.to(F64) if no_clamp else lv.to(F64).clamp(-30.0, 20.0))   # exact in fp32
+        nz = d["noise"].reshape(B, z, HW)
+        if mode == "ref":
+            sd = h.exp()
+            y = f32(row.scale) * (V(mean) + V(sd, 2 * W * sd) * V(nz))           # expf: 1 ulp
+            return {"out": (y.v, y.e)}
+        return {"out": torch.tensor(row.scale, dtype=F32) * (mean.to(F32) + torch.exp(h.to(F32)) * nz)}
+
+    def reference(self, row, d, **wrong):
+        return self._math(row, d, "ref", **wrong)
+
+    def emulate(self, row, d):
+        return self._math(row, d, "emu")
+
+
+# ---- SAM: window partition with the relative-position columns, window merge ---------------------------------
+def sam_geometry(row, dev=None):
+    """S, and per row of the window order: the raster token it gathers (clamped), valid, iy, ix"""
+    B, Hs, Ws = row.B, row.Hs, row.Ws
+    S = row.window or Hs
+    nwy, nwx = -(-Hs // S), -(-Ws // S)
+    wt = torch.arange(B * nwy * nwx * S * S, device=dev)
+    ix, iy, win = wt % S, (wt // S) % S, wt // (S * S)
+    wx, wy, b = win % nwx, (win // nwx) % nwy, win // (nwx * nwy)
+    y, x = wy * S + iy, wx * S + ix
+    valid = (y < Hs) & (x < Ws)
+    tok = (b * Hs + y.clamp_max(Hs - 1)) * Ws + x.clamp_max(Ws - 1)
+    return S, tok, valid, iy, ix
+
+
+def sam_scale(row):
+    return f32(row.d ** -0.5)
+
+
+class SamRelpos:
+    outputs = {"qa": H16, "ka": H16, "va": H16}
+
+    def data(self, row, ps, g):
+        S, C = row.window or row.Hs, row.NH * row.d
+        return {"qkv": _randn(g, row.B * row.Hs * row.Ws, 3 * C, dtype=H16), "qkv_bias": _randn(g, 3 * C),
+                "rel_h": 0.5 * _randn(g, 2 * S - 1, row.d), "rel_w": 0.5 * _randn(g, 2 * S - 1, row.d)}
+
+    def reference(self, row, d, flip=False, w_with_iy=False, zero_pad=False, emu=False):
+        NH, dd, DA = row.NH, row.d, row.DA
+        dev = d["qkv"].device
+        S, tok, valid, iy, ix = sam_geometry(row, dev)
+        R, C = tok.numel(), NH * dd
+        dt = F32 if emu else F64
+        bias = d["qkv_bias"].to(dt) * (0.0 if zero_pad else 1.0)
+        src = torch.where(valid.view(R, 1), d["qkv"][tok].to(dt), bias.view(1, 3 * C).expand(R, 3 * C))   # what the kernel reads
+        q = src[:, :C].reshape(R, NH, dd)
+        j = torch.arange(S, device=dev)
+        sgn = -1 if flip else 1
+        ih = (sgn * (iy.view(R, 1) - j) + S - 1).clamp(0, 2 * S - 2)
+        iw = (sgn * ((iy if w_with_iy else ix).view(R, 1) - j) + S - 1).clamp(0, 2 * S - 2)
+        tabs = torch.cat([d["rel_h"].to(dt)[ih], d["rel_w"].to(dt)[iw]], 1)          # [R][2S][d]
+        prod = q.view(R, NH, 1, dd) * tabs.view(R, 1, 2 * S, dd)
+        sc = sam_scale(row)
+        ref = torch.zeros(3, R, NH, DA, dtype=dt, device=dev)
+        bnd = torch.zeros(3, R, NH, DA, dtype=F64, device=dev)
+        ref[:, :, :, :dd] = src.reshape(R, 3, NH, dd).transpose(0, 1)
+        bnd[:, :, :, :dd] = (~valid).view(1, R, 1, 1) * (U * ref[:, :, :, :dd].abs().to(F64) + 2.0 ** -25)   # fp16(fp32 bias)
+        if emu:
+            acc = torch.zeros(R, NH, 2 * S, dtype=F32)
+            for c in range(dd):
+                acc = acc + prod[..., c]
+            ref[0, :, :, dd:dd + 2 * S] = acc * (torch.tensor(1.0, dtype=F32) / torch.tensor(sc, dtype=F32))
+        else:
+            rel = V(prod.sum(-1), dd * W * prod.abs().sum(-1)) * V(1.0 / sc, W / sc)
+            ref[0, :, :, dd:dd + 2 * S], bnd[0, :, :, dd:dd + 2 * S] = rel.v, r16(rel)
+        ref[1, :, :, dd:dd + S] = (j.view(1, S) == iy.view(R, 1)).to(dt).view(R, 1, S)
+        ref[1, :, :, dd + S:dd + 2 * S] = (j.view(1, S) == ix.view(R, 1)).to(dt).view(R, 1, S)
+        if emu:
+            return {n: ref[i].to(H16) for i, n in enumerate(("qa", "ka", "va"))}
+        return {n: (ref[i], bnd[i]) for i, n in enumerate(("qa", "ka", "va"))}
+
+    def emulate(self, row, d):
+        return self.reference(row, d, emu=True)
+
+
+class SamMerge:
+    outputs = {"out": H16}
+
+    def data(self, row, ps, g):
+        _, _, valid, _, _ = sam_geometry(row)
+        oa = _randn(g, valid.numel(), row.NH, row.DA, dtype=H16)
+        oa[~valid] = NAN                                     # padded rows and the extra columns: a wrong gather shows
+        oa[:, :, row.d:] = NAN
+        return {"oa": oa.reshape(valid.numel(), row.NH * row.DA)}
+
+    def reference(self, row, d, swap=False):
+        B, Hs, Ws, NH, dd, DA = row.B, row.Hs, row.Ws, row.NH, row.d, row.DA
+        S = row.window or Hs
+        nwy, nwx = -(-Hs // S), -(-Ws // S)
+        if swap:
+            nwy, nwx = nwx, nwy
+        t = torch.arange(B * Hs * Ws, device=d["oa"].device)
+        x, y, b = t % Ws, (t // Ws) % Hs, t // (Ws * Hs)
+        wt = ((((b * nwy + y // S) * nwx + x // S) * S + y % S) * S + x % S).clamp_max(d["oa"].shape[0] - 1)
+        v = d["oa"].reshape(-1, NH, DA)[wt][:, :, :dd].reshape(-1, NH * dd).to(F64)
+        return {"out": (v, torch.zeros_like(v))}
+
+    def emulate(self, row, d):
+        return {"out": self.reference(row, d)["out"][0].to(H16)}
+
+
+ENTRIES = {"cfg_plms": Plms(), "md_step": MdStep(), "md_views": MdViews(), "image_u8": ImageU8(), "vae_sample": VaeSample(),
+           "sam_relpos_qkv": SamRelpos(), "sam_window_merge": SamMerge(),
+           "add": Elementwise("add"), "scale": Elementwise("scale"), "quick_gelu": Elementwise("quick_gelu"),
            "act_gelu": Elementwise("gelu"), "act_relu": Elementwise("relu"), "geglu_fwd": Geglu(False), "geglu_bwd": Geglu(True),
            "upsample2x_bwd": Upsample(), "softmax_rows": Softmax(), "nchw_to_nhwc8": Nhwc8(), "conv_out": ConvOut(),
            "conv_in": ConvIn(), "cfg_ddim": Step(False), "cfg_multistep": Step(True), "axpy": Axpy(), "scale_rows": ScaleRows(),
@@ -786,6 +1275,55 @@ for _e in ("cfg_ddim", "cfg_multistep"):
 _ROW_LIST += [Row("axpy", {}, dict(active=a, col=c)) for a in (0, 1) for c in range(4)]
 _ROW_LIST += [Row("scale_rows", dict(n=7, row_stride=5), dict(reps=r, col=3)) for r in (1, 2)]
 _ROW_LIST += [Row("select_row", dict(n=n)) for n in (1, 300)]
+# PLMS: one evaluation kind per k (0 saves and pushes, 1 restarts from the saved sample, 2 and 3 the second and third order, 4 and
+# 5 the fourth order on two ring slots); 2 x 4 x 512 x 513 / 4 = 525 312 vectors > 2048 x 256: the grid-stride loop iterates
+N_PLMS_STRIDE = 512 * 513
+_ROW_LIST += [Row("cfg_plms", dict(B=1, C=1, HW=4), dict(k=k, vpred=0, hist=1, inplace=0)) for k in range(6)]
+_ROW_LIST += [Row("cfg_plms", dict(B=2, C=4, HW=16), dict(k=k, vpred=v, hist=h, inplace=ip))
+              for k in range(6) for v in (0, 1) for h in (0, 1) for ip in (0, 1)]
+_ROW_LIST += [Row("cfg_plms", dict(B=2, C=4, HW=N_PLMS_STRIDE), dict(k=4, vpred=0, hist=0, inplace=1))]
+# MultiDiffusion step: the two prep forms (a bootstrapped and an unbootstrapped step), then step 0 (the next one bootstrapped),
+# 1 (the first unbootstrapped input), 3 (the last: x_in keeps every bit), -1 and 4 (nothing is written); HW = 260 is 65 vectors
+_MD_FORMS = [dict(prep=1, step=s, vpred=0, hist=0) for s in (0, 2)] + \
+            [dict(prep=0, step=s, vpred=v, hist=h) for s in (0, 1, 3, -1, 4) for v in (0, 1) for h in (0, 1)]
+_ROW_LIST += [Row("md_step", dict(P=P_, Pp=Pp, C=C, HW=HW), f)
+              for P_, Pp, C, HW in ((1, 1, 1, 4), (2, 2, 4, 16), (3, 4, 4, 16), (2, 2, 1, 260)) for f in _MD_FORMS]
+
+
+def _vrow(C, Hp, Wp, P_, Pp, **form):
+    return Row("md_views", dict(C=C, Hp=Hp, Wp=Wp, P=P_, Pp=Pp), form)
+
+
+# views: on the 72 x 72 panorama (V = 4) every chunking (one chunk; two of 2; 3 and a short last one) with every
+# (normalization, indep_uncond); the prompts and the prediction hang on that pair, so that the chunkings of one pair share data
+_VIEW_PAIRS = {(0, 0): (2, 2, 0), (0, 1): (3, 4, 1), (1, 0): (1, 1, 1), (1, 1): (3, 4, 0)}
+for _nvc in (4, 2, 3):
+    for (_norm, _indep), (_P, _Pp, _vp) in _VIEW_PAIRS.items():
+        _ROW_LIST.append(_vrow(2, 72, 72, _P, _Pp, prep=0, step=1, nvc=_nvc, indep=_indep, norm=_norm, vpred=_vp, hist=1, nullvc=0))
+    _ROW_LIST += [_vrow(2, 72, 72, 3, 4, prep=1, step=s, nvc=_nvc, indep=1, norm=0, vpred=0, hist=0, nullvc=0) for s in (0, 2)]
+_ROW_LIST += [
+    _vrow(1, 72, 72, 1, 1, prep=1, step=0, nvc=4, indep=1, norm=0, vpred=0, hist=0, nullvc=0),
+    _vrow(1, 72, 72, 2, 2, prep=1, step=0, nvc=2, indep=1, norm=0, vpred=0, hist=0, nullvc=0),
+    _vrow(1, 64, 64, 2, 2, prep=0, step=1, nvc=1, indep=1, norm=1, vpred=0, hist=1, nullvc=1),       # V = 1
+    _vrow(1, 64, 64, 2, 2, prep=1, step=0, nvc=1, indep=1, norm=0, vpred=0, hist=0, nullvc=0),
+    _vrow(2, 64, 72, 2, 2, prep=0, step=0, nvc=2, indep=0, norm=0, vpred=1, hist=1, nullvc=0),       # V = 2 in one chunk
+    _vrow(2, 64, 72, 2, 2, prep=0, step=0, nvc=1, indep=0, norm=0, vpred=1, hist=1, nullvc=0),       # and in two
+    _vrow(2, 64, 72, 2, 2, prep=1, step=0, nvc=1, indep=1, norm=0, vpred=0, hist=0, nullvc=0),
+    _vrow(1, 68, 64, 3, 4, prep=0, step=3, nvc=1, indep=1, norm=1, vpred=0, hist=0, nullvc=0),       # rows 64 .. 67 uncovered
+    _vrow(1, 68, 64, 2, 2, prep=1, step=0, nvc=1, indep=1, norm=0, vpred=0, hist=0, nullvc=0),
+    _vrow(1, 64, 68, 2, 2, prep=0, step=1, nvc=1, indep=0, norm=1, vpred=1, hist=1, nullvc=1),       # columns 64 .. 67 uncovered
+    _vrow(1, 64, 68, 2, 2, prep=1, step=1, nvc=1, indep=1, norm=0, vpred=0, hist=0, nullvc=0)]
+_ROW_LIST += [Row("image_u8", dict(B=1, HW=4)), Row("image_u8", dict(B=2, HW=2 * 257)), Row("image_u8", dict(B=1, HW=4 * (GRID_VECS + 3)))]
+_ROW_LIST += [Row("vae_sample", dict(B=1, z=4, HW=4), dict(scale=0.18215, sweep=0)),
+              Row("vae_sample", dict(B=2, z=8, HW=20), dict(scale=0.18215, sweep=0)), Row("vae_sample", dict(B=2, z=8, HW=20), dict(scale=1.0, sweep=0)),
+              Row("vae_sample", dict(B=1, z=4, HW=15872), dict(scale=1.0, sweep=1)),
+              Row("vae_sample", dict(B=1, z=4, HW=4 * (GRID_VECS + 3)), dict(scale=0.18215, sweep=0))]
+# SAM: the smallest global grid; a 5 x 7 grid in 2 x 3 windows of 3, padded both ways, with tail columns; a window larger than
+# the grid; exact division; NH d = 320, NH 2S = 280 and NH DA = 640 > 256: each of the three thread loops iterates
+_SAM_SHAPES = [dict(B=1, Hs=2, Ws=2, window=0, NH=1, d=8, DA=16), dict(B=2, Hs=5, Ws=7, window=3, NH=2, d=8, DA=16),
+               dict(B=1, Hs=3, Ws=2, window=4, NH=1, d=8, DA=16), dict(B=1, Hs=4, Ws=4, window=2, NH=2, d=16, DA=24),
+               dict(B=1, Hs=14, Ws=14, window=0, NH=10, d=32, DA=64)]
+_ROW_LIST += [Row(e, s) for e in ("sam_relpos_qkv", "sam_window_merge") for s in _SAM_SHAPES]
 ROWS_BY_NAME = {r.name: r for r in _ROW_LIST}
 assert len(ROWS_BY_NAME) == len(_ROW_LIST)
 
@@ -795,7 +1333,8 @@ def rows_of(entry):
 
 
 def grid_stride_rows():
-    return [r for r in _ROW_LIST if r.shape.get("n") == N_STRIDE or r.shape.get("rows") == 4100 or r.shape.get("L") == 257]
+    return [r for r in _ROW_LIST if r.shape.get("n") == N_STRIDE or r.shape.get("rows") == 4100 or r.shape.get("L") == 257
+            or r.shape.get("HW") in (N_PLMS_STRIDE, 4 * (GRID_VECS + 3))]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -830,6 +1369,23 @@ MUTATIONS = {
     "cfg_ddim: the mask of the other image": (_row("cfg_ddim", L=4, vpred=0, blend="on", hist=1, inplace=0), "x_out", "plain", _ref_of(other_mask=True)),
     "cfg_multistep: a stale x0_prev": (_row("cfg_multistep", L=4, vpred=0, blend="on", hist=1, inplace=0, second=1), "x0_prev", "plain", _ref_of(stale=True)),
     "axpy: active ignored": (_row("axpy", active=1, col=0), "x", "plain", _ref_of(ignore_active=True)),
+    "plms: the ring slot pushed before it is read": (_row("cfg_plms", HW=16, k=4, vpred=0, hist=1, inplace=0), "x_out", "plain", _ref_of(push_first=True)),
+    "plms: from_cur ignored": (_row("cfg_plms", HW=16, k=1, vpred=0, hist=1, inplace=0), "x_out", "plain", _ref_of(ignore_cur=True)),
+    "md_step: > for >= at a mask of 0.5": (_row("md_step", P=2, HW=16, prep=1, step=0), "x_in", "plain", _ref_of(gt=True)),
+    "md_step: the picks row of step i": (_row("md_step", P=2, HW=16, prep=0, step=0, vpred=0, hist=1), "x_in", "plain", _ref_of(picks_of_step=True)),
+    "md_step: the cond half at row offset P": (_row("md_step", P=3, Pp=4, prep=0, step=1, vpred=0, hist=1), "latent", "plain", _ref_of(cond_at_P=True)),
+    "views: the shared uncond taken from eu_k": (_row("md_views", Hp=64, Wp=72, prep=0, nvc=2), "latent", "plain", _ref_of(eu_k=True)),
+    "views: division where count == 0": (_row("md_views", Hp=72, prep=0, nvc=4, norm=1, indep=1), "latent", "plain", _ref_of(div0=True)),
+    "views: the view origin swapped": (_row("md_views", Hp=64, Wp=72, prep=0, nvc=2), "latent", "plain", _ref_of(swap_origin=True)),
+    "views: value re-read in the chunk with v0 == 0": (_row("md_views", Hp=72, prep=0, nvc=2, norm=0, indep=1), "latent", "plain", _ref_of(reread=True)),
+    "relpos: the sign of the rel index flipped": (_row("sam_relpos_qkv", Hs=5), "qa", "plain", _ref_of(flip=True)),
+    "relpos: rel_w indexed with iy": (_row("sam_relpos_qkv", Hs=5), "qa", "plain", _ref_of(w_with_iy=True)),
+    "relpos: zero instead of the bias at padded positions": (_row("sam_relpos_qkv", Hs=5), "va", "plain", _ref_of(zero_pad=True)),
+    "window_merge: nwx and nwy swapped": (_row("sam_window_merge", Hs=5), "out", "plain", _ref_of(swap=True)),
+    "vae: the clamp missing": (_row("vae_sample", sweep=1), "out", "plain", _ref_of(no_clamp=True)),
+    "vae: mean and log-variance halves swapped": (_row("vae_sample", HW=20, scale=1.0), "out", "plain", _ref_of(swap=True)),
+    "image_u8: channel order reversed": (_row("image_u8", HW=514), "y", "plain", _ref_of(reverse=True)),
+    "image_u8: the straddling byte from the wrong word": (_row("image_u8", HW=514), "y", "plain", _ref_of(wrong_word=True)),
 }
 
 
@@ -855,6 +1411,14 @@ ARGS = {
     "lgd_axpy_f32": "p:g p:x p:coef_table p:step_idx col p:active per_sample n stream",
     "lgd_select_row_f32": "p:table p:idx p:out n stream",
     "lgd_scale_rows_f32": "p:x p:out p:table p:dyn row_stride col n reps stream",
+    "lgd_cfg_plms_step_f32": "p:eps p:x p:x_out p:ets p:cur_sample p:coef_table p:dyn p:hist B C HW stream",
+    "lgd_multidiffusion_step_f32": "p:eps p:x_in p:latent p:masks p:bg p:noise p:picks p:coef_table p:dyn p:hist P Pp C HW n_steps n_boot prep stream",
+    "lgd_multidiffusion_views_f32": "p:eps p:x_in p:latent p:value p:count p:masks p:bg p:noise p:picks p:coef_table p:dyn p:hist "
+                                    "P Pp C Hp Wp V v0 nv nvc n_steps n_boot indep_uncond normalization prep stream",
+    "lgd_image_u8_to_nhwc8_f16": "p:img p:table p:y B HW stream",
+    "lgd_vae_sample_f32": "p:moments p:noise p:out B z HW scale stream",
+    "lgd_sam_relpos_qkv_f16": "p:qkv p:qkv_bias p:rel_h p:rel_w B Hs Ws window NH d DA scale p:qa p:ka p:va stream",
+    "lgd_sam_window_merge_f16": "p:oa p:out B Hs Ws window NH d DA stream",
 }
 BASE = {
     "lgd_add_f16": dict(n=64), "lgd_scale_f16": dict(alpha=0.5, n=64), "lgd_quick_gelu_f16": dict(n=64),
@@ -864,6 +1428,14 @@ BASE = {
     "lgd_conv_in_f16": dict(B=2, Cin=4, L=5, Cout=64), "lgd_cfg_ddim_step_f32": dict(B=2, C=4, HW=16),
     "lgd_cfg_multistep_step_f32": dict(B=2, C=4, HW=16), "lgd_axpy_f32": dict(col=1, per_sample=20, n=60),
     "lgd_select_row_f32": dict(n=300), "lgd_scale_rows_f32": dict(row_stride=5, col=3, n=7, reps=2),
+    "lgd_cfg_plms_step_f32": dict(B=2, C=4, HW=16),
+    "lgd_multidiffusion_step_f32": dict(P=2, Pp=2, C=4, HW=16, n_steps=4, n_boot=2, prep=0),
+    # the first of two chunks of an accumulate call with normalization: eps, value and count are all needed
+    "lgd_multidiffusion_views_f32": dict(P=2, Pp=2, C=1, Hp=72, Wp=72, V=4, v0=0, nv=2, nvc=2, n_steps=4, n_boot=2, indep_uncond=1,
+                                         normalization=1, prep=0),
+    "lgd_image_u8_to_nhwc8_f16": dict(B=2, HW=50), "lgd_vae_sample_f32": dict(B=2, z=4, HW=20, scale=0.18215),
+    "lgd_sam_relpos_qkv_f16": dict(B=2, Hs=5, Ws=7, window=3, NH=2, d=8, DA=16, scale=8 ** -0.5),
+    "lgd_sam_window_merge_f16": dict(B=2, Hs=5, Ws=7, window=3, NH=2, d=8, DA=16),
 }
 _V16 = dict.fromkeys("a b y x h gy gh gx".split(), 16)
 ALIGN = {fn: {n[2:]: _V16.get(n[2:], 4) for n in a.split() if n.startswith("p:")} for fn, a in ARGS.items()}
@@ -874,9 +1446,31 @@ ALIGN["lgd_axpy_f32"].update(x=4)
 ALIGN["lgd_scale_rows_f32"].update(x=4)
 ALIGN["lgd_cfg_ddim_step_f32"].update(x=4)
 ALIGN["lgd_cfg_multistep_step_f32"].update(x=4)
+_V16F = dict.fromkeys("eps x x_in x_out ets cur_sample latent value count masks bg noise hist".split(), 16)   # fp32 in vectors of 4
+ALIGN["lgd_cfg_plms_step_f32"].update({k: v for k, v in _V16F.items() if k in ALIGN["lgd_cfg_plms_step_f32"]})
+ALIGN["lgd_multidiffusion_step_f32"].update({k: v for k, v in _V16F.items() if k in ALIGN["lgd_multidiffusion_step_f32"]})
+ALIGN["lgd_multidiffusion_views_f32"].update({k: v for k, v in _V16F.items() if k in ALIGN["lgd_multidiffusion_views_f32"]})
+ALIGN["lgd_vae_sample_f32"].update(moments=8, noise=16, out=16)
+ALIGN["lgd_sam_relpos_qkv_f16"].update(qkv=2, qa=2, ka=2, va=2)      # scalar accesses
+ALIGN["lgd_sam_window_merge_f16"].update(oa=16, out=16)
 OPTIONAL = {"bias", "frozen_ref", "mask", "hist", "active"}
+# the entry points whose operand names mean something else elsewhere (noise, eps) say themselves what may be NULL in their BASE
+OPTIONAL_OF = {"lgd_cfg_plms_step_f32": {"hist"}, "lgd_multidiffusion_step_f32": {"hist"},
+               "lgd_multidiffusion_views_f32": {"bg", "noise", "picks", "hist"}, "lgd_image_u8_to_nhwc8_f16": set(),
+               "lgd_vae_sample_f32": set(), "lgd_sam_relpos_qkv_f16": set(), "lgd_sam_window_merge_f16": set()}
+
+
+def optional(fn):
+    return OPTIONAL_OF.get(fn, OPTIONAL)
+
+
 COUNTS = {fn: [n for n in a.split() if n in ("n", "rows", "B", "H", "W", "L", "HW", "C", "Cin", "reps")] for fn, a in ARGS.items()}
 COUNTS["lgd_conv_in_f16"].append("Cout")                 # conv_out answers LGD_ERR_UNSUPPORTED for a Cout outside {4, 8}
+COUNTS["lgd_multidiffusion_step_f32"] += ["P", "n_steps"]
+COUNTS["lgd_multidiffusion_views_f32"] += ["P", "Hp", "Wp", "nv", "n_steps"]
+COUNTS["lgd_vae_sample_f32"].append("z")
+COUNTS["lgd_sam_relpos_qkv_f16"] += ["Hs", "Ws", "NH", "d"]
+COUNTS["lgd_sam_window_merge_f16"] += ["Hs", "Ws", "NH", "d"]
 # what each entry point has beyond NULL / alignment / counts: (class, label, change)
 _STEP_RULES = [("entry", "frozen_ref without mask", dict(mask=None)), ("entry", "mask without frozen_ref", dict(frozen_ref=None)),
                ("alias", "x_out partly over x", dict(x_out=("x", 64))), ("alias", "x_out inside eps", dict(x_out=("eps", 512))),
@@ -905,6 +1499,59 @@ RULES = {
     "lgd_axpy_f32": [("divisibility", "n % per_sample with active", dict(n=70)), ("alias", "x over g", dict(x=("g", 236))),
                      ("entry", "col 4", dict(col=4)), ("entry", "col -1", dict(col=-1)), ("entry", "per_sample -1", dict(per_sample=-1))],
     "lgd_select_row_f32": [],
+    # B C HW = 128 floats: x, x_out, cur_sample 512 bytes, eps 1024, ets 1536
+    "lgd_cfg_plms_step_f32": [("divisibility", "B C HW % 4", dict(B=1, C=1, HW=6)), ("alias", "x_out 64 bytes into x", dict(x_out=("x", 64))),
+                              ("alias", "x_out inside eps", dict(x_out=("eps", 512))), ("alias", "x_out over ets", dict(x_out=("ets", 1520))),
+                              ("alias", "x_out is cur_sample", dict(x_out=("cur_sample", 0))), ("alias", "ets inside eps", dict(ets=("eps", 16))),
+                              ("alias", "ets over x", dict(ets=("x", 496))), ("alias", "ets over x_out", dict(ets=("x_out", 0))),
+                              ("alias", "ets over cur_sample", dict(ets=("cur_sample", 256))), ("alias", "cur_sample is x", dict(cur_sample=("x", 0))),
+                              ("alias", "cur_sample in the tail of eps", dict(cur_sample=("eps", 1008)))],
+    # a plane C HW is 256 bytes: x_in and eps 1024, latent and noise 256, masks 128, bg 512
+    "lgd_multidiffusion_step_f32": [("entry", "Pp < P", dict(Pp=1)), ("entry", "prep = 2", dict(prep=2)), ("entry", "prep = -1", dict(prep=-1)),
+                                    ("divisibility", "HW % 4", dict(HW=18)), ("entry", "n_boot = -1", dict(n_boot=-1)),
+                                    ("alias", "latent inside x_in", dict(latent=("x_in", 768))), ("alias", "x_in in the tail of eps", dict(x_in=("eps", 1008))),
+                                    ("alias", "latent is eps", dict(latent=("eps", 0))), ("alias", "x_in in the tail of masks", dict(x_in=("masks", 112))),
+                                    ("alias", "latent is masks", dict(latent=("masks", 0))), ("alias", "x_in in the tail of bg", dict(x_in=("bg", 496))),
+                                    ("alias", "latent inside bg", dict(latent=("bg", 256))), ("alias", "x_in is noise", dict(x_in=("noise", 0))),
+                                    ("alias", "latent in the tail of noise", dict(latent=("noise", 240)))],
+    # a view row C 4096 is 16 384 bytes: eps and x_in 131 072; a panorama plane 20 736: latent, value, count, noise; masks 41 472; bg 32 768
+    "lgd_multidiffusion_views_f32": [("entry", "V != nbh nbw", dict(V=3)), ("entry", "v0 + nv > V", dict(v0=3)), ("entry", "v0 = -1", dict(v0=-1)),
+                                     ("entry", "nvc < nv", dict(nvc=1)), ("divisibility", "Wp % 4", dict(Wp=74)), ("entry", "Hp < 64", dict(Hp=56)),
+                                     ("entry", "Wp < 64", dict(Wp=60)), ("entry", "C > 64", dict(C=65)),
+                                     ("entry", "a multi-chunk call without value", dict(normalization=0, value=None)),
+                                     ("entry", "normalization without count", dict(count=None)),
+                                     ("entry", "bootstrapping without picks", dict(prep=1, picks=None)),
+                                     ("entry", "bootstrapping without bg", dict(prep=1, bg=None)),
+                                     ("entry", "bootstrapping without noise", dict(prep=1, noise=None)),
+                                     ("entry", "Pp < P", dict(Pp=1)), ("entry", "prep = 2", dict(prep=2)), ("entry", "n_boot = -1", dict(n_boot=-1)),
+                                     ("alias", "latent is value", dict(latent=("value", 0))), ("alias", "value in the tail of count", dict(value=("count", 20720))),
+                                     ("alias", "count is latent", dict(count=("latent", 0))), ("alias", "latent inside eps", dict(latent=("eps", 4096))),
+                                     ("alias", "value in the tail of x_in", dict(value=("x_in", 131056))), ("alias", "count in the tail of masks", dict(count=("masks", 41456))),
+                                     ("alias", "latent is masks", dict(latent=("masks", 0))), ("alias", "value is eps", dict(value=("eps", 0))),
+                                     ("alias", "prep: x_in is latent", dict(prep=1, x_in=("latent", 0))),
+                                     ("alias", "prep: x_in in the tail of masks", dict(prep=1, x_in=("masks", 41456))),
+                                     ("alias", "prep: x_in in the tail of bg", dict(prep=1, x_in=("bg", 32752))),
+                                     ("alias", "prep: x_in is noise", dict(prep=1, x_in=("noise", 0)))],
+    # 100 pixels: img 300 bytes, y 1600, the table 1024
+    "lgd_image_u8_to_nhwc8_f16": [("divisibility", "B HW % 4", dict(HW=5)), ("alias", "y is img", dict(y=("img", 0))),
+                                  ("alias", "y in the tail of img", dict(y=("img", 288))), ("alias", "y in the tail of the table", dict(y=("table", 1008)))],
+    # moments, noise and out are 640 bytes each
+    "lgd_vae_sample_f32": [("divisibility", "z % 4", dict(z=6)), ("divisibility", "HW % 4", dict(HW=22)), ("alias", "out is moments", dict(out=("moments", 0))),
+                           ("alias", "out in the tail of moments", dict(out=("moments", 624))), ("alias", "out is noise", dict(out=("noise", 0))),
+                           ("alias", "out in the tail of noise", dict(out=("noise", 624)))],
+    # 108 window rows: qa, ka, va 6912 bytes each; qkv 6720, qkv_bias 192, rel_h and rel_w 160
+    "lgd_sam_relpos_qkv_f16": [("entry", "DA < d + 2S", dict(DA=8)), ("entry", "window = 0 with Hs != Ws", dict(window=0)), ("entry", "window = -1", dict(window=-1)),
+                               ("divisibility", "d % 8", dict(d=12, DA=24)), ("divisibility", "DA % 8", dict(DA=20)), ("entry", "scale = 0", dict(scale=0.0)),
+                               ("entry", "scale = NaN", dict(scale=NAN)), ("entry", "scale = -1", dict(scale=-1.0)),
+                               ("alias", "ka is qa", dict(ka=("qa", 0))), ("alias", "va in the tail of qa", dict(va=("qa", 6910))),
+                               ("alias", "ka is va", dict(ka=("va", 0))), ("alias", "qa in the tail of qkv", dict(qa=("qkv", 6718))),
+                               ("alias", "ka in the tail of qkv_bias", dict(ka=("qkv_bias", 190))), ("alias", "va in the tail of rel_h", dict(va=("rel_h", 158))),
+                               ("alias", "qa is rel_w", dict(qa=("rel_w", 0)))],
+    # oa 6912 bytes, out 70 x 16 halfs = 2240
+    "lgd_sam_window_merge_f16": [("divisibility", "d % 8", dict(d=12)), ("divisibility", "DA % 8", dict(DA=20)), ("entry", "DA < d", dict(d=24)),
+                                 ("entry", "window = 0 with Hs != Ws", dict(window=0)), ("entry", "window = -1", dict(window=-1)),
+                                 ("entry", "oa off by 2 bytes", dict(oa=2)), ("alias", "out is oa", dict(out=("oa", 0))),
+                                 ("alias", "out in the tail of oa", dict(out=("oa", 6896)))],
     "lgd_scale_rows_f32": [("alias", "out is x", dict(out=("x", 0))), ("alias", "the second copy over x", dict(x=("out", 28))),
                            ("entry", "col = row_stride", dict(col=5)), ("entry", "col -1", dict(col=-1)), ("entry", "row_stride 0", dict(row_stride=0))],
 }
@@ -913,7 +1560,8 @@ NEEDS["lgd_select_row_f32"] = set()                      # the table's extent is
 NEEDS["lgd_scale_rows_f32"] = {"alias"}
 for _fn in ("lgd_cfg_ddim_step_f32", "lgd_cfg_multistep_step_f32"):
     NEEDS[_fn] = {"alias", "entry"}
-for _fn in ("lgd_axpy_f32", "lgd_act_f16"):
+for _fn in ("lgd_axpy_f32", "lgd_act_f16", "lgd_multidiffusion_step_f32", "lgd_multidiffusion_views_f32", "lgd_sam_relpos_qkv_f16",
+            "lgd_sam_window_merge_f16"):
     NEEDS[_fn] = {"alias", "divisibility", "entry"}
 
 
@@ -924,7 +1572,7 @@ def pointers(fn):
 def _generated(fn):
     rows = []
     for p in pointers(fn):
-        if p not in OPTIONAL:
+        if p not in optional(fn):
             rows.append((fn, f"{p} NULL", {p: None}))
         a = ALIGN[fn][p]
         rows.append((fn, f"{p} off {a} bytes", {p: a // 2}))
@@ -935,7 +1583,9 @@ def _generated(fn):
 
 REFUSALS = [r for fn in ARGS for r in _generated(fn) + [(fn, label, change) for _, label, change in RULES[fn]]]
 UNSUPPORTED = [("lgd_conv_out_f16", "Cout 5", dict(Cout=5)), ("lgd_conv_out_f16", "Cout 0", dict(Cout=0)),
-               ("lgd_conv_in_f16", "the filter and the patches past 64 KB of LDS", dict(Cin=8, Cout=400))]
+               ("lgd_conv_in_f16", "the filter and the patches past 64 KB of LDS", dict(Cin=8, Cout=400)),
+               ("lgd_sam_relpos_qkv_f16", "more than 2^31 - 1 window rows", dict(B=1 << 28)),
+               ("lgd_sam_relpos_qkv_f16", "the query and its rel columns past 64 KB of LDS", dict(NH=2048))]
 
 
 def call_args(fn, change, base=P):

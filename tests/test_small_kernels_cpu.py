@@ -42,7 +42,7 @@ def _answer(fn, change):
 # refusals
 # ---------------------------------------------------------------------------------------------
 def test_the_refusal_table_is_well_formed():
-    assert set(skc.ARGS) == set(skc.BASE) == set(skc.RULES) and len(skc.ARGS) == 16
+    assert set(skc.ARGS) == set(skc.BASE) == set(skc.RULES) and len(skc.ARGS) == 23
     labels = {}
     for fn, what, change in skc.REFUSALS:
         assert set(change) <= {n[2:] if n.startswith("p:") else n for n in skc.ARGS[fn].split()}, (fn, what)
@@ -52,20 +52,33 @@ def test_the_refusal_table_is_well_formed():
         names = args.split()
         assert len(names) == len(_lib.SIGNATURES[fn]), fn
         ptrs = skc.pointers(fn)
-        want = {f"{p} NULL" for p in ptrs if p not in skc.OPTIONAL}
+        want = {f"{p} NULL" for p in ptrs if p not in skc.optional(fn)}
         want |= {f"{p} off {skc.ALIGN[fn][p]} bytes" for p in ptrs}
         counts = [n for n in names if n in ("n", "rows", "B", "H", "W", "L", "HW", "C", "Cin", "reps")]
         want |= {f"{c} = {v}" for c in counts for v in (0, -1)}
         assert want <= labels[fn], (fn, sorted(want - labels[fn]))
         assert skc.NEEDS[fn] <= {cls for cls, _, _ in skc.RULES[fn]}, fn
         vec = [p for p in ptrs if skc.ALIGN[fn][p] == 16]
-        assert all(isinstance(v, tuple) and (v[1] % skc.ALIGN[fn][k] == 0) for cls, _, ch in skc.RULES[fn] if cls == "alias"
-                   for k, v in ch.items()), fn           # an alias row is refused for the overlap, not for its alignment
+        for cls, what, ch in skc.RULES[fn]:              # an alias row is refused for the overlap, not for its alignment or its form
+            if cls == "alias":
+                moved = {k: v for k, v in ch.items() if isinstance(v, tuple)}
+                assert moved and all(v[1] % skc.ALIGN[fn][k] == 0 for k, v in moved.items()), (fn, what)
+                assert set(ch) - set(moved) <= {"prep"}, (fn, what)       # test_alias_rows_change_a_served_form
         assert fn in ("lgd_cfg_ddim_step_f32", "lgd_cfg_multistep_step_f32", "lgd_axpy_f32", "lgd_select_row_f32",
-                      "lgd_scale_rows_f32", "lgd_conv_in_f16") or vec, fn
+                      "lgd_scale_rows_f32", "lgd_conv_in_f16", "lgd_sam_relpos_qkv_f16") or vec, fn
     step = {w for f, w, _ in skc.REFUSALS if f == "lgd_cfg_ddim_step_f32"}
     assert {"frozen_ref without mask", "mask without frozen_ref"} <= step
     assert {"col 4", "col -1", "per_sample -1", "n % per_sample with active"} <= labels["lgd_axpy_f32"]
+    assert {"V != nbh nbw", "v0 + nv > V", "nvc < nv", "Wp % 4", "Hp < 64", "C > 64", "a multi-chunk call without value",
+            "normalization without count", "bootstrapping without picks"} <= labels["lgd_multidiffusion_views_f32"]
+    assert {"Pp < P", "prep = 2", "HW % 4"} <= labels["lgd_multidiffusion_step_f32"]
+    assert {"DA < d + 2S", "window = 0 with Hs != Ws", "d % 8", "scale = 0", "scale = NaN"} <= labels["lgd_sam_relpos_qkv_f16"]
+    assert {f for f, _, _ in skc.UNSUPPORTED} >= {"lgd_sam_relpos_qkv_f16"}
+    # the calls a probe of the parent commit saw reach the launch
+    assert {"qkv NULL", "ka is qa"} <= labels["lgd_sam_relpos_qkv_f16"]
+    assert {"out NULL", "oa off by 2 bytes", "out is oa"} <= labels["lgd_sam_window_merge_f16"]
+    assert {"x_out 64 bytes into x", "cur_sample is x", "ets inside eps", "coef_table off 4 bytes"} <= labels["lgd_cfg_plms_step_f32"]
+    assert "out is moments" in labels["lgd_vae_sample_f32"] and "y is img" in labels["lgd_image_u8_to_nhwc8_f16"]
 
 
 def test_base_calls_are_well_formed():
@@ -87,8 +100,20 @@ def test_unsupported_stays_unsupported(fn, what, change):
     assert _answer(fn, change) == ERR_UNSUPPORTED, (fn, what)
 
 
+def test_alias_rows_change_a_served_form():
+    """An alias row that also switches the form (views: prep = 1) overlaps operands of a call the library serves."""
+    if torch.cuda.is_available():
+        pytest.skip("the placeholder pointers would be launched on")
+    forms = {(fn, tuple(sorted((k, v) for k, v in ch.items() if not isinstance(v, tuple))))
+             for fn in skc.RULES for cls, _, ch in skc.RULES[fn] if cls == "alias"}
+    assert any(form for _, form in forms)
+    for fn, form in forms:
+        assert _answer(fn, dict(form)) == ERR_LAUNCH, (fn, form)
+
+
 def test_optional_operands_stay_optional():
-    """bias; hist; frozen_ref and mask together; active: NULL passes every check (host without a GPU: the launch is reached)."""
+    """bias; hist; frozen_ref and mask together; active; eps with prep; bg, noise and picks with one prompt; value and count with
+    one chunk: NULL passes every check (host without a GPU: the launch is reached)."""
     if torch.cuda.is_available():
         pytest.skip("the placeholder pointers would be launched on")
     for fn, change in (("lgd_conv_out_f16", dict(bias=None)), ("lgd_conv_in_f16", dict(bias=None)),
@@ -99,7 +124,18 @@ def test_optional_operands_stay_optional():
                        ("lgd_add_f16", dict(y=("a", 0))), ("lgd_add_f16", dict(y=("b", 0))), ("lgd_add_f16", dict(y=("a", 0), b=("a", 0))),
                        ("lgd_add_f16", dict(b=("a", 16))), ("lgd_scale_f16", dict(y=("x", 0))), ("lgd_quick_gelu_f16", dict(y=("x", 0))),
                        ("lgd_act_f16", dict(y=("x", 0))), ("lgd_act_f16", dict(mode=2)), ("lgd_softmax_rows_f16", dict(y=("x", 0))),
-                       ("lgd_cfg_ddim_step_f32", dict(x_out=("x", 0))), ("lgd_cfg_multistep_step_f32", dict(x_out=("x", 0)))):
+                       ("lgd_cfg_ddim_step_f32", dict(x_out=("x", 0))), ("lgd_cfg_multistep_step_f32", dict(x_out=("x", 0))),
+                       ("lgd_cfg_plms_step_f32", dict(x_out=("x", 0))), ("lgd_cfg_plms_step_f32", dict(hist=None)),
+                       ("lgd_cfg_multistep_step_f32", dict(hist=None)), ("lgd_multidiffusion_step_f32", dict(hist=None)),
+                       ("lgd_multidiffusion_views_f32", dict(hist=None)), ("lgd_multidiffusion_step_f32", dict(prep=1, eps=None)),
+                       ("lgd_multidiffusion_step_f32", dict(P=1, Pp=1, bg=None, noise=None, picks=None)),
+                       ("lgd_multidiffusion_step_f32", dict(n_boot=0, bg=None, noise=None, picks=None)),
+                       ("lgd_multidiffusion_views_f32", dict(nv=4, nvc=4, value=None, count=None)),
+                       ("lgd_multidiffusion_views_f32", dict(normalization=0, count=None)),
+                       ("lgd_multidiffusion_views_f32", dict(bg=None, noise=None, picks=None)),
+                       ("lgd_multidiffusion_views_f32", dict(prep=1, eps=None, value=None, count=None, hist=None)),
+                       ("lgd_multidiffusion_views_f32", dict(prep=1, P=1, Pp=1, bg=None, noise=None, picks=None)),
+                       ("lgd_multidiffusion_views_f32", dict(v0=2)), ("lgd_multidiffusion_views_f32", dict(nvc=3, nv=3))):
         assert _answer(fn, change) == ERR_LAUNCH, (fn, change)
 
 
@@ -150,6 +186,35 @@ def _wrapper_faults():
         ("scale_rows: dtype", lambda: ops.scale_rows(h(8), f(8), f(3, 5), i(4), 3)),
         ("select_row: no rows of that length", lambda: ops.select_row(f(4, 300), i(1), f(299))),
         ("select_row: idx dtype", lambda: ops.select_row(f(4, 300), torch.zeros(1, dtype=torch.int64), f(300))),
+        ("cfg_plms_step: ets count", lambda: ops.cfg_plms_step(f(4, 4, 4, 4), x4, x4, f(2, 2, 4, 4, 4), f(2, 4, 4, 4), f(7, 16), i(4))),
+        ("cfg_plms_step: table width", lambda: ops.cfg_plms_step(f(4, 4, 4, 4), x4, x4, f(3, 2, 4, 4, 4), f(2, 4, 4, 4), f(7, 10), i(4))),
+        ("cfg_plms_step: cur_sample dtype", lambda: ops.cfg_plms_step(f(4, 4, 4, 4), x4, x4, f(3, 2, 4, 4, 4), h(2, 4, 4, 4), f(7, 16), i(4))),
+        ("cfg_plms_step: eps strided", lambda: ops.cfg_plms_step(f(4, 4, 4, 8)[..., :4], x4, x4, f(3, 2, 4, 4, 4), f(2, 4, 4, 4), f(7, 16), i(4))),
+        ("multidiffusion_step: eps count", lambda: ops.multidiffusion_step(f(2, 4, 4, 4), f(4, 4, 4, 4), f(4, 4, 4), f(2, 16), f(4, 4), i(4), n_prompts=2, n_steps=4)),
+        ("multidiffusion_step: masks rows", lambda: ops.multidiffusion_step(f(4, 4, 4, 4), f(4, 4, 4, 4), f(4, 4, 4), f(1, 16), f(4, 4), i(4), n_prompts=2, n_steps=4)),
+        ("multidiffusion_step: latent is no row", lambda: ops.multidiffusion_step(f(4, 4, 4, 4), f(4, 4, 4, 4), f(4, 4, 2), f(2, 16), f(4, 4), i(4), n_prompts=2, n_steps=4)),
+        ("multidiffusion_step: picks dtype", lambda: ops.multidiffusion_step(f(4, 4, 4, 4), f(4, 4, 4, 4), f(4, 4, 4), f(2, 16), f(4, 4), i(4), n_prompts=2, n_steps=4,
+                                                                              bg=f(2, 4, 4, 4), noise=f(4, 4, 4), picks=torch.zeros(4, 1, dtype=torch.int64), n_boot=2)),
+        ("multidiffusion_step: bg rows", lambda: ops.multidiffusion_step(f(4, 4, 4, 4), f(4, 4, 4, 4), f(4, 4, 4), f(2, 16), f(4, 4), i(4), n_prompts=2, n_steps=4,
+                                                                          bg=f(1, 4, 4, 4), noise=f(4, 4, 4), picks=i(4, 1), n_boot=2)),
+        ("multidiffusion_views: value count", lambda: ops.multidiffusion_views(f(4, 1, 64, 64), f(4, 1, 64, 64), f(1, 72, 72), f(1, 72, 64), None, f(2, 72, 72), f(4, 4), i(4),
+                                                                                n_prompts=2, rows_per_view=2, n_views=4, v0=0, nv=1, n_steps=4)),
+        ("multidiffusion_views: window", lambda: ops.multidiffusion_views(f(4, 1, 32, 32), f(4, 1, 32, 32), f(1, 72, 72), None, None, f(2, 72, 72), f(4, 4), i(4),
+                                                                           n_prompts=2, rows_per_view=2, n_views=4, v0=0, nv=1, n_steps=4)),
+        ("multidiffusion_views: masks dtype", lambda: ops.multidiffusion_views(f(4, 1, 64, 64), f(4, 1, 64, 64), f(1, 72, 72), None, None, h(2, 72, 72), f(4, 4), i(4),
+                                                                                n_prompts=2, rows_per_view=2, n_views=4, v0=0, nv=1, n_steps=4)),
+        ("image_u8_to_nhwc8: dtype", lambda: ops.image_u8_to_nhwc8(f(2, 5, 10, 3))),
+        ("image_u8_to_nhwc8: channels", lambda: ops.image_u8_to_nhwc8(torch.zeros(2, 5, 10, 4, dtype=torch.uint8))),
+        ("image_u8_to_nhwc8: strided", lambda: ops.image_u8_to_nhwc8(torch.zeros(2, 5, 20, 3, dtype=torch.uint8)[:, :, :10])),
+        ("vae_sample: moments count", lambda: ops.vae_sample(h(40, 4), f(2, 4, 4, 5), 1.0)),
+        ("vae_sample: noise dtype", lambda: ops.vae_sample(h(40, 8), h(2, 4, 4, 5), 1.0)),
+        ("vae_sample: out count", lambda: ops.vae_sample(h(40, 8), f(2, 4, 4, 5), 1.0, f(2, 4, 4, 4))),
+        ("sam_relpos_qkv: qkv count", lambda: ops.sam_relpos_qkv(h(70, 24), f(48), f(5, 8), f(5, 8), 2, 5, 7, 3, 2, 8, 16, 0.35)),
+        ("sam_relpos_qkv: rel_h rows", lambda: ops.sam_relpos_qkv(h(70, 48), f(48), f(6, 8), f(5, 8), 2, 5, 7, 3, 2, 8, 16, 0.35)),
+        ("sam_relpos_qkv: qa count", lambda: ops.sam_relpos_qkv(h(70, 48), f(48), f(5, 8), f(5, 8), 2, 5, 7, 3, 2, 8, 16, 0.35, qa=h(70, 32))),
+        ("sam_relpos_qkv: bias dtype", lambda: ops.sam_relpos_qkv(h(70, 48), h(48), f(5, 8), f(5, 8), 2, 5, 7, 3, 2, 8, 16, 0.35)),
+        ("sam_window_merge: oa count", lambda: ops.sam_window_merge(h(70, 32), 2, 5, 7, 3, 2, 8, 16)),
+        ("sam_window_merge: out strided", lambda: ops.sam_window_merge(h(108, 32), 2, 5, 7, 3, 2, 8, 16, out=h(70, 32)[:, :16])),
         # the two guidance energies: tests/test_energy_kernels_cpu.py holds the full list
         ("ca_energy: partial count", lambda: ops.ca_energy(torch.zeros(1, dtype=torch.int64), None, i(1), i(3, 8), f(3, 4), f(2, 256), None, 0,
                                                            None, i(2, 2), 2, 3, 3, 77, 256, f(3), f(1))),
@@ -172,7 +237,8 @@ def test_every_wrapper_has_a_check():
     heads = {w.split(":")[0] for w, _ in _FAULTS}
     assert heads == {"add", "scale", "quick_gelu", "act", "geglu_fwd", "geglu_bwd", "softmax_rows", "upsample2x_bwd", "nchw_to_nhwc8",
                      "conv_out", "conv_in", "cfg_ddim_step", "cfg_multistep_step", "axpy", "scale_rows", "select_row", "ca_energy",
-                     "boxdiff_energy"}
+                     "boxdiff_energy", "cfg_plms_step", "multidiffusion_step", "multidiffusion_views", "image_u8_to_nhwc8", "vae_sample",
+                     "sam_relpos_qkv", "sam_window_merge"}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -219,9 +285,29 @@ def test_wrong_answer_falls_outside(name):
     assert r > 1.0, name
 
 
+def test_views_chunkings_share_one_panorama():
+    """The GPU suite asks every chunking of a views form for the same latent bits: the rows that differ only in nvc hold the same
+    logical operands, and all three chunkings of V = 4 (one chunk, two of 2, 3 and a short last one) are among them."""
+    groups = {}
+    for row in skc.rows_of("md_views"):
+        if not row.prep:
+            groups.setdefault(skc.ENTRIES["md_views"].key(row), []).append(row)
+    assert sum(1 for g in groups.values() if {r.nvc for r in g} == {4, 2, 3}) == 4
+    assert any({r.nvc for r in g} == {2, 1} for g in groups.values())
+    for g in groups.values():
+        first = g[0].data("plain")
+        for row in g[1:]:
+            d = row.data("plain")
+            assert all(torch.equal(d[n].view(torch.int32), first[n].view(torch.int32)) for n in ("eps_l", "xin_l", "masks")), row.name
+
+
 def test_grid_stride_tail_left_unwritten_falls_outside():
     rows = skc.grid_stride_rows()
-    assert {r.entry for r in rows} >= {"add", "scale", "quick_gelu", "act_gelu", "act_relu", "geglu_fwd", "geglu_bwd", "cfg_ddim", "cfg_multistep"}
+    assert {r.entry for r in rows} >= {"add", "scale", "quick_gelu", "act_gelu", "act_relu", "geglu_fwd", "geglu_bwd", "cfg_ddim", "cfg_multistep",
+                                       "cfg_plms", "image_u8", "vae_sample"}
+    for entry, vecs in (("cfg_plms", lambda r: r.B * r.C * r.HW // 4), ("image_u8", lambda r: r.B * r.HW // 4),
+                        ("vae_sample", lambda r: r.B * (r.z // 4) * (r.HW // 4))):
+        assert [r for r in rows if r.entry == entry and vecs(r) > skc.GRID_VECS], entry      # the loop iterates
     row = skc.ROWS_BY_NAME[f"add:n={skc.N_STRIDE}:inplace="]
     assert row.n // 8 > skc.GRID_VECS                      # the loop iterates
     d = row.data("plain")
