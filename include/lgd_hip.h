@@ -417,6 +417,20 @@ int lgd_vae_sample_f32(const void* moments, const float* noise, float* out, int 
  * every row is finite; +inf and NaN are not inputs.
  * rows >= 1; n >= 8 and n % 8 == 0; x, y non-NULL and 16-byte aligned; y may be x. */
 int lgd_softmax_rows_f16(const void* x, void* y, int64_t rows, int n, float scale, void* stream);
+/* Range probe of an fp16 matrix (additive export: LGD_ABI_VERSION stays 12) — what vae.calibrate_ranges measures of
+ * every tensor the VAE blocks store, to choose the power-of-two scales of an overflow-prone (SDXL) VAE:
+ *   out2[0] = max(out2[0], bits of the fp32 value of the largest |x| among the FINITE elements)
+ *   out2[1] += number of non-finite elements (+-Inf, NaN), saturating at 2^32 - 1
+ * Non-negative floats order like their bit patterns, so out2[0] read as a float is the running maximum.  The caller
+ * zeroes the 8 bytes to start a measurement; several calls accumulate into one pair.  Both combiners are
+ * order-independent: the result is exact and the same for every grid.  x: fp16 [rows][ld], of which only the columns
+ * < cols of each row are read (the padding up to ld may hold anything, NaN included).  One launch (capturable): 16-byte
+ * loads when cols % 8 == 0, ld % 8 == 0 and x is 16-byte aligned, element loads otherwise; one atomic max and, where
+ * there is something to count, one atomic add per workgroup.  This entry point takes non-finite inputs: counting them
+ * is its purpose.
+ * rows, cols >= 1; ld >= cols; x, out2 non-NULL, x 2-byte and out2 4-byte aligned; out2 outside the range of x
+ * (LGD_ERR_ARG otherwise); more than 2^40 elements: LGD_ERR_UNSUPPORTED. */
+int lgd_range_f16(const void* x, int64_t rows, int64_t cols, int64_t ld, uint32_t* out2, void* stream);
 /* sum over the 2x2 children of a nearest-2x upsampling: gy [B][2H*2W][C] -> gx [B][H*W][C],
  *   gx[b][y][x][c] = sum_{dy,dx < 2} gy[b][2y+dy][2x+dx][c]      (fp32 sum, one fp16 rounding).
  * B, H, W >= 1; C >= 8 and C % 8 == 0; gy, gx non-NULL and 16-byte aligned; no aliasing. */

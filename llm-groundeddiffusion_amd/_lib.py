@@ -99,6 +99,7 @@ SIGNATURES = {
     "lgd_nchw_to_nhwc8_f16": [_P, _P, _I, _I, _I, _P],
     "lgd_image_u8_to_nhwc8_f16": [_P, _P, _P, _I, _I, _P],
     "lgd_vae_sample_f32": [_P, _P, _P, _I, _I, _I, _F, _P],
+    "lgd_range_f16": [_P, _L, _L, _L, _P, _P],
     "lgd_sam_relpos_qkv_f16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "lgd_sam_window_merge_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lgd_ca_energy_f32": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],

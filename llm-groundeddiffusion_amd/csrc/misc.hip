@@ -705,6 +705,77 @@ __global__ __launch_bounds__(256) void select_row_kernel(const float* __restrict
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = table[r * n + i];
 }
 
+// Range probe of an fp16 matrix (lgd_hip.h: lgd_range_f16): the largest finite magnitude and the count of non-finite
+// elements, accumulated into out2.  The bit pattern of |x| orders fp16 magnitudes, and >= 0x7c00 is Inf or NaN, so the
+// whole reduction is integer max / add: exact and the same for every grid.  VEC: a unit is a 16-byte vector of 8
+// elements, else one element; `per_row` units of each row are read, rows are `ld` elements apart.
+constexpr int RANGE_WGS = 4 * 256;  // 4 workgroups (16 waves) on each of the 256 CUs, two loads in flight per lane
+
+__device__ __forceinline__ void range_take(uint32_t h, uint32_t& mx, uint32_t& bad) {
+  h &= 0x7fffu;
+  const bool nf = h >= 0x7c00u;
+  mx = max(mx, nf ? 0u : h);
+  bad += nf ? 1u : 0u;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void range_unit(const uint16_t* __restrict__ x, long i, long per_row, long ld, bool narrow,
+                                           uint32_t& mx, uint32_t& bad) {
+  // (the host hands a contiguous matrix over as one row, so only a padded one pays for the division)
+  const long r = per_row == 0 ? 0 : (narrow ? (long)((uint32_t)i / (uint32_t)per_row) : i / per_row);
+  const long c = i - r * per_row;
+  if (VEC) {
+    const uint4 v = *reinterpret_cast<const uint4*>(x + r * ld + c * 8);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      range_take(w[e], mx, bad);
+      range_take(w[e] >> 16, mx, bad);
+    }
+  } else {
+    range_take(x[r * ld + c], mx, bad);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void range_f16_kernel(const uint16_t* __restrict__ x, long rows, long per_row, long ld,
+                                                         uint32_t* out2) {
+  __shared__ uint32_t red[8];
+  const long total = rows * per_row, stride = gridDim.x * 256L;
+  const bool narrow = total <= 0x7fffffffL;
+  const long div = rows == 1 ? 0 : per_row;  // one row: unit i is column i
+  uint32_t mx = 0, bad = 0;
+  long i = blockIdx.x * 256L + threadIdx.x;
+  for (; i + stride < total; i += 2 * stride) {
+    uint32_t m1 = 0, b1 = 0;
+    range_unit<VEC>(x, i, div, ld, narrow, mx, bad);
+    range_unit<VEC>(x, i + stride, div, ld, narrow, m1, b1);
+    mx = max(mx, m1);
+    bad += b1;
+  }
+  if (i < total) range_unit<VEC>(x, i, div, ld, narrow, mx, bad);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+    bad += (uint32_t)__shfl_xor((int)bad, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = mx;
+    red[4 + (threadIdx.x >> 6)] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mx = max(max(red[0], red[1]), max(red[2], red[3]));
+    bad = red[4] + red[5] + red[6] + red[7];  // at most 2^40 elements over RANGE_WGS workgroups: 2^30 in one
+    if (mx) atomicMax(out2, __float_as_uint((float)__builtin_bit_cast(_Float16, (uint16_t)mx)));
+    if (bad) {
+      // saturating: the counter leaves 0xffffffff only through an add, which wraps, and whoever wraps it pins it again
+      const uint32_t was = atomicAdd(out2 + 1, bad);
+      if (was + bad < was) atomicMax(out2 + 1, 0xffffffffu);
+    }
+  }
+}
+
 using lgd_contract::misaligned;
 using lgd_contract::overlaps;
 using lgd_contract::partly_overlaps;
@@ -1059,5 +1130,29 @@ extern "C" int lgd_select_row_f32(const float* table, const int32_t* idx, float*
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(select_row_kernel, dim3(ew_blocks(n)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), table, idx, out, n);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_range_f16(const void* x, int64_t rows, int64_t cols, int64_t ld, uint32_t* out2, void* stream) {
+  if (!x || !out2 || rows < 1 || cols < 1 || ld < cols || misaligned(x, 2) || misaligned(out2, 4)) return LGD_ERR_ARG;
+  constexpr int64_t MAX_ELEMS = (int64_t)1 << 40;
+  if (rows > MAX_ELEMS / cols) return LGD_ERR_UNSUPPORTED;
+  if (rows > 1 && ld > ((int64_t)1 << 60) / rows) return LGD_ERR_ARG;  // no such address range
+  if (overlaps(out2, 8, x, ((rows - 1) * ld + cols) * 2)) return LGD_ERR_ARG;
+  const bool vec = (cols % 8) == 0 && (ld % 8) == 0 && !misaligned(x, 16);
+  if (ld == cols || rows == 1) {  // contiguous: one long row
+    cols *= rows;
+    rows = 1;
+    ld = cols;
+  }
+  const long per_row = vec ? cols / 8 : cols;
+  const long wgs = (rows * per_row + 255) / 256;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  const dim3 grid((unsigned)(wgs < RANGE_WGS ? wgs : RANGE_WGS));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL((range_f16_kernel<true>), grid, dim3(256), 0, st, (const uint16_t*)x, (long)rows, per_row, (long)ld, out2);
+  else
+    hipLaunchKernelGGL((range_f16_kernel<false>), grid, dim3(256), 0, st, (const uint16_t*)x, (long)rows, per_row, (long)ld, out2);
   return lgd_check_launch();
 }

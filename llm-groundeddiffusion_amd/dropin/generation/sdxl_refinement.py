@@ -23,8 +23,8 @@ pipe = None
 REFINE_SIZE = 1024                     # sdxl_refinement.py:26
 
 
-def init(offload_model=True, device="cuda"):
-    """sdxl_refinement.py:10-22."""
+def init(offload_model=True, device="cuda", vae_ranges=None):
+    """sdxl_refinement.py:10-22.  vae_ranges: see _vae_ranges (the checkpoint's VAE sets config.force_upcast)."""
     global pipe
     try:
         from diffusers import StableDiffusionXLImg2ImgPipeline
@@ -33,13 +33,32 @@ def init(offload_model=True, device="cuda"):
                            "diffusers, which is not installed here; use init_synthetic() for seeded random weights") from e
     hf = StableDiffusionXLImg2ImgPipeline.from_pretrained("stabilityai/stable-diffusion-xl-refiner-1.0",
                                                           torch_dtype=torch.float16, variant="fp16", use_safetensors=True)
-    pipe = from_diffusers(hf, device)
+    pipe = from_diffusers(hf, device, vae_ranges)
     return pipe
 
 
-def from_diffusers(hf_pipe, device="cuda"):
+def _vae_ranges(config, override, env):
+    """The range plan (lgd_amd.vae.RangePlan | None) a VAE with this `config` is built with.  The SDXL VAE is exported
+    with force_upcast = true: its activations leave the fp16 range and the reference pipeline runs it in fp32.  The HIP
+    VAE stays in fp16 and stores the residual stream scaled down by powers of two instead:
+      LGD_SDXL_VAE_FP16 set in `env`   None: plain fp16, whatever else is given (the switch keeps its meaning)
+      `override` given                 that plan (a caller who ran vae.calibrate_ranges on the checkpoint)
+      config.force_upcast              RangePlan.uniform(vae.FORCE_UPCAST_EXPONENT) — unmeasured on the real checkpoint
+      otherwise                        None, as for every fp16-safe VAE
+    refine() still checks that the latents and the decoded image are finite."""
+    from lgd_amd import vae
+    if env.get("LGD_SDXL_VAE_FP16"):
+        return None
+    if override is not None:
+        return override
+    flag = config.get("force_upcast", False) if isinstance(config, dict) else getattr(config, "force_upcast", False)
+    return vae.RangePlan.uniform(vae.FORCE_UPCAST_EXPONENT) if flag else None
+
+
+def from_diffusers(hf_pipe, device="cuda", vae_ranges=None):
     """A loaded StableDiffusionXLImg2ImgPipeline -> SDXLRefiner: weights are read from the modules' state dicts, the
-    UNet configuration from `unet.config` (must be the refiner's topology family: text_time, linear projections)."""
+    UNet configuration from `unet.config` (must be the refiner's topology family: text_time, linear projections).
+    vae_ranges: the VAE's range plan (see _vae_ranges)."""
     from lgd_amd import clip, vae, weights
     from lgd_amd.scheduler import EulerDiscreteScheduler
     from lgd_amd.unet import UNetEngine
@@ -57,26 +76,19 @@ def from_diffusers(hf_pipe, device="cuda"):
                              projection_class_embeddings_input_dim=c.projection_class_embeddings_input_dim)
     eng = UNetEngine(cfg, device, {k: v.float().cpu() for k, v in hf_pipe.unet.state_dict().items()}, max_text_batch=2)
     vsd = hf_pipe.vae.state_dict()
-    if getattr(hf_pipe.vae.config, "force_upcast", False) and not _os.environ.get("LGD_SDXL_VAE_FP16"):
-        # The SDXL VAE is exported with force_upcast=true: its activations overflow fp16, so the reference pipeline runs
-        # encode and decode in fp32.  HipVAEEncoder / HipVAEDecoder keep every activation in fp16 -> inf / NaN latents
-        # or black images with the real checkpoint.  Refuse instead of producing them silently; a checkpoint with the
-        # fp16-safe VAE weights (config.force_upcast = false) loads, and LGD_SDXL_VAE_FP16=1 overrides (refine() then
-        # still checks that the moments and the decoded image are finite).
-        raise RuntimeError("this VAE sets config.force_upcast (fp16 overflow): the fp16 HIP VAE would produce non-finite "
-                           "latents; load an fp16-safe VAE (force_upcast=false) or set LGD_SDXL_VAE_FP16=1 to try anyway")
+    ranges = _vae_ranges(hf_pipe.vae.config, vae_ranges, _os.environ)
     sch = hf_pipe.scheduler.config
-    return _sdxl.SDXLRefiner(eng, vae.HipVAEEncoder(vsd, device), vae.HipVAEDecoder(vsd, device),
+    return _sdxl.SDXLRefiner(eng, vae.HipVAEEncoder(vsd, device, ranges=ranges), vae.HipVAEDecoder(vsd, device, ranges=ranges),
                              text_encoder=clip.from_hf(hf_pipe.text_encoder_2, device), tokenizer=hf_pipe.tokenizer_2,
                              scheduler=EulerDiscreteScheduler(sch.num_train_timesteps, sch.beta_start, sch.beta_end,
                                                               sch.steps_offset, sch.prediction_type),
                              scaling_factor=hf_pipe.vae.config.scaling_factor)
 
 
-def init_synthetic(config="sdxl_refiner", device="cuda", seed=0):
+def init_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ranges=None):
     """Offline stand-in for init(): the refiner's networks with seeded random parameters."""
     global pipe
-    pipe, _ = _sdxl.build_synthetic(config, device, seed)
+    pipe, _ = _sdxl.build_synthetic(config, device, seed, vae_ranges=vae_ranges)
     return pipe
 
 

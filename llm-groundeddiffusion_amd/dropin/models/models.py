@@ -62,13 +62,14 @@ def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True, loa
 
 
 def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_scheduler=False,
-            use_dpm_multistep_scheduler=False, scheduler_cls=None):
+            use_dpm_multistep_scheduler=False, scheduler_cls=None, vae_ranges=None):
     """models/models.py:16-62.  Needs the Hugging Face checkpoint (diffusers + network/cache); the UNet
     state dict is repacked into the HIP engine's arenas, the CLIP text tower runs on the HIP kernels
     (lgd_amd.clip), the VAE's state dict is repacked for the HIP kernels (lgd_amd.vae.HipVAE: the decoder at once, the
     encoder when pipelines.encode first needs it; LGD_HF_VAE=1 in the environment keeps the Hugging Face module, for A/B
     checks against it).  load_inverse_scheduler (models/models.py:57-59): model_dict.inverse_scheduler for
-    pipelines.invert."""
+    pipelines.invert.  vae_ranges: the range plan of a VAE whose config sets force_upcast (the SDXL VAE), by the rule
+    of generation.sdxl_refinement._vae_ranges: RangePlan.uniform(8) when none is given, none for an fp16-safe VAE."""
     if not use_fp16:      # models/models.py:33-38: the reference then loads fp32 weights ("run final results in fp32")
         from generation._common import note_precision
         note_precision("models.load_sd", "use_fp16=False")
@@ -114,9 +115,11 @@ def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_s
     if _os.environ.get("LGD_HF_VAE", "0") == "1":
         dec = _HFVae()
     else:
+        from generation.sdxl_refinement import _vae_ranges
         from lgd_amd.vae import HipVAE
         dec = HipVAE.from_state_dict(vae.state_dict(), torch_device,             # models/models.py:41 on the HIP kernels
-                                     scaling_factor=getattr(vae.config, "scaling_factor", 0.18215))
+                                     scaling_factor=getattr(vae.config, "scaling_factor", 0.18215),
+                                     ranges=_vae_ranges(vae.config, vae_ranges, _os.environ))
     return build_model_dict(cfg, {k: v.float() for k, v in hf.state_dict().items()}, vae=dec, tokenizer=tok,
                             text_encoder=te, scheduler_config=sched_cfg,
                             use_dpm_multistep_scheduler=use_dpm_multistep_scheduler,

@@ -470,6 +470,20 @@ def vae_sample(moments, noise, scale, out=None):
     return out
 
 
+def range_f16(x2d, table, site):
+    """Row `site` of `table` (int32 [n, 2], zeroed by the caller) takes the range of x2d (fp16 [rows, cols], rows
+    `stride(0)` elements apart): word 0 = the fp32 bits of the largest finite |x| so far, word 1 = how many elements were
+    not finite (lgd_hip.h: lgd_range_f16).  Calls accumulate; read word 0 through `table.view(torch.float32)`."""
+    if x2d.dim() != 2 or x2d.dtype != F16 or (x2d.shape[1] > 1 and x2d.stride(1) != 1):
+        raise RuntimeError(f"range_f16: x is {x2d.dtype} {tuple(x2d.shape)} with strides {x2d.stride()}, the kernel reads fp16 rows")
+    _operands("range_f16", ("table", table, torch.int32, None))
+    if table.dim() != 2 or table.shape[1] != 2 or not 0 <= int(site) < table.shape[0]:
+        raise RuntimeError(f"range_f16: table {tuple(table.shape)} has no pair {site}")
+    rows, cols = x2d.shape
+    ld = x2d.stride(0) if rows > 1 else cols
+    _call("lgd_range_f16", _p(x2d), rows, cols, ld, C.c_void_p(table.data_ptr() + 8 * int(site)), _stream())
+
+
 def conv_out(x, w, bias, B, L, out=None, out_scale=1.0):
     Cin = x.shape[1]
     Cout = w.shape[0]

@@ -152,26 +152,30 @@ class SDXLRefiner:
             raise ValueError(f"strength {strength} leaves no denoising step")
         lat = self.prepare_latents(image, seed, float(sch.timesteps[first]))
         if not bool(torch.isfinite(lat).all()):
-            # fp16 activations of the HIP VAE encoder overflowed (the real SDXL VAE needs fp32: config.force_upcast)
-            raise RuntimeError("non-finite latents from the VAE encoder (fp16 overflow; this VAE needs an fp32 / fp16-safe variant)")
+            # fp16 activations of the HIP VAE encoder overflowed: no range plan, or one too small for this image
+            raise RuntimeError("non-finite latents from the VAE encoder (fp16 overflow): build the refiner with vae_ranges= "
+                               "— the plan vae.calibrate_ranges measures on this checkpoint, or a larger RangePlan.uniform(k)")
         lat = self.refine_latents(lat, prompt_embeds, pooled, first_index=first, num_inference_steps=num_inference_steps,
                                   guidance_scale=guidance_scale, height=H, width=W)
         if output == "latent":
             return lat
         img = self.dec.decode(lat / self.scaling_factor)
         if not bool(torch.isfinite(img).all()):
-            raise RuntimeError("non-finite image from the VAE decoder (fp16 overflow; this VAE needs an fp32 / fp16-safe variant)")
+            raise RuntimeError("non-finite image from the VAE decoder (fp16 overflow): build the refiner with vae_ranges= "
+                               "— the plan vae.calibrate_ranges measures on this checkpoint, or a larger RangePlan.uniform(k)")
         if output == "float":
             return img
         u8 = ((img[0] / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0)
         return u8.contiguous() if output == "device" else u8.cpu().numpy()
 
 
-def build_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ch=(128, 256, 512, 512), vae_layers=2):
+def build_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ch=(128, 256, 512, 512), vae_layers=2,
+                    vae_ranges=None):
     """The refiner with seeded random parameters of the real architectures (no checkpoints in the sandbox):
-    UNet `config`, SD / SDXL VAE encoder + decoder.  No text tower (callers pass embeddings)."""
+    UNet `config`, SD / SDXL VAE encoder + decoder.  No text tower (callers pass embeddings).  vae_ranges: the
+    vae.RangePlan both VAE halves are built with (None: plain fp16)."""
     from . import vae, weights
     cfg = weights.CONFIGS[config]
     eng = UNetEngine(cfg, device, weights.synth_state_dict(cfg, seed), max_text_batch=2)
     sd = vae.synth_aekl_state_dict(vae_ch, vae_layers, seed=seed)
-    return SDXLRefiner(eng, vae.HipVAEEncoder(sd, device), vae.HipVAEDecoder(sd, device)), sd
+    return SDXLRefiner(eng, vae.HipVAEEncoder(sd, device, ranges=vae_ranges), vae.HipVAEDecoder(sd, device, ranges=vae_ranges)), sd

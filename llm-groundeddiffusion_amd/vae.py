@@ -14,7 +14,10 @@ Architecture (SD config: block_out_channels (128,256,512,512), layers_per_block 
 post_quant_conv 4->4 (1x1), conv_in 4->512, mid (resnet, 1-head attention, resnet), 4 up blocks
 (512,512,256,128) x 3 resnets with 3 nearest-2x upsamplers, GroupNorm+SiLU, conv_out 128->3.
 """
+import collections
+import math
 import re
+import types
 
 import torch
 
@@ -22,6 +25,164 @@ import torch
 def _state_dict(source):
     """An AutoencoderKL state dict, or a module that hands one out through `aekl_state_dict()`."""
     return source.aekl_state_dict() if hasattr(source, "aekl_state_dict") else source
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Range plan: an overflow-prone VAE (SDXL: config.force_upcast) in fp16.
+#
+# Between its GroupNorms the network is scale-covariant: GroupNorm(x / s) with eps / s^2 equals GroupNorm(x) with eps.
+# Every tensor that can grow is the residual stream or a resnet's conv1 output, and each of them is written by a GEMM
+# whose epilogue computes alpha * (acc + bias) + res.  So the stream is STORED as x / 2^k and a conv1 output as h / 2^j:
+# exact in real arithmetic, no launch and no pass more than without a plan, and no weight is rescaled (no fp16 weight
+# turns subnormal).  Scores, q / k / v, GroupNorm outputs, conv_out and the moments sit behind a normalisation and keep
+# their scale.  Results under a plan with k > 0 are NOT bit-identical to those without: small stored values enter the
+# fp16 subnormals (DESIGN.md (c), "fp16 range of the VAE").
+# ---------------------------------------------------------------------------------------------------------------------
+Site = collections.namedtuple("Site", "kind key name")
+Site.__doc__ = """One fp16 tensor the blocks store.  kind "stream": the residual stream behind module `name`, key = the
+segment it belongs to; "inner": the conv1 output of resnet `key`; "free": the attention's `a` (behind a softmax: it carries
+no scale and is probed for non-finite values only)."""
+
+
+def stream_layout(keys, part):
+    """The run order of the `part` ("decoder" | "encoder") of an AutoencoderKL, read off the state dict's keys:
+    [(kind, name)] with kind "conv_in", "res" (identity residual), "res_sc" (conv_shortcut), "attn" or "sampler"."""
+    keys = set(keys)
+
+    def count(prefix):
+        return 1 + max(int(m.group(1)) for k in keys for m in [re.match(re.escape(prefix) + r"\.(\d+)\.", k)] if m)
+
+    def res(n):
+        return ("res_sc" if f"{n}.conv_shortcut.weight" in keys else "res", n)
+
+    mid = [res(f"{part}.mid_block.resnets.0"), ("attn", f"{part}.mid_block.attentions.0"), res(f"{part}.mid_block.resnets.1")]
+    prefix, sampler = (f"{part}.up_blocks", "upsamplers") if part == "decoder" else (f"{part}.down_blocks", "downsamplers")
+    blocks = []
+    for i in range(count(prefix)):
+        blocks += [res(f"{prefix}.{i}.resnets.{j}") for j in range(count(f"{prefix}.{i}.resnets"))]
+        s = f"{prefix}.{i}.{sampler}.0.conv"
+        if f"{s}.weight" in keys:
+            blocks.append(("sampler", s))
+    return [("conv_in", f"{part}.conv_in")] + (mid + blocks if part == "decoder" else blocks + mid)
+
+
+class RangePlan:
+    """Integer exponents (powers of two only) for the tensors of a VAE that can grow: one per stream SEGMENT (the stream
+    is stored as x / 2^k) and one per resnet (`inner`: its conv1 output is stored as h / 2^j).  A segment starts at
+    conv_in's output, at the output of every up / down-sampler convolution and at the output of every resnet with a
+    conv_shortcut, and carries that module's name; resnets with an identity residual and the attention stay in their
+    input's segment.  Names are AutoencoderKL's, so one plan serves the decoder and the encoder; a name the plan does
+    not list gets `default`."""
+    MAX_EXPONENT = 24        # eps * 2^-48 is still a normal fp32 number for every eps a VAE uses
+
+    def __init__(self, segments=None, inner=None, default=0):
+        self.segments, self.inner, self.default = dict(segments or {}), dict(inner or {}), default
+        for k in [default, *self.segments.values(), *self.inner.values()]:
+            if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= self.MAX_EXPONENT:
+                raise ValueError(f"a range exponent is an integer in [0, {self.MAX_EXPONENT}], got {k!r}")
+
+    @classmethod
+    def uniform(cls, k):
+        return cls(default=k)
+
+    @staticmethod
+    def exponent(peak, headroom_bits=4):
+        """max(0, ceil(log2(peak / 2^(16 - headroom_bits)))): the smallest exponent that stores `peak` at or below
+        2^(16 - headroom_bits).  Exact (frexp, not a rounded logarithm)."""
+        peak = float(peak)
+        if not 0.0 <= peak < math.inf:
+            raise ValueError(f"a peak is a finite magnitude, got {peak}")
+        if peak == 0.0:
+            return 0
+        m, e = math.frexp(peak)                      # peak = m 2^e with 0.5 <= m < 1
+        return max(0, (e - 1 if m == 0.5 else e) - (16 - int(headroom_bits)))
+
+    @classmethod
+    def from_peaks(cls, peaks, headroom_bits=4):
+        """peaks: {Site: largest TRUE magnitude seen there} -> the plan whose stored peaks are <= 2^(16 - headroom_bits)
+        for these inputs (2^12 by default: 16x room below 65504 for hotter ones): per segment the maximum over its
+        stream sites of `exponent(peak)`, the same per resnet for `inner`.  A pure host function."""
+        seg, inner = {}, {}
+        for site, peak in peaks.items():
+            to = seg if site.kind == "stream" else inner if site.kind == "inner" else None
+            if to is not None:
+                to[site.key] = max(to.get(site.key, 0), cls.exponent(peak, headroom_bits))
+        return cls(seg, inner)
+
+    def segment(self, name):
+        return self.segments.get(name, self.default)
+
+    def resnet(self, name):
+        return self.inner.get(name, self.default)
+
+    def is_identity(self):
+        return not (self.default or any(self.segments.values()) or any(self.inner.values()))
+
+    # the three rules every launch under a plan follows
+    @staticmethod
+    def alpha_out(k_out):
+        """GEMM that reads a GroupNorm output (unscaled) and writes a tensor stored at exponent k_out: alpha."""
+        return 2.0 ** -k_out
+
+    @staticmethod
+    def carry(k_in, k_out):
+        """GEMM that reads a tensor stored at k_in and writes one stored at k_out (shortcut, sampler):
+        (alpha, factor of the fp32 bias) = (2^(k_in - k_out), 2^-k_in), since alpha * (W x / 2^k_in + b / 2^k_in)."""
+        return 2.0 ** (k_in - k_out), 2.0 ** -k_in
+
+    @staticmethod
+    def eps_scale(k):
+        """GroupNorm that reads a tensor stored at exponent k: the factor of its eps."""
+        return 2.0 ** (-2 * k)
+
+    def ops(self, layout):
+        """The scales of every op of `layout` (stream_layout), by module name — all a forward pass needs of the plan:
+          conv_in   k_out, alpha
+          res(_sc)  k_in, k_out, j, eps1 (factor of norm1's eps), a1 (conv1's alpha), eps2, a2 (conv2's alpha),
+                    sc = (alpha, bias factor) of the conv_shortcut | None
+          attn      k, eps (factor), a_out (to_out's alpha)
+          sampler   k_in, k_out, alpha, bias (factor)
+        and under "norm_out" the eps factor of conv_norm_out.  Each record names its segment(s) and its Sites."""
+        out, seg, k = {}, None, 0
+        for kind, name in layout:
+            rec = types.SimpleNamespace(kind=kind, name=name, k_in=k, seg_in=seg)
+            if kind in ("conv_in", "sampler", "res_sc"):
+                seg, k = name, self.segment(name)
+            rec.seg_out, rec.k_out, rec.site = seg, k, Site("stream", seg, name)
+            if kind == "conv_in":
+                rec.alpha = self.alpha_out(k)
+            elif kind == "sampler":
+                rec.alpha, rec.bias = self.carry(rec.k_in, k)
+            elif kind == "attn":
+                rec.k, rec.eps, rec.a_out, rec.site_a = k, self.eps_scale(k), self.alpha_out(k), Site("free", name, name + ".a")
+            else:
+                rec.j = self.resnet(name)
+                rec.eps1, rec.a1, rec.eps2, rec.a2 = self.eps_scale(rec.k_in), self.alpha_out(rec.j), self.eps_scale(rec.j), self.alpha_out(k)
+                rec.sc = self.carry(rec.k_in, k) if kind == "res_sc" else None
+                rec.site_inner = Site("inner", name, name + ".conv1")
+            out[name] = rec
+        out["norm_out"] = types.SimpleNamespace(kind="norm_out", k=k, eps=self.eps_scale(k))
+        return out
+
+    def __eq__(self, other):
+        return isinstance(other, RangePlan) and (self.segments, self.inner, self.default) == (other.segments, other.inner, other.default)
+
+    def __repr__(self):
+        return f"RangePlan(segments={self.segments}, inner={self.inner}, default={self.default})"
+
+
+def sites_of(layout):
+    """Every Site of `layout`, in run order (what calibrate_ranges probes)."""
+    out = []
+    for rec in list(RangePlan().ops(layout).values())[:-1]:
+        out += [s for s in (getattr(rec, "site_inner", None), getattr(rec, "site_a", None), rec.site) if s is not None]
+    return out
+
+
+_NO_PLAN = RangePlan()
+# what _Blocks._res / _attn run under when a caller hands them no record: no scale, nothing probed
+_RES_1 = types.SimpleNamespace(eps1=1.0, a1=1.0, eps2=1.0, a2=1.0, sc=None, sc_bias=None, site=None, site_inner=None)
+_ATTN_1 = types.SimpleNamespace(eps=1.0, a_out=1.0, site=None, site_a=None)
 
 
 class _Pack:
@@ -95,17 +256,58 @@ class _Blocks:
         self.ops = ops
         self.dev = torch.device(device)
         self.groups, self.eps = groups, eps
+        self._probe = None                   # calibration only (probe_ranges): called with (Site, stored tensor)
 
-    def _res(self, p, x, B, H, W):
+    def _plan(self, pk, part, ranges):
+        """The scale records of `ranges` (None: no plan) for this half, with the fp32 biases of the GEMMs that read a
+        scaled tensor (shortcuts, samplers) multiplied by their factor; a factor of one keeps the packed bias itself."""
+        self.ranges = _NO_PLAN if ranges is None else ranges
+        if not isinstance(self.ranges, RangePlan):
+            raise TypeError(f"ranges is a vae.RangePlan or None, got {type(ranges).__name__}")
+        self.layout = stream_layout(pk.sd, part)
+        starts = {n for k, n in self.layout if k in ("conv_in", "sampler", "res_sc")}
+        resnets = {n for k, n in self.layout if k in ("res", "res_sc")}
+        for what, names, known in (("segment", self.ranges.segments, starts), ("resnet", self.ranges.inner, resnets)):
+            for n in names:                  # a name of the other half is that half's business; a misspelt one of ours is not
+                if n.startswith(part + ".") and n not in known:
+                    raise ValueError(f"the range plan names {n}, which is no {what} of this {part}")
+        self.sites = sites_of(self.layout)
+        self.rs = self.ranges.ops(self.layout)
+        for rec in self.rs.values():
+            if rec.kind in ("res", "res_sc"):
+                rec.sc_bias = None
+                if rec.sc is not None and rec.sc[1] != 1.0:
+                    rec.sc_bias = pk.f32(pk.sd[f"{rec.name}.conv_shortcut.bias"] * rec.sc[1])
+            elif rec.kind == "sampler":
+                rec.bias_t = pk.f32(pk.sd[f"{rec.name}.bias"] * rec.bias) if rec.bias != 1.0 else None
+
+    def _see(self, site, t):
+        if self._probe is not None and site is not None:
+            self._probe(site, t)
+        return t
+
+    def _res(self, p, x, B, H, W, r=_RES_1):
+        """r: the resnet's record of RangePlan.ops — x arrives as x / 2^k_in, conv1's output is stored as h / 2^j, the
+        result leaves as (shortcut(x) + h) / 2^k_out."""
         ops = self.ops
         HW = H * W
-        h = ops.groupnorm(x, B, HW, self.groups, self.eps, p["n1"][0], p["n1"][1], True)
-        h = ops.conv3x3(h, p["c1"][0], B, H, W, bias=p["c1"][1])
-        h = ops.groupnorm(h, B, HW, self.groups, self.eps, p["n2"][0], p["n2"][1], True)
-        sc = x if p["sc"] is None else ops.linear(x, p["sc"][0], p["sc"][1])
-        return ops.conv3x3(h, p["c2"][0], B, H, W, bias=p["c2"][1], res=sc)
+        h = ops.groupnorm(x, B, HW, self.groups, self.eps * r.eps1, p["n1"][0], p["n1"][1], True)
+        h = self._see(r.site_inner, ops.conv3x3(h, p["c1"][0], B, H, W, bias=p["c1"][1], alpha=r.a1))
+        h = ops.groupnorm(h, B, HW, self.groups, self.eps * r.eps2, p["n2"][0], p["n2"][1], True)
+        if p["sc"] is None:
+            sc = x
+        elif r.sc is None:
+            sc = ops.linear(x, p["sc"][0], p["sc"][1])
+        else:
+            sc = ops.linear(x, p["sc"][0], p["sc"][1] if r.sc_bias is None else r.sc_bias, alpha=r.sc[0])
+        return self._see(r.site, ops.conv3x3(h, p["c2"][0], B, H, W, bias=p["c2"][1], res=sc, alpha=r.a2))
 
-    def _attn(self, p, x, B, H, W):
+    def _sampler(self, c, x, B, H, W, r, ups):
+        """The 3x3 convolution of an up / down-sampler: reads the stream at k_in, starts the segment stored at k_out."""
+        return self._see(r.site, self.ops.conv3x3(x, c[0], B, H, W, bias=c[1] if r.bias_t is None else r.bias_t, ups=ups,
+                                                  alpha=r.alpha))
+
+    def _attn(self, p, x, B, H, W, r=_ATTN_1):
         """Single-head attention over the H*W positions at width C (512): the head is wider than the flash kernels'
         160, so the batch runs as three BATCHED GEMM launches + one row softmax:
             scores[b] = q[b] k[b]^T      ->  P = softmax(scores)      (q, k carry C^-1/4 each)
@@ -115,7 +317,7 @@ class _Blocks:
         S = H * W
         C = x.shape[1]
         F16 = torch.float16
-        n = ops.groupnorm(x, B, S, self.groups, self.eps, p["n"][0], p["n"][1], False)
+        n = ops.groupnorm(x, B, S, self.groups, self.eps * r.eps, p["n"][0], p["n"][1], False)
         qk = ops.linear(n, p["qk"][0], p["qk"][1])                                  # [B*S, 2C]
         sc = torch.empty((B * S, S), device=self.dev, dtype=F16)
         ops.gemm_launch(ops.gemm_desc(qk, qk[:, C:], sc, S, S, C, lda0=2 * C, ldw=2 * C, ldc=S, nb_o=B,
@@ -127,19 +329,22 @@ class _Blocks:
         a = torch.empty((B * S, C), device=self.dev, dtype=F16)
         ops.gemm_launch(ops.gemm_desc(pr, vt, a, S, C, S, lda0=S, ldw=S, ldc=C, bias=p["vb"], nb_o=B,
                                       a_bs=(S * S, 0), w_bs=(C * S, 0), c_bs=(S * C, 0)))
-        return ops.linear(a, p["o"][0], p["o"][1], res=x)
+        # q, k, v, the scores and a sit behind the GroupNorm: only to_out meets the (scaled) stream again
+        return self._see(r.site, ops.linear(self._see(r.site_a, a), p["o"][0], p["o"][1], res=x, alpha=r.a_out))
 
 
 class HipVAEDecoder(_Blocks):
     """AutoencoderKL.decode (the `.sample` tensor) on the lgd_hip kernels: channels-last fp16, fp32 accumulate.
 
     HipVAEDecoder(state_dict | module with `aekl_state_dict()`, device).  The state dict is AutoencoderKL's (encoder keys are ignored);
-    the decoder's shape (channels per up block, resnets per block, which blocks upsample) is read off the keys."""
+    the decoder's shape (channels per up block, resnets per block, which blocks upsample) is read off the keys.
+    ranges: a RangePlan for a VAE whose activations leave the fp16 range (None = RangePlan.uniform(0): plain fp16)."""
 
-    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6):
+    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, ranges=None):
         super().__init__(device, groups, eps)
         pk = _Pack(_state_dict(source), self.dev, "decoder", "post_quant_conv")
         sd = pk.sd
+        self._plan(pk, "decoder", ranges)
         # post_quant_conv (1x1, 4 -> 4) folded into conv_in: conv_in(W1 z + b1) = conv_in'(z) + border-aware bias map
         # (the zero padding of conv_in does not carry b1, so the folded bias depends on which taps lie inside the image)
         w_in, self._b_in = sd["decoder.conv_in.weight"], sd["decoder.conv_in.bias"]
@@ -168,13 +373,15 @@ class HipVAEDecoder(_Blocks):
 
     def _bias_map(self, B, H, W):
         """conv_in bias + what post_quant_conv's bias contributes through the taps that lie inside the image:
-        fp16 [B*H*W, C] (residual operand of the conv_in GEMM)."""
+        fp16 [B*H*W, C] (residual operand of the conv_in GEMM); under a range plan the map of the stream's first segment,
+        scaled in fp32 and rounded once."""
         key = (B, H, W)
         if key not in self._bias_maps:
             vy, vx = torch.ones(3, H), torch.ones(3, W)
             vy[0, 0] = vx[0, 0] = 0          # tap row ky = 0 reads y - 1: outside at y = 0
             vy[2, H - 1] = vx[2, W - 1] = 0
             m = torch.einsum("okl,ky,lx->yxo", self._tap_bias, vy, vx) + self._b_in          # [H, W, C]
+            m = m * self.rs["decoder.conv_in"].alpha
             self._bias_maps = {key: m.reshape(1, H * W, -1).expand(B, -1, -1).reshape(B * H * W, -1)
                                .to(self.dev, torch.float16).contiguous()}
         return self._bias_maps[key]
@@ -185,24 +392,25 @@ class HipVAEDecoder(_Blocks):
         attention runs over all Hl*Wl positions with a materialised fp16 score matrix of (Hl*Wl)^2 elements per image:
         32 MB at 64 x 64, 512 MB at the 64 x 256 latent of a 512 x 2048 panorama.  That is accepted: it is one call per
         image."""
-        ops = self.ops
+        ops, rs = self.ops, self.rs
         z = z.to(self.dev, torch.float32).contiguous()
         B, _, H, W = z.shape
         lat8 = ops.nchw_to_nhwc8(z)
         h = torch.empty((B * H * W, self.c_mid), device=self.dev, dtype=torch.float16)
         ops.gemm_launch(ops.gemm_desc(lat8, self.conv_in_w8, h, B * H * W, self.c_mid, 72, c0=8, lda0=8, taps=9, hin=H,
                                       win=W, hout=H, wout=W, res=self._bias_map(B, H, W), ldr=self.c_mid,
-                                      ldc=self.c_mid, splits=1))
-        h = self._res(self.mid[0], h, B, H, W)
-        h = self._attn(self.attn, h, B, H, W)
-        h = self._res(self.mid[1], h, B, H, W)
-        for blk, up in self.ups:
-            for r in blk:
-                h = self._res(r, h, B, H, W)
+                                      ldc=self.c_mid, splits=1, alpha=rs["decoder.conv_in"].alpha))
+        self._see(rs["decoder.conv_in"].site, h)
+        h = self._res(self.mid[0], h, B, H, W, rs["decoder.mid_block.resnets.0"])
+        h = self._attn(self.attn, h, B, H, W, rs["decoder.mid_block.attentions.0"])
+        h = self._res(self.mid[1], h, B, H, W, rs["decoder.mid_block.resnets.1"])
+        for i, (blk, up) in enumerate(self.ups):
+            for j, r in enumerate(blk):
+                h = self._res(r, h, B, H, W, rs[f"decoder.up_blocks.{i}.resnets.{j}"])
             if up is not None:
-                h = ops.conv3x3(h, up[0], B, H, W, bias=up[1], ups=1)
+                h = self._sampler(up, h, B, H, W, rs[f"decoder.up_blocks.{i}.upsamplers.0.conv"], 1)
                 H, W = 2 * H, 2 * W
-        h = ops.groupnorm(h, B, H * W, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
+        h = ops.groupnorm(h, B, H * W, self.groups, self.eps * rs["norm_out"].eps, self.norm_out[0], self.norm_out[1], True)
         # conv_out (128 -> 3, padded to 4 channels) on the matrix cores as well: at 512 x 512 the one-wave-per-pixel
         # kernel took 1.7 ms per image, the implicit GEMM (N = 4 inside a 64-wide tile) a few tens of microseconds
         y = ops.conv3x3(h, self.conv_out[0], B, H, W, bias=self.conv_out[1])            # [B*H*W, 4] fp16
@@ -289,10 +497,11 @@ class HipVAEEncoder(_Blocks):
     position past the border reads the zero the asymmetric pad adds) — 4x the flops of three small convolutions,
     once per image."""
 
-    def __init__(self, state_dict, device, groups: int = 32, eps: float = 1e-6):
+    def __init__(self, state_dict, device, groups: int = 32, eps: float = 1e-6, ranges=None):
         super().__init__(device, groups, eps)
         pk = _Pack(state_dict, self.dev, "encoder", "quant_conv")
         sd = pk.sd
+        self._plan(pk, "encoder", ranges)
         self.conv_in = (pk.in8(sd["encoder.conv_in.weight"], "image channels"), pk.f32(sd["encoder.conv_in.bias"]))
         self.downs = pk.blocks("encoder.down_blocks", "downsamplers")
         self.mid = [pk.res("encoder.mid_block.resnets.0"), pk.res("encoder.mid_block.resnets.1")]
@@ -310,23 +519,25 @@ class HipVAEEncoder(_Blocks):
         """The encoder from its conv_in operand x8 (fp16 [B*H*H, 8]: value, rounding remainder, zeros; what
         lgd_nchw_to_nhwc8_f16 / lgd_image_u8_to_nhwc8_f16 write) -> fp16 moments [B*(H/8)^2, 2z], channels-last: z means,
         then z log-variances (unclamped) per latent pixel."""
-        ops = self.ops
+        ops, rs = self.ops, self.rs
         c0 = self.conv_in[0].shape[0]
         h = torch.empty((B * H * H, c0), device=self.dev, dtype=torch.float16)
         ops.gemm_launch(ops.gemm_desc(x8, self.conv_in[0], h, B * H * H, c0, 72, c0=8, lda0=8, taps=9,
-                                      hin=H, win=H, hout=H, wout=H, bias=self.conv_in[1], ldc=c0, splits=1))
-        for blk, down in self.downs:
-            for r in blk:
-                h = self._res(r, h, B, H, H)
+                                      hin=H, win=H, hout=H, wout=H, bias=self.conv_in[1], ldc=c0, splits=1,
+                                      alpha=rs["encoder.conv_in"].alpha))
+        self._see(rs["encoder.conv_in"].site, h)
+        for i, (blk, down) in enumerate(self.downs):
+            for j, r in enumerate(blk):
+                h = self._res(r, h, B, H, H, rs[f"encoder.down_blocks.{i}.resnets.{j}"])
             if down is not None:
-                full = ops.conv3x3(h, down[0], B, H, H, bias=down[1])
+                full = self._sampler(down, h, B, H, H, rs[f"encoder.down_blocks.{i}.downsamplers.0.conv"], False)
                 C = full.shape[1]
                 h = full.view(B, H, H, C)[:, 1::2, 1::2].reshape(B * (H // 2) * (H // 2), C).contiguous()
                 H //= 2
-        h = self._res(self.mid[0], h, B, H, H)
-        h = self._attn(self.attn, h, B, H, H)
-        h = self._res(self.mid[1], h, B, H, H)
-        h = ops.groupnorm(h, B, H * H, self.groups, self.eps, self.norm_out[0], self.norm_out[1], True)
+        h = self._res(self.mid[0], h, B, H, H, rs["encoder.mid_block.resnets.0"])
+        h = self._attn(self.attn, h, B, H, H, rs["encoder.mid_block.attentions.0"])
+        h = self._res(self.mid[1], h, B, H, H, rs["encoder.mid_block.resnets.1"])
+        h = ops.groupnorm(h, B, H * H, self.groups, self.eps * rs["norm_out"].eps, self.norm_out[0], self.norm_out[1], True)
         return ops.conv3x3(h, self.conv_out[0], B, H, H, bias=self.conv_out[1])       # [B*H*H, 2z] fp16
 
     @torch.no_grad()
@@ -391,9 +602,9 @@ class HipVAE(HipVAEDecoder):
     encoder is a HipVAEEncoder over the same AutoencoderKL state dict, built on first use (a generation-only run never
     packs it)."""
 
-    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215):
+    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215, ranges=None):
         sd = _state_dict(source)
-        super().__init__(sd, device, groups, eps)
+        super().__init__(sd, device, groups, eps, ranges=ranges)
         self._encoder_sd = {k: v for k, v in sd.items() if k.startswith(("encoder.", "quant_conv."))}
         self._encoder = None
         self.config = _Config(scaling_factor=scaling_factor)
@@ -403,7 +614,8 @@ class HipVAE(HipVAEDecoder):
         if self._encoder is None:
             if "encoder.conv_in.weight" not in self._encoder_sd:
                 raise RuntimeError("this VAE was built from a state dict without encoder weights: it cannot encode")
-            self._encoder = HipVAEEncoder(self._encoder_sd, self.dev, self.groups, self.eps)
+            # (a plan names AutoencoderKL's modules: the encoder takes its half by name)
+            self._encoder = HipVAEEncoder(self._encoder_sd, self.dev, self.groups, self.eps, ranges=self.ranges)
             self._encoder_sd = None
         return self._encoder
 
@@ -426,3 +638,51 @@ class HipVAE(HipVAEDecoder):
             raise RuntimeError(f"square images with a side that is a multiple of 8 only (got {H} x {W})")
         m = enc.moments_nhwc(x8, B, H)
         return HipEncoderOutput(HipLatentDist(ops, m, (B, enc.n_moments // 2, H // 8, W // 8)))
+
+
+# The plan a VAE with config.force_upcast gets when its caller brings none: RangePlan.uniform(8).  True magnitudes up to
+# 65504 * 2^8 = 1.6e7 stay finite, and on the synthetic nets the scaling costs a few per cent of the fp16 rounding error
+# that is there anyway ("fp16 range of the VAE").  Whether 8 suffices for the real SDXL checkpoint is
+# UNMEASURED: no real checkpoint has been loaded.  calibrate_ranges is the answer for a user who has it.
+FORCE_UPCAST_EXPONENT = 8
+CALIBRATION_EXPONENT = 12        # true magnitudes up to 65504 * 2^12 = 2.7e8 stay finite while they are measured
+
+
+@torch.no_grad()
+def probe_ranges(source, device, ranges, latents=None, images=None):
+    """Runs the decoder on `latents` (B, z, H, W) and / or the encoder on `images` (B, 3, S, S in [-1, 1]) eagerly under
+    `ranges` and measures every fp16 tensor the blocks store — the stream behind each block, each conv1 output, the
+    attention's `a` — with lgd_range_f16: {Site: (largest finite STORED magnitude, number of non-finite elements)}.
+    The probes write into one device table; there is one download, at the end."""
+    from . import ops
+    sd, dev = _state_dict(source), torch.device(device)
+    halves = []
+    if latents is not None:
+        halves.append((HipVAEDecoder(sd, dev, ranges=ranges), "decode", latents))
+    if images is not None:
+        halves.append((HipVAEEncoder(sd, dev, ranges=ranges), "encode_moments", images))
+    if not halves:
+        raise ValueError("nothing to measure: pass latents for the decoder, images for the encoder, or both")
+    sites = [s for half, _, _ in halves for s in half.sites]
+    row = {s: i for i, s in enumerate(sites)}
+    table = torch.zeros((len(sites), 2), device=dev, dtype=torch.int32)
+    for half, run, x in halves:
+        half._probe = lambda site, t: ops.range_f16(t, table, row[site])
+        getattr(half, run)(x)
+    host = table.cpu()
+    peaks, bad = host.view(torch.float32)[:, 0].tolist(), (host[:, 1].to(torch.int64) & 0xffffffff).tolist()
+    return {s: (peaks[i], bad[i]) for s, i in row.items()}
+
+
+def calibrate_ranges(source, device, latents=None, images=None, headroom_bits=4) -> RangePlan:
+    """The plan for a VAE whose checkpoint is at hand: runs the given inputs once at RangePlan.uniform(12), takes the
+    peak of every stored tensor (probe_ranges) and returns RangePlan.from_peaks of the true magnitudes, peak * 2^12 —
+    stored peaks of these inputs then are <= 2^(16 - headroom_bits).  An eager, offline call: nothing of it runs inside
+    a product path.  Raises if a tensor is non-finite even at that exponent."""
+    k = CALIBRATION_EXPONENT
+    seen = probe_ranges(source, device, RangePlan.uniform(k), latents, images)
+    bad = [f"{s.name} ({n})" for s, (_, n) in seen.items() if n]
+    if bad:
+        raise RuntimeError(f"non-finite values at exponent {k}, no power-of-two range plan holds this VAE on these inputs: "
+                           + ", ".join(bad))
+    return RangePlan.from_peaks({s: p * 2.0 ** k for s, (p, _) in seen.items() if s.kind != "free"}, headroom_bits)
