@@ -712,6 +712,48 @@ int lgd_detect_nms_f32(int mode, const float* logits_or_scores, const float* box
                        int32_t* out_count, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Safety checker of the `sd` baseline (additive exports: LGD_ABI_VERSION stays 12; csrc/safety.hip) —
+ * generation/stable_diffusion_generate.py:14,44-49 builds StableDiffusionPipeline with its default checker, which blanks
+ * the images it flags.  The CLIP vision tower and `visual_projection` are the GEMM / LayerNorm / attention calls above;
+ * these two are what follows them.
+ * ------------------------------------------------------------------------------------------- */
+/* Tail of [ext, unpinned] diffusers 0.18.0 pipelines/stable_diffusion/safety_checker.py, StableDiffusionSafetyChecker
+ * .forward, restated here (diffusers itself was not available to this project; this text is the contract).  Per image,
+ * all in fp32 and in exactly this order:
+ *   n(x)  = x / max(|x|_2, 1e-12)                          (torch.nn.functional.normalize)
+ *   cos_j = n(e) . n(c_j)                                  for the n_special special-care rows, then the n_concepts rows
+ *   adj   = 0
+ *   special rows, ascending j:  s_j = (cos_j - w_j) + adj;  the row HITS iff fl32(s_j * 1000) > 0.5;  a hit sets
+ *                               adj = 0.01 for every LATER special row and for all concept rows (a sequential prefix:
+ *                               the hitting row itself and the rows before it keep adj = 0)
+ *   concept rows:               s_j = (cos_j - w_j) + adj,  the same hit test;  has_nsfw iff any concept row hits
+ * The hit test is the reference's `round(score, 3) > 0` of a numpy.float32 score (checked equal over 400 005 values,
+ * 200 000 of them within 2e-6 of the boundary 0.0005, under NumPy 2.2).  Under NumPy 1.x the reference's `cos - w + adj`
+ * is promoted to fp64: the two can differ only for a score within ~1e-6 of 0.0005.
+ * embeds: fp32 [B][ld_embeds], the `visual_projection` output (D columns read); special: fp32 [n_special][D] and
+ * special_w: fp32 [n_special] (`special_care_embeds`, `special_care_embeds_weights`; both may be NULL when n_special is
+ * 0); concepts: fp32 [n_concepts][D] and concept_w: fp32 [n_concepts] (`concept_embeds`, `concept_embeds_weights`) — the
+ * raw checkpoint tensors, normalised inside the kernel.  scores: fp32 [B][n_special + n_concepts], the unrounded s_j,
+ * special rows first; flags: int32 [B][2] = {has_nsfw, a special-care row hit}.  One wave per image, 16-byte loads along
+ * D, wave64 sums; no atomics, every output element is written once.
+ * LGD_ERR_ARG, before any runtime call: a NULL operand; B, D or n_concepts <= 0, n_special < 0; D % 4 or ld_embeds % 4
+ * != 0, ld_embeds < D; embeds, special or concepts not 16-byte aligned, any other operand not 4-byte aligned; scores or
+ * flags overlapping an input or each other.  LGD_ERR_UNSUPPORTED: D > 1024, n_special > 32, n_concepts > 64, B > 65535. */
+int lgd_safety_head_f32(const float* embeds, int64_t ld_embeds, const float* special, const float* special_w,
+                        int n_special, const float* concepts, const float* concept_w, int n_concepts, float* scores,
+                        int32_t* flags, int B, int D, void* stream);
+/* Zeroes the flagged images of a batch in place (what the checker does to `images[idx]`).  Image n is the image_bytes
+ * bytes at images + n * image_bytes and is zeroed iff flags[n * flag_stride] != 0 (int32; flag_stride in elements, e.g. 2
+ * for column 0 of lgd_safety_head_f32's flags).  A workgroup reads its image's flag first and returns when it is 0: an
+ * unflagged image is neither read nor written.  16-byte stores with byte stores for an unaligned head and tail: images
+ * and image_bytes need no alignment.  Nothing outside [images, images + N * image_bytes) is written.
+ * LGD_ERR_ARG, before any runtime call: images or flags NULL, image_bytes, flag_stride or N <= 0, flags not 4-byte
+ * aligned, flags inside the images.  LGD_ERR_UNSUPPORTED: N * image_bytes beyond int64, or more than 2^31 - 1
+ * workgroups (N * min(64, ceil(image_bytes / 16384))). */
+int lgd_blank_flagged_u8(uint8_t* images, int64_t image_bytes, const int32_t* flags, int64_t flag_stride, int N,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask refinement around the SAM network for a batch of (image, prompt) items (additive exports: LGD_ABI_VERSION stays
  * 12) — models/sam.py as generation/lmd_plus.py:122-130 and generation/lmd.py:124-149 call it, everything that follows
  * the model's logits and, for LMD, everything that precedes its point prompt, without a host read.

@@ -106,6 +106,8 @@ SIGNATURES = {
     "lgd_boxdiff_energy_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
     "lgd_owl_heads_f32": [_P, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgd_detect_nms_f32": [_I, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P],
+    "lgd_safety_head_f32": [_P, _L, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P],
+    "lgd_blank_flagged_u8": [_P, _L, _P, _L, _I, _P],
     "lgd_sam_mask_tail_f32": [_P, _P, _P, _P] + [_I] * 8 + [_D, _D] + [_P] * 6,
     "lgd_sam_attn_prompt_f32": [_P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P],
     "lgd_handoff_place": [_P, _P, _P] + [_I] * 6 + [_P, _P, _P],

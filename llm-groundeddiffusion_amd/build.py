@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblgd_hip.so")
 STAMP = OUT + ".stamp"
-SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "attn_w4.hip", "attn_bwd.hip", "misc.hip", "energy.hip", "boxdiff.hip", "sam.hip", "options.hip", "detect.hip", "sam_tail.hip", "handoff.hip", "resample.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "attn.hip", "attn_w4.hip", "attn_bwd.hip", "misc.hip", "energy.hip", "boxdiff.hip", "sam.hip", "options.hip", "detect.hip", "sam_tail.hip", "handoff.hip", "resample.hip", "safety.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-Wno-unused-value"]
 # Per-file extras.  The attention kernels run softmax VALU work on MFMA results every key tile: keep
@@ -25,7 +25,9 @@ EXTRA_FLAGS = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # the alignment offsets are Python's fp64 arithmetic, operation by operation
                "handoff.hip": ["-ffp-contract=off"],
                # Pillow's fp64 weights on the host and the fp32 output forms on the device, operation by operation
-               "resample.hip": ["-ffp-contract=off"]}
+               "resample.hip": ["-ffp-contract=off"],
+               # the checker's decision `(cos - w) + adj`, `* 1000`, `> 0.5` is numpy's fp32 arithmetic, operation by operation
+               "safety.hip": ["-ffp-contract=off"]}
 
 
 def _digest():

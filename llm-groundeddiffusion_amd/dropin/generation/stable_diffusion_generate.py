@@ -4,8 +4,11 @@
 the same key) run the pipeline's loop — classifier-free guidance and the checkpoint's own PNDMScheduler (PLMS,
 skip_prk_steps; lgd_amd.scheduler.PNDMScheduler.from_config) — through models.pipelines.generate's sampler.
 
-Not run: the pipeline's safety checker (a CLIP vision model that blanks images it flags).  Images are returned as the
-pipeline returns them with the checker switched off."""
+The pipeline's safety checker (a CLIP vision model that blanks the images it flags) runs when `models.model_dict` carries
+one (`models.load_sd(..., safety_checker=True)` or LGD_SAFETY_CHECKER=1; lgd_amd.safety.HipSafetyChecker, on the device
+between the VAE and the host copy): a flagged image comes back black, as from the reference, and the result says so in
+`nsfw_content_detected`.  Without one, the default, images are returned as the pipeline returns them with the checker
+switched off."""
 import torch
 from PIL import Image
 
@@ -44,7 +47,8 @@ def start_latents(seed, in_channels, h, w):
 
 
 def run(prompt, seed=100, extra_neg_prompt=""):
-    """stable_diffusion_generate.py:32-51 -> EasyDict(image=<PIL.Image>)."""
+    """stable_diffusion_generate.py:32-51 -> EasyDict(image=<PIL.Image>), with a checker in model_dict
+    EasyDict(image=<PIL.Image>, nsfw_content_detected=<bool>)."""
     md = models.model_dict
     print(f"prompt: {prompt}")
     text = models.encode_prompts(tokenizer=md.tokenizer, text_encoder=md.text_encoder, prompts=[prompt],
@@ -52,6 +56,11 @@ def run(prompt, seed=100, extra_neg_prompt=""):
     h, w = image_scale()
     scheduler = PNDMScheduler.from_config(md.scheduler)
     lat = start_latents(seed, md.unet.config.in_channels, h, w) * scheduler.init_noise_sigma
-    _, images = sd_generate_batch(md.sampler, [text.float()], lat, num_total_steps,
-                                  guidance_scale=generate_guidance_scale, scheduler=scheduler)
-    return EasyDict(image=Image.fromarray(images[0]))
+    checker = md.get("safety_checker")
+    if checker is None:
+        _, images = sd_generate_batch(md.sampler, [text.float()], lat, num_total_steps,
+                                      guidance_scale=generate_guidance_scale, scheduler=scheduler)
+        return EasyDict(image=Image.fromarray(images[0]))
+    _, images, flags = sd_generate_batch(md.sampler, [text.float()], lat, num_total_steps,
+                                         guidance_scale=generate_guidance_scale, scheduler=scheduler, safety_checker=checker)
+    return EasyDict(image=Image.fromarray(images[0]), nsfw_content_detected=bool(flags[0, 0]))

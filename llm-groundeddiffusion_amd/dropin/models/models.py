@@ -52,24 +52,45 @@ def build_model_dict(cfg, state_dict, vae=None, tokenizer=None, text_encoder=Non
     return md
 
 
-def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True, load_inverse_scheduler=False):
+def _with_checker(md, checker):
+    """model_dict entries of the `sd` baseline's safety checker: the HIP checker and the device processor it runs behind."""
+    md["safety_checker"], md["safety_processor"] = checker, checker.processor
+    return md
+
+
+def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True, load_inverse_scheduler=False,
+                   safety_checker=False):
     """Seeded random weights of the exact architecture (no checkpoints in the sandbox).  The VAE is make_hip_vae's decoder
-    with the encoder of the same state dict behind it (built when pipelines.encode first asks for it)."""
+    with the encoder of the same state dict behind it (built when pipelines.encode first asks for it).  safety_checker:
+    True puts a seeded checker of ViT-L/14 geometry with 2 layers (lgd_amd.safety.HipSafetyChecker.synthetic) and its
+    processor into model_dict, an instance built with that constructor is taken as it is; False (the default): none."""
+    from lgd_amd.safety import HipSafetyChecker
     from lgd_amd.vae import make_hip_vae_pair
+    if not isinstance(safety_checker, (bool, HipSafetyChecker)):
+        raise TypeError("safety_checker: True, False or a lgd_amd.safety.HipSafetyChecker")
     cfg = _weights.CONFIGS[name]
-    return build_model_dict(cfg, _weights.synth_state_dict(cfg, seed), vae=make_hip_vae_pair(device) if with_vae else None,
-                            device=device, load_inverse_scheduler=load_inverse_scheduler)
+    md = build_model_dict(cfg, _weights.synth_state_dict(cfg, seed), vae=make_hip_vae_pair(device) if with_vae else None,
+                          device=device, load_inverse_scheduler=load_inverse_scheduler)
+    if safety_checker is False:
+        return md
+    if safety_checker is True:
+        safety_checker = HipSafetyChecker.synthetic(seed=seed, device=device)
+    return _with_checker(md, safety_checker)
 
 
 def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_scheduler=False,
-            use_dpm_multistep_scheduler=False, scheduler_cls=None, vae_ranges=None):
+            use_dpm_multistep_scheduler=False, scheduler_cls=None, vae_ranges=None, safety_checker=False):
     """models/models.py:16-62.  Needs the Hugging Face checkpoint (diffusers + network/cache); the UNet
     state dict is repacked into the HIP engine's arenas, the CLIP text tower runs on the HIP kernels
     (lgd_amd.clip), the VAE's state dict is repacked for the HIP kernels (lgd_amd.vae.HipVAE: the decoder at once, the
     encoder when pipelines.encode first needs it; LGD_HF_VAE=1 in the environment keeps the Hugging Face module, for A/B
     checks against it).  load_inverse_scheduler (models/models.py:57-59): model_dict.inverse_scheduler for
     pipelines.invert.  vae_ranges: the range plan of a VAE whose config sets force_upcast (the SDXL VAE), by the rule
-    of generation.sdxl_refinement._vae_ranges: RangePlan.uniform(8) when none is given, none for an fp16-safe VAE."""
+    of generation.sdxl_refinement._vae_ranges: RangePlan.uniform(8) when none is given, none for an fp16-safe VAE.
+    safety_checker=True, or LGD_SAFETY_CHECKER=1 in the environment: the checkpoint's `safety_checker` and
+    `feature_extractor` subfolders are loaded and model_dict carries `safety_checker` (lgd_amd.safety.HipSafetyChecker)
+    and `safety_processor`; generation.stable_diffusion_generate.run then blanks what the checker flags, as the
+    reference's pipeline does.  The default runs no checker."""
     if not use_fp16:      # models/models.py:33-38: the reference then loads fp32 weights ("run final results in fp32")
         from generation._common import note_precision
         note_precision("models.load_sd", "use_fp16=False")
@@ -120,10 +141,18 @@ def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_s
         dec = HipVAE.from_state_dict(vae.state_dict(), torch_device,             # models/models.py:41 on the HIP kernels
                                      scaling_factor=getattr(vae.config, "scaling_factor", 0.18215),
                                      ranges=_vae_ranges(vae.config, vae_ranges, _os.environ))
-    return build_model_dict(cfg, {k: v.float() for k, v in hf.state_dict().items()}, vae=dec, tokenizer=tok,
-                            text_encoder=te, scheduler_config=sched_cfg,
-                            use_dpm_multistep_scheduler=use_dpm_multistep_scheduler,
-                            load_inverse_scheduler=load_inverse_scheduler)
+    md = build_model_dict(cfg, {k: v.float() for k, v in hf.state_dict().items()}, vae=dec, tokenizer=tok,
+                          text_encoder=te, scheduler_config=sched_cfg,
+                          use_dpm_multistep_scheduler=use_dpm_multistep_scheduler,
+                          load_inverse_scheduler=load_inverse_scheduler)
+    if safety_checker or _os.environ.get("LGD_SAFETY_CHECKER", "0") == "1":
+        from diffusers.pipelines.stable_diffusion.safety_checker import StableDiffusionSafetyChecker
+        from transformers import CLIPImageProcessor
+        from lgd_amd.safety import from_diffusers
+        _with_checker(md, from_diffusers(StableDiffusionSafetyChecker.from_pretrained(key, subfolder="safety_checker"),
+                                         torch_device,
+                                         CLIPImageProcessor.from_pretrained(key, subfolder="feature_extractor")))
+    return md
 
 
 def encode_prompts(tokenizer, text_encoder, prompts, negative_prompt="", return_full_only=False,

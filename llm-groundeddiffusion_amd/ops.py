@@ -1120,6 +1120,51 @@ def detect_nms(scores_or_logits, boxes, *, labels=None, counts=None, score_thres
 
 
 # ---------------------------------------------------------------------------------------------
+# safety checker of the `sd` baseline (csrc/safety.hip)
+# ---------------------------------------------------------------------------------------------
+def safety_head(embeds, special, special_w, concepts, concept_w, *, scores=None, flags=None):
+    """Tail of StableDiffusionSafetyChecker.forward (lgd_safety_head_f32).  embeds fp32 [B, >=D] (row stride = its
+    stride(0), D columns read), special fp32 [n_special, D] with special_w [n_special] (None, None: no special rows),
+    concepts fp32 [n_concepts, D] with concept_w [n_concepts] -> (scores fp32 [B, n_special + n_concepts], special rows
+    first; flags int32 [B, 2] = (has_nsfw, a special row hit))."""
+    if embeds.dim() != 2 or concepts.dim() != 2 or embeds.stride(1) != 1:
+        raise RuntimeError("safety_head: embeds [B, D] with unit column stride and concepts [n_concepts, D]")
+    if (special is None) != (special_w is None):
+        raise RuntimeError("safety_head: special and special_w go together")
+    B, D = embeds.shape[0], concepts.shape[1]
+    ns, nc = (0 if special is None else special.shape[0]), concepts.shape[0]
+    if embeds.dtype != F32 or embeds.shape[1] < D or (B > 1 and embeds.stride(0) < D):
+        raise RuntimeError(f"safety_head: embeds is fp32 with at least D = {D} columns per row")
+    dev = embeds.device
+    if scores is None:
+        scores = torch.empty((B, ns + nc), device=dev, dtype=F32)
+    if flags is None:
+        flags = torch.empty((B, 2), device=dev, dtype=torch.int32)
+    _operands("safety_head", ("special", special, F32, ns * D), ("special_w", special_w, F32, ns),
+              ("concepts", concepts, F32, nc * D), ("concept_w", concept_w, F32, nc),
+              ("scores", scores, F32, B * (ns + nc)), ("flags", flags, torch.int32, B * 2))
+    if len({t.device for t in (embeds, special, special_w, concepts, concept_w, scores, flags) if t is not None}) != 1:
+        raise RuntimeError("safety_head: operands on different devices")
+    _call("lgd_safety_head_f32", _p(embeds), embeds.stride(0) if B > 1 else max(embeds.stride(0), D), _p(special),
+          _p(special_w), ns, _p(concepts), _p(concept_w), nc, _p(scores), _p(flags), B, D, _stream())
+    return scores, flags
+
+
+def blank_flagged(images, flags):
+    """Zeroes image n of the contiguous uint8 batch `images` (N, ...) in place iff flags[n] != 0 (lgd_blank_flagged_u8).
+    flags: int32, one element per image at a constant stride, e.g. column 0 of safety_head's flags.  Returns images."""
+    if images.dtype != torch.uint8 or not images.is_contiguous() or images.dim() < 1 or images.numel() == 0:
+        raise RuntimeError("blank_flagged: images is a contiguous, non-empty uint8 batch")
+    N = images.shape[0]
+    if flags.dtype != torch.int32 or flags.dim() != 1 or flags.shape[0] != N or (N > 1 and flags.stride(0) < 1):
+        raise RuntimeError(f"blank_flagged: flags is an int32 vector of {N} elements (a strided view is fine)")
+    if flags.device != images.device:
+        raise RuntimeError("blank_flagged: operands on different devices")
+    _call("lgd_blank_flagged_u8", _p(images), images.numel() // N, _p(flags), flags.stride(0) if N > 1 else 1, N, _stream())
+    return images
+
+
+# ---------------------------------------------------------------------------------------------
 # mask refinement around the SAM network (csrc/sam_tail.hip)
 # ---------------------------------------------------------------------------------------------
 def sam_mask_tail(logits, iou, geom, target, grid, coarse, below_conf, below_iou, *, want_cand=True):

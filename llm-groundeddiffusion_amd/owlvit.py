@@ -174,27 +174,14 @@ class HipOwlViTDetector(vit.Tower):
     def encode_image(self, pixel_values):
         """pixel_values (B, 3, S, S) -> image_embeds fp16 [B*P, C]: [ext] OwlViTVisionTransformer.forward followed by
         OwlViTForObjectDetection.image_text_embedder's post_layernorm, class-token merge and layer_norm."""
-        cfg, g, d, P = self.cfg, self.grid, self.d, self.P
+        cfg, P = self.cfg, self.P
         B, Cin, Hh, Ww = pixel_values.shape
         if (Cin, Hh, Ww) != (cfg.num_channels, cfg.image_size, cfg.image_size):
             raise ValueError(f"Input image size ({Hh}*{Ww}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
-        ps, C, NH, eps = cfg.patch_size, cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
-        S = P + 1
-        emb = ops.linear(vit.patch_rows(pixel_values, g, ps, self.dev), self.patch, None,
-                         res=self.rep_rows("pos", self.pos, B))                        # [B*P, C] + position
-        x = torch.empty((B, S, C), device=self.dev, dtype=F16)
-        x[:, 0] = self.cls_pos.to(F16)
-        x[:, 1:] = emb.reshape(B, P, C)
-        x = ops.layernorm(x.reshape(B * S, C), self.pre_ln[0], self.pre_ln[1], eps)
-        view = (3 * C, S * 3 * C)
-
-        def attend(qkv):                                                                # [B*S, 3C]
-            o = torch.empty((B * S, C), device=self.dev, dtype=F16)
-            return ops.attn_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, NH, S, S, d, d ** -0.5, q_view=view, k_view=view,
-                                v_view=view)
-        for L in self.layers:
-            x = vit.block(x, L, eps, attend, "quick_gelu")
-        y = ops.layernorm(x, self.post_ln[0], self.post_ln[1], eps).reshape(B, S, C)
+        C, S = cfg.hidden_size, P + 1
+        eps = cfg.layer_norm_eps
+        y = vit.clip_vision_trunk(self, pixel_values, patch_size=cfg.patch_size, heads=cfg.num_attention_heads,
+                                  eps=eps).reshape(B, S, C)
         merged = (y[:, 1:].float() * y[:, :1].float()).to(F16).reshape(B * P, C).contiguous()
         return ops.layernorm(merged, self.merge_ln[0], self.merge_ln[1], eps)
 

@@ -473,7 +473,7 @@ def boxdiff_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, num
 
 
 def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=50, guidance_scale=7.5, scheduler=None,
-                      decode=True, save_all_latents=False):
+                      decode=True, save_all_latents=False, safety_checker=None):
     """Plain Stable Diffusion, the `sd` baseline (generation/stable_diffusion_generate.py -> StableDiffusionPipeline, whose
     denoising loop is models/pipelines.py:257-273): classifier-free guidance and the checkpoint's own sampler, by default
     PLMS (scheduler.PNDMScheduler.from_config of the sampler's scheduler; n steps = n + 1 UNet evaluations).  `scheduler`
@@ -483,7 +483,14 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor, already scaled
     by init_noise_sigma.  Returns (final latents (N,C,L,L), uint8 images (N,8L,8L,3) from sampler.decode or None), plus
     the per-image histories (E+1,1,C,L,L) with save_all_latents.  decode="device": the images stay on the GPU
-    (sampler.decode_device), the same bytes."""
+    (sampler.decode_device), the same bytes.
+
+    safety_checker: a safety.HipSafetyChecker runs StableDiffusionPipeline's default checker on the decoded images
+    (`check_device`, device to device): flagged images come back black, and its flags, int32 (N, 2) = (has_nsfw, a
+    special-care concept hit), are returned as one extra trailing element — on the device with decode="device", on the
+    host with decode=True.  None (the default): no checker runs and the return is as above."""
+    if safety_checker is not None and not decode:
+        raise ValueError("safety_checker checks decoded images: decode=True or decode=\"device\"")
     sch = PNDMScheduler.from_config(sampler.scheduler) if scheduler is None else scheduler
     starts = [latents[i:i + 1] for i in range(latents.shape[0])] if torch.is_tensor(latents) else list(latents)
     if len(starts) != len(texts):
@@ -492,10 +499,17 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     res = sampler.denoise_batch(jobs, num_inference_steps, guidance_scale=guidance_scale, scheduler=sch,
                                 save_all_latents=save_all_latents)
     lat = torch.cat([r["latents"] for r in res])
-    images = _decoded(sampler, lat, decode, len(jobs)) if decode else None
+    if safety_checker is None:
+        images = _decoded(sampler, lat, decode, len(jobs)) if decode else None
+        out = (lat, images)
+    else:
+        if isinstance(decode, str) and decode != "device":
+            raise ValueError(f"decode={decode!r}: True, False or \"device\"")
+        images, flags = safety_checker.check_device(sampler.decode_device(lat))
+        out = (lat, images, flags) if isinstance(decode, str) else (lat, images.cpu().numpy(), flags.cpu())
     if save_all_latents:
-        return lat, images, [r["latents_all"] for r in res]
-    return lat, images
+        return out[:2] + ([r["latents_all"] for r in res],) + out[2:]
+    return out
 
 
 def invert_batch(sampler: LMDSampler, texts, latents, num_inference_steps=50, guidance_scale=7.5, inverse_scheduler=None):

@@ -7,6 +7,8 @@ towers), the OWL-ViT vision tower (owlvit.py) and the SAM image encoder (sam.py)
                with residual -> LayerNorm -> fc1 -> activation -> fc2 with residual.  The field names are this module's;
                each tower maps its checkpoint's names when it loads.
   patch_rows   the unfolding of an image into the rows of the patch-embedding GEMM
+  clip_vision_trunk  the CLIP vision transformer both OWL-ViT's detector (owlvit.py) and the safety checker (safety.py)
+               run: patch GEMM, class token + position table, pre_layernorm, the layers, post_layernorm
   Tower        the `to` / `eval` call surface of an nn.Module user and the cache of tables repeated once per image
 """
 from collections import namedtuple
@@ -67,6 +69,40 @@ def patch_rows(pixel_values, grid, patch, dev):
     B, Cin = pixel_values.shape[:2]
     return (pixel_values.to(dev, F16).reshape(B, Cin, grid, patch, grid, patch).permute(0, 2, 4, 1, 3, 5)
             .reshape(B * grid * grid, Cin * patch * patch).contiguous())
+
+
+def clip_vision_trunk(tower, pixel_values, *, patch_size, heads, eps, pooled=False):
+    """[ext] transformers CLIPVisionTransformer / OwlViTVisionTransformer.forward up to and including post_layernorm.
+    pixel_values (B, Cin, g*patch_size, g*patch_size) -> fp16 [B*(P + 1), C], every token normalised; pooled=True ->
+    [B, C], the class token alone (CLIP's pooler_output: LayerNorm is per row, so the other rows are not computed).
+
+    `tower` (a Tower) holds what its loader made of the checkpoint: `patch` fp16 [C, K] (K may be zero-padded past
+    Cin*patch_size^2 to a multiple of 8: the rows are padded to match), `pos` fp16 [P, C], `cls_pos` fp32 [C] (class
+    embedding + position row 0), `pre_ln`, `post_ln`, `layers` (Layer, quick_gelu), `grid`, `dev`."""
+    g, dev = tower.grid, tower.dev
+    B = pixel_values.shape[0]
+    C = tower.patch.shape[0]
+    P, d = g * g, C // heads
+    S = P + 1
+    rows = patch_rows(pixel_values, g, patch_size, dev)
+    if rows.shape[1] != tower.patch.shape[1]:
+        rows = torch.nn.functional.pad(rows, (0, tower.patch.shape[1] - rows.shape[1]))
+    emb = ops.linear(rows, tower.patch, None, res=tower.rep_rows("pos", tower.pos, B))     # [B*P, C] + position
+    x = torch.empty((B, S, C), device=dev, dtype=F16)
+    x[:, 0] = tower.cls_pos.to(F16)
+    x[:, 1:] = emb.reshape(B, P, C)
+    x = ops.layernorm(x.reshape(B * S, C), tower.pre_ln[0], tower.pre_ln[1], eps)
+    view = (3 * C, S * 3 * C)
+
+    def attend(qkv):                                                                    # [B*S, 3C]
+        o = torch.empty((B * S, C), device=dev, dtype=F16)
+        return ops.attn_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B, heads, S, S, d, d ** -0.5, q_view=view, k_view=view,
+                            v_view=view)
+    for L in tower.layers:
+        x = block(x, L, eps, attend, "quick_gelu")
+    if pooled:
+        x = x.reshape(B, S, C)[:, 0].contiguous()
+    return ops.layernorm(x, tower.post_ln[0], tower.post_ln[1], eps)
 
 
 class Tower:
