@@ -29,7 +29,7 @@ import torch
 from . import ops
 from ._lib import EPI_GEGLU, PAIR_DUP, PAIR_HALF
 from .weights import UNetConfig, unet_blocks
-from .weightstore import WeightStore
+from .weightstore import GRAD_PLAN_LAST_UP_BLOCK, WeightStore
 
 F16, F32 = torch.float16, torch.float32
 N_OBJ_TOKENS = 30  # max_objs of pipelines.py:289
@@ -66,8 +66,12 @@ class PairMode:
 
 
 class Op:
-    def __init__(self, fwd, make_bwd=None, gouts=(), passthrough=None):
+    def __init__(self, fwd, make_bwd=None, gouts=(), passthrough=None, meta=None):
         self.fwd = fwd
+        # plain-data description of the op (kind, input / output Acts with their views, side outputs, scratch, parameter
+        # names of the state dict, geometry, the inputs that are constants of a run).  Written when the plan is built and
+        # read by tests only (tests/unet_plan_cases.py): no launch closure looks at it
+        self.meta = meta
         self.make_bwd = make_bwd    # (acc flags for gouts) -> callable
         self.gouts = list(gouts)    # Acts whose .g this op's backward writes, in write order
         self.acc = None
@@ -130,9 +134,24 @@ class Plan:
     def _act(self, rows, C):
         return Act(self._new(rows, C))
 
-    def _add(self, fwd, make_bwd=None, gouts=(), passthrough=None):
+    def _add(self, fwd, make_bwd=None, gouts=(), passthrough=None, meta=None):
         self.ops.append(Op(fwd, make_bwd if self.grad else None, gouts if self.grad else (),
-                           passthrough if self.grad else None))
+                           passthrough if self.grad else None, meta))
+
+    @staticmethod
+    def _sd_names(name: str) -> List[str]:
+        """State-dict names of the matrices behind an engine weight name (weightstore fuses to_q | to_k | to_v)."""
+        if name.endswith(".qkv"):
+            return [f"{name[:-4]}.{p}.weight" for p in ("to_q", "to_k", "to_v")]
+        return [f"{name}.weight"]
+
+    @staticmethod
+    def _gate_name(name: str) -> Optional[str]:
+        """State-dict name of the fuser gate (alpha = its tanh) on a linear layer, or None."""
+        for tail, gate in ((".fuser.attn.to_out.0", "alpha_attn"), (".fuser.ff.net.2", "alpha_dense")):
+            if name.endswith(tail):
+                return f"{name[:-len(tail)]}.fuser.{gate}"
+        return None
 
     def _ws(self, n_floats):
         return self.eng.workspace(n_floats)
@@ -175,8 +194,12 @@ class Plan:
         # q/k/v/out projections count towards the "attention path" of the benchmark's roofline report
         tag = "attn_path" if any(t in name for t in (".attn1.", ".attn2.", ".fuser.attn.")) else None
         fwd = lambda: ops.gemm_launch(d, tag)
+        meta = dict(kind="linear", name=name, ins=[x], res=res, out=y, rows=M, desc=d, alpha=alpha, geglu_epilogue=geglu,
+                    params=dict(weight=self._sd_names(name), bias=f"{name}.bias" if bias else None,
+                                geglu_rows=name.endswith(".net.0.proj"),
+                                alpha=self._gate_name(name)))
         if not (self.grad and bwd):
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return y
         assert not geglu, "grad plans keep the GEGLU pre-activation (see ff())"
         Wt = self.eng.w.h[f"{name}.wt"]
@@ -197,7 +220,7 @@ class Plan:
                 elif not aliased:
                     ops.copy_(res.g, y.g)
             return run
-        self._add(fwd, make_bwd, gouts, passthrough=(res, y) if res is not None else None)
+        self._add(fwd, make_bwd, gouts, passthrough=(res, y) if res is not None else None, meta=meta)
         return y
 
     def conv(self, x: Act, name: str, H: int, *, x1: Optional[Act] = None, res: Optional[Act] = None,
@@ -233,8 +256,11 @@ class Plan:
                               ldr=res.C if res else 0, ldc=Cout)
             self._pair_op([x, x1, res], y, half, d)
             fwd = lambda: ops.gemm_launch(d)
+        meta = dict(kind="conv", name=name, ins=[x] + ([x1] if x1 else []), res=res, out=y, H=H, stride=stride, ups=bool(ups),
+                    temb_off=temb_off, scratch=[], params=dict(weight=[f"{name}.weight"], bias=f"{name}.bias"),
+                    const=["temb"] if temb_off is not None else [])
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return y
         Wd = self.eng.w.h[f"{name}.wd"]          # [Cin][9*Cout]
         gouts = [x] + ([x1] if x1 else []) + ([res] if res else [])
@@ -258,6 +284,7 @@ class Plan:
             else:
                 # nearest-2x upsample folded in forward: dgrad at 2H x 2H, then 2x2 sum
                 tmp = self._new(B * Hl * Hl, c0)
+                meta["scratch"].append(tmp)
                 dd = ops.gemm_desc(y.g, Wd, tmp, B * Hl * Hl, c0, Kd, c0=Cout, lda0=Cout, taps=9,
                                    hin=Hl, win=Hl, hout=Hl, wout=Hl, ldc=c0)
                 assert not acc[0]
@@ -269,7 +296,7 @@ class Plan:
                 elif res.g.data_ptr() != y.g.data_ptr():
                     runs.append(lambda: ops.copy_(res.g, y.g))
             return lambda: [r() for r in runs]
-        self._add(fwd, make_bwd, gouts, passthrough=(res, y) if res is not None else None)
+        self._add(fwd, make_bwd, gouts, passthrough=(res, y) if res is not None else None, meta=meta)
         return y
 
     def shortcut(self, x: Act, x1: Optional[Act], name: str) -> Act:
@@ -284,8 +311,10 @@ class Plan:
         d = ops.gemm_desc(x.t, W, y.t, M, Cout, K, a1=x1.t if x1 else None, c0=c0, c1=c1, lda0=c0,
                           lda1=c1, bias=b, ldc=Cout)
         fwd = lambda: ops.gemm_launch(d)
+        meta = dict(kind="shortcut", name=name, ins=[x] + ([x1] if x1 else []), out=y, desc=d,
+                    params=dict(weight=[f"{name}.weight"], bias=f"{name}.bias"))
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return y
         Wt = self.eng.w.h[f"{name}.wt"]          # [Cin][Cout]
         gouts = [x] + ([x1] if x1 else [])
@@ -297,7 +326,7 @@ class Plan:
                                    res=src.g if acc[i] else None, ldr=cn)
                 runs.append(lambda dd=dd: ops.gemm_launch(dd))
             return lambda: [r() for r in runs]
-        self._add(fwd, make_bwd, gouts)
+        self._add(fwd, make_bwd, gouts, meta=meta)
         return y
 
     # ---- norms -----------------------------------------------------------------------------
@@ -316,8 +345,11 @@ class Plan:
             fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, pair=pm.mode)
         else:
             fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, stats=stats)
+        meta = dict(kind="groupnorm", name=name, ins=[x] + ([x1] if x1 else []), out=y, HW=HW, G=G, eps=eps, silu=silu,
+                    side=dict(part=part, stats=stats), scratch=[part],
+                    params=dict(weight=f"{name}.weight", bias=f"{name}.bias"))
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return y
         gouts = [x] + ([x1] if x1 else [])
 
@@ -327,7 +359,7 @@ class Plan:
                 assert acc[0] == acc[1], "mixed accumulate modes on a concat GroupNorm"
             return lambda: ops.groupnorm_bwd(y.g, x.t, B, HW, G, gm, bt, silu, stats, x1=xt1, gx0=x.g,
                                              gx1=x1.g if x1 else None, part=part, accumulate=a)
-        self._add(fwd, make_bwd, gouts)
+        self._add(fwd, make_bwd, gouts, meta=meta)
         return y
 
     def layernorm(self, x: Act, name: str, *, out_t=None, ldy=None, S=None, y_bs=0, half=False) -> Act:
@@ -348,15 +380,18 @@ class Plan:
             pm.on_dup = lambda: self._need_full(x)
         fwd = lambda: ops.layernorm(x.t, gm, bt, out=y.t, ldy=ldy or C, stats=stats, rows=x.rows,
                                     rows_per_batch=rpb, x_bs=x_bs, y_bs=y_bs, pair=PAIR_HALF if y.pair is not None else 0)
+        meta = dict(kind="layernorm", name=name, ins=[x], out=y, rows=x.rows, ldy=ldy or C, rows_per_batch=rpb, x_bs=x_bs,
+                    y_bs=y_bs, S=S, eps=1e-5, side=dict(stats=stats), params=dict(weight=f"{name}.weight", bias=f"{name}.bias"),
+                    const=["grounding_rows"] if out_t is not None else [])
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return y
 
         def make_bwd(acc):
             return lambda: ops.layernorm_bwd(y.g, x.t, gm, stats, gx=x.g, rows=x.rows, ldgy=ldy or C,
                                              rows_per_batch=rpb, gy_bs=y_bs, x_bs=x_bs, gx_bs=x_bs,
                                              accumulate=acc[0])
-        self._add(fwd, make_bwd, [x])
+        self._add(fwd, make_bwd, [x], meta=meta)
         return y
 
     def ln_linear(self, x: Act, norm: str, name: str, *, geglu=False, half=False) -> Act:
@@ -383,7 +418,11 @@ class Plan:
         xt = x.t
         # the statistics are read by this GEMM only: in pair mode it reads those of the first M / 2 rows
         sp = PAIR_HALF if self._pair_op([x], y, half, d) is not None else 0
-        self._add(lambda: (ops.layernorm_stats(xt, K, stats=stats, rows=M, pair=sp), ops.gemm_launch(d, tag)))
+        self._add(lambda: (ops.layernorm_stats(xt, K, stats=stats, rows=M, pair=sp), ops.gemm_launch(d, tag)),
+                  meta=dict(kind="ln_linear", name=name, norm=norm, ins=[x], out=y, rows=M, desc=d, geglu_epilogue=geglu,
+                            side=dict(stats=stats), params=dict(weight=self._sd_names(name), bias=f"{name}.bias" if has_b else None,
+                                                                norm_weight=f"{norm}.weight", norm_bias=f"{norm}.bias",
+                                                                geglu_rows=name.endswith(".net.0.proj"))))
         return y
 
     # ---- attention -------------------------------------------------------------------------
@@ -402,13 +441,16 @@ class Plan:
         pm = self._pair_op([qkv], o, half)
         fwd = lambda: ops.attn_fwd(qt, kt, vt, o.t, B, heads, S, Sk, d, scale, lse=lse,
                                    q_view=view, k_view=view, v_view=view, pair=pm.mode if pm is not None else 0)
+        meta = dict(kind="self_attn", ins=[qkv], out=o, heads=heads, S=S, Sk=Sk, d=d, scale=scale, view=view,
+                    side=dict(lse=lse), scratch=[], sk_grad=S, const=["grounding_rows"] if Sk > S else [])
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return o
 
         def make_bwd(acc):
             assert not acc[0]
             delta = self._alloc((B, heads, S))
+            meta["scratch"].append(delta)
             g = qkv.g
             gq, gk, gv = g, g[:, C:], g[:, 2 * C:]
             pad = Sk > S
@@ -426,7 +468,7 @@ class Plan:
                 ops.attn_bwd(qt, kt, vt, o.t, o.g, lse, delta, gq, gk, gv, B, heads, S, Sk, d, scale,
                              q_view=view, k_view=view, v_view=view, gq_view=view, gk_view=view, gv_view=view, sk_grad=S)
             return run
-        self._add(fwd, make_bwd, [qkv])
+        self._add(fwd, make_bwd, [qkv], meta=meta)
         return o
 
     def cross_attn(self, q: Act, key: Tuple, layer_name: str, heads: int, S: int, last: bool) -> Optional[Act]:
@@ -453,8 +495,12 @@ class Plan:
         def fwd():
             ops.cross_attn_fwd(q.t, kt, vt, o.t, B, heads, S, T, d, scale, probs=probs,
                                k_view=k_view, v_view=k_view)
+        meta = dict(kind="cross_attn", ins=[q], out=o, key=key, layer=layer_name, heads=heads, S=S, Sk=T, d=d, scale=scale,
+                    last=last, kv=kv_t, k_view=k_view, side=dict(maps=probs), gmap=self.gmaps.get(key), const=["text_kv"],
+                    params=dict(kv=[f"{layer_name.partition('@')[0]}.transformer_blocks.{layer_name.partition('@')[2] or 0}"
+                                    f".attn2.{p}.weight" for p in ("to_k", "to_v")]))
         if not self.grad:
-            self._add(fwd)
+            self._add(fwd, meta=meta)
             return o
         gp = self.gmaps.get(key)
 
@@ -462,7 +508,7 @@ class Plan:
             assert not acc[0]
             return lambda: ops.cross_attn_bwd(q.t, kt, vt, None if last else o.g, gp, q.g, B, heads, S, T,
                                               d, scale, k_view=k_view, v_view=k_view)
-        self._add(fwd, make_bwd, [q])
+        self._add(fwd, make_bwd, [q], meta=meta)
         return o
 
     def ff(self, x: Act, res: Act, name: str, alpha=1.0, norm: Optional[str] = None) -> Act:
@@ -476,7 +522,8 @@ class Plan:
         pre = self.linear(x, f"{name}.net.0.proj")                 # packed [M, 8C] pre-activation
         act = self._act(x.rows, pre.C // 2)
         self._add(lambda: ops.geglu_fwd(pre.t, out=act.t),
-                  lambda acc: (lambda: ops.geglu_bwd(pre.t, act.g, pre.g)), [pre])
+                  lambda acc: (lambda: ops.geglu_bwd(pre.t, act.g, pre.g)), [pre],
+                  meta=dict(kind="geglu", ins=[pre], out=act))
         return self.linear(act, f"{name}.net.2", res=res, alpha=alpha)
 
     # --------------------------------------------------------------------------------------
@@ -566,7 +613,9 @@ class Plan:
             lat = lat[:B // 2]
             f_in *= 0.5
         lat8_in = lat8[:lat.shape[0] * L * L]              # the rows the converter writes: the first half under the pair
-        self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8_in), ops.gemm_launch(d_in, None, f_in)))
+        self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8_in), ops.gemm_launch(d_in, None, f_in)),
+                  meta=dict(kind="conv_in", ins=[lat], out=x0, H=L, scratch=[lat8_in], desc=d_in,
+                            params=dict(weight=["conv_in.weight"], bias="conv_in.bias")))
         skips = [(x, L)]
         H = L
         done = False
@@ -615,7 +664,8 @@ class Plan:
             n = self.groupnorm(x, None, "conv_norm_out", H * H, cfg.norm_eps, True)
             self.eps_out = self._alloc((B, cfg.out_channels, L, L))
             eo = self.eps_out
-            self._add(lambda: ops.conv_out(n.t, w.h["conv_out.w"], w.f["conv_out.b"], B, L, out=eo))
+            self._add(lambda: ops.conv_out(n.t, w.h["conv_out.w"], w.f["conv_out.b"], B, L, out=eo),
+                      meta=dict(kind="conv_out", ins=[n], out=eo, H=L, params=dict(weight=["conv_out.weight"], bias="conv_out.bias")))
         if self.grad:
             self._finalize_backward()
 
@@ -643,6 +693,9 @@ class Plan:
                 op.bwd = op.make_bwd(op.acc)
         self.g_latents = self._alloc(tuple(self.latents_in.shape))
         self._bwd_ops = [op.bwd for op in reversed(self.ops) if op.bwd is not None]
+        # the conv_in input gradient at the end of Plan.backward (ops.conv_out on conv_in.wd)
+        self.bwd_tail_meta = dict(kind="conv_in_dgrad", ins=[self._x0], out=self.g_latents, H=self.L,
+                                  params=dict(weight=["conv_in.weight"]))
 
     # --------------------------------------------------------------------------------------
     def forward(self, latents: Optional[torch.Tensor] = None):
@@ -877,6 +930,15 @@ class UNetEngine:
                text_batch_offset, obj_batch_offset, mode, self.fold_ln, pair_shared)
         if B + text_batch_offset > self.max_text_batch:
             raise RuntimeError(f"plan batch {B} (+{text_batch_offset}) exceeds max_text_batch={self.max_text_batch}")
+        if grad:
+            # the store packs dgrad weights (.wt / .wd) up to up block GRAD_PLAN_LAST_UP_BLOCK only (weightstore._needs_bwd)
+            if not stop_key:
+                raise ValueError("grad plan refused: without a stop_key the plan runs to the end of the network, and a grad plan "
+                                 f"ends at up block {GRAD_PLAN_LAST_UP_BLOCK} at the latest (no dgrad weights are packed behind it)")
+            k = tuple(stop_key)
+            if k[0] == "up" and k[1] > GRAD_PLAN_LAST_UP_BLOCK:
+                raise ValueError(f"grad plan refused: attention key {k} lies in up block {k[1]}, and a grad plan ends at "
+                                 f"up block {GRAD_PLAN_LAST_UP_BLOCK} at the latest (no dgrad weights are packed behind it)")
         if key not in self._plans:
             with ops.tuning(mode):                        # descriptors are tuned when they are built
                 self._plans[key] = Plan(self, B, L, grad=grad, fuser=fuser, stop_key=stop_key,

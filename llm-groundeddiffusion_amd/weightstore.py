@@ -26,9 +26,12 @@ F16, F32 = torch.float16, torch.float32
 # (pipelines.py:14 DEFAULT_GUIDANCE_ATTN_KEYS) — SURVEY.md §0.3
 
 
+GRAD_PLAN_LAST_UP_BLOCK = 1     # UNetEngine.plan refuses a grad plan that would run behind this up block
+
+
 def _needs_bwd(prefix: str) -> bool:
     if prefix.startswith("up_blocks."):
-        return int(prefix.split(".")[1]) <= 1
+        return int(prefix.split(".")[1]) <= GRAD_PLAN_LAST_UP_BLOCK
     return True
 
 

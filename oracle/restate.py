@@ -24,11 +24,12 @@ DEFAULT_GUIDANCE_ATTN_KEYS = [("mid", 0, 0, 0), ("up", 1, 0, 0), ("up", 1, 1, 0)
 # =================================================================================================
 # UNet forward (models/unet_2d_condition.py:704-980)
 # =================================================================================================
-def timestep_embedding(t, dim):
-    """[ext] Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) — unet_2d_condition.py:305,801."""
+def timestep_embedding(t, dim, dtype=torch.float32):
+    """[ext] Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) — unet_2d_condition.py:305,801.
+    dtype: that of the weights the result meets (fp32: the reference; fp64: the whole forward in double, tests)."""
     half = dim // 2
-    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
-    e = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=dtype) / half)
+    e = t[:, None].to(dtype) * freqs[None]
     return torch.cat([torch.cos(e), torch.sin(e)], dim=-1)
 
 
@@ -41,12 +42,19 @@ def resnet(sd, p, x, temb, groups, eps):
     h = F.conv2d(h, sd[f"{p}.conv2.weight"], sd[f"{p}.conv2.bias"], padding=1)
     if f"{p}.conv_shortcut.weight" in sd:
         x = F.conv2d(x, sd[f"{p}.conv_shortcut.weight"], sd[f"{p}.conv_shortcut.bias"])
-    if _TAPS is not None:
-        _TAPS[f"{p}.out"] = (x + h).detach()
-    return x + h
+    return _tap(f"{p}.out", x + h)
 
 
 _TAPS = None  # optional dict collecting named intermediate activations (debugging only)
+_TAPS_LIVE = False  # taps stay attached to the autograd graph and retain their gradient (tests/unet_plan_cases.py)
+
+
+def _tap(name, x):
+    if _TAPS is not None:
+        if _TAPS_LIVE and x.requires_grad:
+            x.retain_grad()
+        _TAPS[name] = x if _TAPS_LIVE else x.detach()
+    return x
 
 
 def attention(sd, p, x, ctx, heads, hook=None):
@@ -82,8 +90,7 @@ def fuser(sd, p, x, objs, heads):
     objs = F.linear(objs, sd[f"{p}.linear.weight"], sd[f"{p}.linear.bias"])
     h = layer_norm(sd, f"{p}.norm1", torch.cat([x, objs], dim=1))
     x = x + sd[f"{p}.alpha_attn"].tanh() * attention(sd, f"{p}.attn", h, None, heads)[:, :n_visual]
-    if _TAPS is not None:
-        _TAPS[p.replace(".transformer_blocks.0.fuser", "") + ".after_fuser_attn"] = x.detach()
+    _tap(p.replace(".transformer_blocks.0.fuser", "") + ".after_fuser_attn", x)
     x = x + sd[f"{p}.alpha_dense"].tanh() * feed_forward(sd, f"{p}.ff", layer_norm(sd, f"{p}.norm2", x))
     return x
 
@@ -104,13 +111,9 @@ def transformer(sd, p, x, ctx, heads, groups, key, st):
     else:
         h = F.linear(h.permute(0, 2, 3, 1).reshape(B, H * W, C), w_in, sd[f"{p}.proj_in.bias"])
     t = f"{p}.transformer_blocks.0"
-    h = attention(sd, f"{t}.attn1", layer_norm(sd, f"{t}.norm1", h), None, heads) + h
-    if _TAPS is not None:
-        _TAPS[f"{p}.after_attn1"] = h.detach()
+    h = _tap(f"{p}.after_attn1", attention(sd, f"{t}.attn1", layer_norm(sd, f"{t}.norm1", h), None, heads) + h)
     if st["objs"] is not None and st["fuser_enabled"]:
-        h = fuser(sd, f"{t}.fuser", h, st["objs"], heads)          # attention.py:198-200
-        if _TAPS is not None:
-            _TAPS[f"{p}.after_fuser"] = h.detach()
+        h = _tap(f"{p}.after_fuser", fuser(sd, f"{t}.fuser", h, st["objs"], heads))          # attention.py:198-200
     hook = None
     if st["saved"] is not None and (st["save_keys"] is None or key in st["save_keys"]):
         def hook(probs, key=key):                                   # attention_processor.py:463-480
@@ -120,9 +123,7 @@ def transformer(sd, p, x, ctx, heads, groups, key, st):
             if st["cond_only"]:
                 probs = probs[probs.shape[0] // 2:]
             st["saved"][key] = probs
-    h = attention(sd, f"{t}.attn2", layer_norm(sd, f"{t}.norm2", h), ctx, heads, hook) + h
-    if _TAPS is not None:
-        _TAPS[f"{p}.after_attn2"] = h.detach()
+    h = _tap(f"{p}.after_attn2", attention(sd, f"{t}.attn2", layer_norm(sd, f"{t}.norm2", h), ctx, heads, hook) + h)
     if st["stop_after"] is not None and key == st["stop_after"]:
         raise _Stop()
     h = feed_forward(sd, f"{t}.ff", layer_norm(sd, f"{t}.norm3", h)) + h
@@ -131,9 +132,7 @@ def transformer(sd, p, x, ctx, heads, groups, key, st):
         h = F.conv2d(h.reshape(B, H, W, C).permute(0, 3, 1, 2), w_out, sd[f"{p}.proj_out.bias"])
     else:
         h = F.linear(h, w_out, sd[f"{p}.proj_out.bias"]).reshape(B, H, W, C).permute(0, 3, 1, 2)
-    if _TAPS is not None:
-        _TAPS[f"{p}.out"] = (h + res).detach()
-    return h + res
+    return _tap(f"{p}.out", h + res)
 
 
 def position_net(sd, boxes, masks, positive_embeddings):
@@ -151,23 +150,24 @@ def position_net(sd, boxes, masks, positive_embeddings):
 
 
 def unet_forward(sd, cfg, sample, t, ehs, *, saved=None, save_keys=None, token_only=None,
-                 cond_only=False, gligen=None, fuser_enabled=True, stop_after=None, taps=None):
+                 cond_only=False, gligen=None, fuser_enabled=True, stop_after=None, taps=None, taps_live=False):
     """UNet2DConditionModel.forward (unet_2d_condition.py:704-980) for the SD 1.x/2.x configs.
 
     cfg: dict-like with block_out_channels, layers_per_block, attention_head_dim, norm_num_groups,
     norm_eps.  gligen: dict(boxes, masks, positive_embeddings) or None (:863-872).
     stop_after: attn key after whose cross-attention the forward is abandoned (returns None) — the
     algorithmic minimum for the guidance pass (TODO at pipelines.py:46); loss/grad are identical.
+    taps_live: the tensors collected in `taps` stay in the autograd graph and retain their gradients.
     """
-    global _TAPS
-    _TAPS = taps
+    global _TAPS, _TAPS_LIVE
+    _TAPS, _TAPS_LIVE = taps, bool(taps_live)
     boc = list(cfg["block_out_channels"])
     heads_l = list(cfg["attention_head_dim"])
     groups, eps, lpb = cfg["norm_num_groups"], cfg["norm_eps"], cfg["layers_per_block"]
     n = len(boc)
     B = sample.shape[0]
     tt = torch.as_tensor(t).reshape(-1).expand(B)
-    emb = timestep_embedding(tt, boc[0])
+    emb = timestep_embedding(tt, boc[0], sd["time_embedding.linear_1.weight"].dtype)
     emb = F.linear(emb, sd["time_embedding.linear_1.weight"], sd["time_embedding.linear_1.bias"])
     emb = F.linear(F.silu(emb), sd["time_embedding.linear_2.weight"], sd["time_embedding.linear_2.bias"])
     st = dict(saved=saved, save_keys=[tuple(k) for k in save_keys] if save_keys is not None else None,

@@ -29,11 +29,11 @@ from lgd_amd import ops  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gemm_conformance_cases import SENT16, SENT32, Carved  # noqa: E402
+from layernorm_cases import EPS, fwd_ref as _fwd_ref, bwd_ref as _bwd_ref  # noqa: E402
 
 H16, F32, F64 = torch.float16, torch.float32, torch.float64
 U, W = 2.0 ** -11, 2.0 ** -24
 NAN = float("nan")
-EPS = 1e-5
 WIDTHS = [64, 320, 640, 1280, 1536, 2560]
 B, S, TAIL = 3, 100, 30
 ROW_CODE = {64: 514, 320: 514, 640: 524, 1280: 532, 1536: 532, 2560: 550}        # the row kernels, the wave kernel at 2560
@@ -62,32 +62,6 @@ def _data(rows, C, seed):
     beta = torch.randn(C, generator=g).to(F32).to(F64)
     gy = torch.randn(rows, C, generator=g).to(H16).to(F64)
     return x, gamma, beta, gy
-
-
-def _fwd_ref(x, gamma, beta):
-    C = x.shape[-1]
-    mean = x.mean(-1, keepdim=True)
-    var = ((x - mean) ** 2).mean(-1, keepdim=True)
-    rstd = (var + EPS) ** -0.5
-    y = (x - mean) * rstd * gamma + beta
-    e_m = (C + 2) * W * x.abs().mean(-1, keepdim=True)
-    e_r = 0.5 * ((C + 6) * W + e_m ** 2 / var) + 2.0 ** -22
-    bound = U * y.abs() + 2.0 ** -25 + (x - mean).abs() * rstd * gamma.abs() * (e_r + 3 * W) + e_m * rstd * gamma.abs() + W * y.abs()
-    return dict(y=y, bound=bound, mean=mean, rstd=rstd, bound_mean=e_m + W * mean.abs(), bound_rstd=rstd * (e_r + W))
-
-
-def _bwd_ref(x, gy, gamma, mean, rstd, base=None):
-    C = x.shape[-1]
-    d = gy * gamma
-    xh = (x - mean) * rstd
-    s1 = d.mean(-1, keepdim=True)
-    s2 = (d * xh).mean(-1, keepdim=True)
-    dx = rstd * (d - s1 - xh * s2)
-    out = dx if base is None else dx + base
-    bound = (U * out.abs() + 2.0 ** -25 + 2 * W * out.abs()
-             + rstd * ((C + 2) * W * d.abs().mean(-1, keepdim=True) + xh.abs() * (C + 4) * W * (d * xh).abs().mean(-1, keepdim=True)
-                       + 6 * W * (d.abs() + s1.abs() + (xh * s2).abs())))
-    return out, bound
 
 
 def _ratio(y, ref, bound, what):
