@@ -791,9 +791,35 @@ int lgd_sam_mask_tail_f32(const float* logits, const float* iou, const int32_t* 
  *   the first maximum in raster order — up_w = height / wm and up_h = width / hm, the reference's swapped naming
  *   (:135,:146) kept; smooth: fp32 [N][hm][wm], the filtered map, or NULL.  One workgroup per item, fp32 in LDS.
  * LGD_ERR_ARG: NULL attn / coarse / points, a size or scale <= 0, sigma <= 0.  LGD_ERR_UNSUPPORTED: hm * wm > 4096 (a
- * 64 x 64 map), radius > 64, N > 65535.  The box branch (use_box_input=True) needs an erosion and stays on the host. */
+ * 64 x 64 map), radius > 64, N > 65535.  The box branch (use_box_input=True) is lgd_sam_attn_box_prompt_f32 below. */
 int lgd_sam_attn_prompt_f32(const float* attn, int N, int hm, int wm, float sigma, float mask_th, int up_w, int up_h,
                             uint8_t* coarse, float* points, float* smooth, void* stream);
+/* LMD's BOX prompt from the object token's attention map: models/sam.py:125-147 with use_box_input=True and :113-122
+ * (preprocess_mask WITH its opening), then utils/utils.py:72-88 (binary_mask_to_box).  One workgroup per item; the map
+ * and two byte masks live in LDS; no atomics; every output element is written once.
+ *   Smoothing and threshold: exactly those of lgd_sam_attn_prompt_f32 (one device function serves both kernels): scipy's
+ *   gaussian_filter defaults — mode `reflect`, radius int(4 sigma + 0.5), fp32 — and the mask
+ *   (a - min) / max(a - min) > mask_th.
+ *   Opening: n_open erosions, then n_open dilations (scipy.ndimage.binary_erosion / binary_dilation, iterations =
+ *   n_open).  The structuring element is scipy's default generate_binary_structure(2, 1): a pixel and its 4 neighbours.
+ *   border_value = 0 for both: a set pixel on the border, which has an outside neighbour, erodes, and the outside never
+ *   dilates inward.  iterations = n equals n single steps, here with one barrier per step.  n_open = 0 skips it.
+ *   coarse: uint8 [N][hm][wm], 0 / 1: the OPENED mask.
+ *   boxes: fp32 [N][4] = {xmin * up_w, ymin * up_h, xmax * up_w, ymax * up_h} with ymin = max(min_y - 1, 0), ymax =
+ *   min(max_y + 1, hm), xmin = max(min_x - 1, 0), xmax = min(max_x + 1, wm) over the set pixels — binary_mask_to_box(
+ *   enlarge_box_by_one=True, w_scale=up_w, h_scale=up_h) as sam_refine_attn calls it, with up_w = height / wm and up_h =
+ *   width / hm: the reference's swapped (w, h) naming (:135,:141) kept, as the point kernel keeps it.  The values are
+ *   small integers, exact in fp32.  Minimum and maximum come from wave reductions and one pass over LDS.
+ *   empty: int32 [N], 1 where the opened mask has no pixel (the reference fails there: min() of an empty sequence).  A
+ *   constant map counts: max(a - min) = 0, and the reference's NaN > mask_th is False everywhere.  boxes is {0, 0, 0, 0}
+ *   there.
+ *   smooth: fp32 [N][hm][wm], the filtered map, or NULL.
+ * LGD_ERR_ARG: NULL attn / coarse / boxes / empty, a size or scale <= 0, sigma <= 0, n_open < 0, an fp32 / int32 operand
+ * not 4-byte aligned.  LGD_ERR_UNSUPPORTED: hm * wm > 4096, radius > 64, N > 65535, n_open > 64.  Both are refused on
+ * the host before any launch: nothing is written. */
+int lgd_sam_attn_box_prompt_f32(const float* attn, int N, int hm, int wm, float sigma, float mask_th, int n_open,
+                                int up_w, int up_h, uint8_t* coarse, float* boxes, int32_t* empty, float* smooth,
+                                void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The hand-off between the two stages of LMD / LMD+ for all layouts of a batch (additive exports: LGD_ABI_VERSION stays

@@ -110,6 +110,7 @@ SIGNATURES = {
     "lgd_blank_flagged_u8": [_P, _L, _P, _L, _I, _P],
     "lgd_sam_mask_tail_f32": [_P, _P, _P, _P] + [_I] * 8 + [_D, _D] + [_P] * 6,
     "lgd_sam_attn_prompt_f32": [_P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P],
+    "lgd_sam_attn_box_prompt_f32": [_P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P],
     "lgd_handoff_place": [_P, _P, _P] + [_I] * 6 + [_P, _P, _P],
     "lgd_handoff_compose_f32": [_P] * 5 + [_I] * 6 + [_P] * 4,
     "lgd_handoff_ref_maps_f32": [_P] * 4 + [_I] * 6 + [_P, _P],

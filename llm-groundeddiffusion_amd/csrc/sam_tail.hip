@@ -13,6 +13,10 @@
 //  * sam_attn_prompt_kernel — models/sam.py:113-122 (`preprocess_mask`, no erosion) and :125-147 (the point-prompt
 //    branch of `sam_refine_attn`): scipy.ndimage.gaussian_filter (separable, axis 0 then axis 1, mode `reflect`),
 //    min-max normalisation, threshold, first arg-max.  One workgroup per item, the map in LDS, fp32.
+//  * sam_attn_box_prompt_kernel — the box-prompt branch of the same lines (use_box_input=True): the same smoothing and
+//    threshold (one device function serves both kernels), then `preprocess_mask`'s opening (scipy.ndimage.binary_erosion /
+//    binary_dilation, 4-neighbourhood, border 0) on two byte masks in LDS and utils.binary_mask_to_box as a min / max
+//    reduction.  One workgroup per item.
 #include "common.h"
 
 #include <float.h>
@@ -21,7 +25,7 @@ namespace {
 
 constexpr int TAIL_MAX_K = 4, TAIL_MAX_SIDE = 4096, TAIL_MAX_SRC = 32768, TAIL_MAX_N = 65535;
 constexpr int SEL_THREADS = 256;
-constexpr int PROMPT_THREADS = 256, PROMPT_MAX_PIX = 4096, PROMPT_MAX_RADIUS = 64;
+constexpr int PROMPT_THREADS = 256, PROMPT_MAX_PIX = 4096, PROMPT_MAX_RADIUS = 64, PROMPT_MAX_OPEN = 64;
 
 // One axis of torch's bilinear sampling (align_corners=False): at::native::area_pixel_compute_source_index and
 // guard_index_and_lambda.  `scale` = (float)in / out.
@@ -215,39 +219,48 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
   return m < n ? m : 2 * n - 1 - m;
 }
 
-__global__ __launch_bounds__(PROMPT_THREADS) void sam_attn_prompt_kernel(const PromptArgs a) {
-  __shared__ float s_a[PROMPT_MAX_PIX], s_b[PROMPT_MAX_PIX];
+// What both prompt kernels share (models/sam.py:128 and the first two lines of :113-116): item n's map smoothed into s_a
+// (and into `smooth` when given), and the block-wide minimum, maximum and first arg-max of the smoothed map.  s_a, s_b:
+// PROMPT_MAX_PIX floats of LDS each.  Every thread leaves with the same three values; s_a[p] is final for the thread
+// that owns p (p = tid, tid + PROMPT_THREADS, ..), for the others after the next barrier.
+struct SmoothStat {
+  float lo, hi;
+  int at;
+};
+
+__device__ __forceinline__ SmoothStat prompt_smooth(const float* attn, float* smooth, int n, int hm, int wm, int r,
+                                                    float sigma, float* s_a, float* s_b) {
   __shared__ float s_w[2 * PROMPT_MAX_RADIUS + 1];
   constexpr int NW = PROMPT_THREADS / LGD_WAVE;
   __shared__ float s_red[2 * NW];
   __shared__ int s_idx[NW];
-  const int n = blockIdx.x, tid = threadIdx.x, P = a.hm * a.wm, r = a.radius;
-  const float* src = a.attn + (long)n * P;
+  const int tid = threadIdx.x, P = hm * wm;
+  const float* src = attn + (long)n * P;
   for (int p = tid; p < P; p += PROMPT_THREADS) s_a[p] = src[p];
   // scipy's _gaussian_kernel1d: exp(-0.5 / sigma^2 * x^2) over [-r, r], divided by its sum (fp64 there; here fp64 too,
   // rounded once to fp32)
   if (tid == 0) {
-    const double c = -0.5 / ((double)a.sigma * (double)a.sigma);
+    const double c = -0.5 / ((double)sigma * (double)sigma);
     double sum = 0.0;
     for (int j = -r; j <= r; ++j) sum += exp(c * (double)(j * j));
     for (int j = -r; j <= r; ++j) s_w[j + r] = (float)(exp(c * (double)(j * j)) / sum);
   }
   __syncthreads();
   for (int p = tid; p < P; p += PROMPT_THREADS) {  // axis 0
-    const int y = p / a.wm, x = p - y * a.wm;
+    const int y = p / wm, x = p - y * wm;
     float acc = 0.f;
-    for (int j = -r; j <= r; ++j) acc += s_w[j + r] * s_a[reflect_index(y + j, a.hm) * a.wm + x];
+    for (int j = -r; j <= r; ++j) acc += s_w[j + r] * s_a[reflect_index(y + j, hm) * wm + x];
     s_b[p] = acc;
   }
   __syncthreads();
   float lo = FLT_MAX, hi = -FLT_MAX;
   int at = P;
   for (int p = tid; p < P; p += PROMPT_THREADS) {  // axis 1
-    const int y = p / a.wm, x = p - y * a.wm;
+    const int y = p / wm, x = p - y * wm;
     float acc = 0.f;
-    for (int j = -r; j <= r; ++j) acc += s_w[j + r] * s_b[y * a.wm + reflect_index(x + j, a.wm)];
+    for (int j = -r; j <= r; ++j) acc += s_w[j + r] * s_b[y * wm + reflect_index(x + j, wm)];
     s_a[p] = acc;
-    if (a.smooth) a.smooth[(long)n * P + p] = acc;
+    if (smooth) smooth[(long)n * P + p] = acc;
     lo = fminf(lo, acc);
     if (acc > hi) hi = acc, at = p;  // ascending p: the first of equal maxima
   }
@@ -268,13 +281,107 @@ __global__ __launch_bounds__(PROMPT_THREADS) void sam_attn_prompt_kernel(const P
     const int a2 = s_idx[i];
     if (h2 > hi || (h2 == hi && a2 < at)) hi = h2, at = a2;
   }
-  const float span = hi - lo;  // = max(a - min(a)): the subtraction is monotonic
+  SmoothStat st;
+  st.lo = lo, st.hi = hi, st.at = at;
+  return st;
+}
+
+// preprocess_mask's `(a - min) / max(a - min) > mask_th`; span = max - min = max(a - min): the subtraction is monotonic.
+// A constant map has span 0: 0 / 0 = NaN, and NaN > th is false, as in numpy.
+__device__ __forceinline__ int prompt_bit(float v, float lo, float span, float mask_th) {
+  return ((v - lo) / span > mask_th) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(PROMPT_THREADS) void sam_attn_prompt_kernel(const PromptArgs a) {
+  __shared__ float s_a[PROMPT_MAX_PIX], s_b[PROMPT_MAX_PIX];
+  const int n = blockIdx.x, tid = threadIdx.x, P = a.hm * a.wm;
+  const SmoothStat st = prompt_smooth(a.attn, a.smooth, n, a.hm, a.wm, a.radius, a.sigma, s_a, s_b);
+  const float span = st.hi - st.lo;
   uint8_t* co = a.coarse + (long)n * P;
-  for (int p = tid; p < P; p += PROMPT_THREADS) co[p] = ((s_a[p] - lo) / span > a.mask_th) ? 1 : 0;
+  for (int p = tid; p < P; p += PROMPT_THREADS) co[p] = (uint8_t)prompt_bit(s_a[p], st.lo, span, a.mask_th);
   if (tid == 0) {
-    const int peak_y = at / a.wm, peak_x = at - peak_y * a.wm;
+    const int peak_y = st.at / a.wm, peak_x = st.at - peak_y * a.wm;
     a.points[(long)n * 2] = (float)(peak_x * a.up_h);  // the reference's swapped (w, h) naming (:135,:146)
     a.points[(long)n * 2 + 1] = (float)(peak_y * a.up_w);
+  }
+}
+
+struct BoxPromptArgs {
+  const float* attn;  // [N][hm][wm]
+  uint8_t* coarse;    // [N][hm][wm]
+  float* boxes;       // [N][4]
+  int32_t* empty;     // [N]
+  float* smooth;      // [N][hm][wm] or NULL
+  int hm, wm, radius, n_open, up_w, up_h;
+  float sigma, mask_th;
+};
+
+__global__ __launch_bounds__(PROMPT_THREADS) void sam_attn_box_prompt_kernel(const BoxPromptArgs a) {
+  __shared__ float s_a[PROMPT_MAX_PIX], s_b[PROMPT_MAX_PIX];
+  __shared__ uint8_t s_m0[PROMPT_MAX_PIX], s_m1[PROMPT_MAX_PIX];
+  constexpr int NW = PROMPT_THREADS / LGD_WAVE;
+  __shared__ int s_box[4 * NW];
+  const int n = blockIdx.x, tid = threadIdx.x, hm = a.hm, wm = a.wm, P = hm * wm;
+  const SmoothStat st = prompt_smooth(a.attn, a.smooth, n, hm, wm, a.radius, a.sigma, s_a, s_b);
+  const float span = st.hi - st.lo;
+  for (int p = tid; p < P; p += PROMPT_THREADS) s_m0[p] = (uint8_t)prompt_bit(s_a[p], st.lo, span, a.mask_th);
+  __syncthreads();
+  // the opening (preprocess_mask :118-120): n_open erosions, then n_open dilations, with the pixel and its 4 neighbours
+  // (generate_binary_structure(2, 1)) and border_value = 0: whatever lies outside the map is 0 for both, so a set pixel
+  // on the border erodes and the outside never dilates inward.  One step per pass, from one byte mask into the other.
+  uint8_t* cur = s_m0;
+  uint8_t* nxt = s_m1;
+#pragma unroll 1
+  for (int s = 0; s < 2 * a.n_open; ++s) {
+    const bool erode = s < a.n_open;
+    for (int p = tid; p < P; p += PROMPT_THREADS) {
+      const int y = p / wm, x = p - y * wm;
+      const int up = y > 0 ? cur[p - wm] : 0, down = y < hm - 1 ? cur[p + wm] : 0;
+      const int left = x > 0 ? cur[p - 1] : 0, right = x < wm - 1 ? cur[p + 1] : 0;
+      const int c = cur[p];
+      nxt[p] = (uint8_t)(erode ? (c & up & down & left & right) : (c | up | down | left | right));
+    }
+    __syncthreads();
+    uint8_t* t = cur;
+    cur = nxt, nxt = t;
+  }
+  // the opened mask out, and its bounding box: min / max per thread, per wave, then over the waves through LDS
+  uint8_t* co = a.coarse + (long)n * P;
+  int y0 = hm, y1 = -1, x0 = wm, x1 = -1;
+  for (int p = tid; p < P; p += PROMPT_THREADS) {
+    const int bit = cur[p];
+    co[p] = (uint8_t)bit;
+    if (bit) {
+      const int y = p / wm, x = p - y * wm;
+      y0 = min(y0, y), y1 = max(y1, y), x0 = min(x0, x), x1 = max(x1, x);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    y0 = min(y0, __shfl_xor(y0, o, 64)), y1 = max(y1, __shfl_xor(y1, o, 64));
+    x0 = min(x0, __shfl_xor(x0, o, 64)), x1 = max(x1, __shfl_xor(x1, o, 64));
+  }
+  if ((tid & 63) == 0) {
+    int* d = s_box + 4 * (tid >> 6);
+    d[0] = y0, d[1] = y1, d[2] = x0, d[3] = x1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      y0 = min(y0, s_box[4 * i]), y1 = max(y1, s_box[4 * i + 1]);
+      x0 = min(x0, s_box[4 * i + 2]), x1 = max(x1, s_box[4 * i + 3]);
+    }
+    // utils.binary_mask_to_box(enlarge_box_by_one=True, w_scale=up_w, h_scale=up_h): the reference's swapped (w, h)
+    // naming (:135,:141) kept.  An empty mask (the reference raises there) is flagged and gets the zero box.
+    const bool none = y1 < 0;
+    const int ymin = max(y0 - 1, 0), ymax = min(y1 + 1, hm), xmin = max(x0 - 1, 0), xmax = min(x1 + 1, wm);
+    float* b = a.boxes + (long)n * 4;
+    b[0] = none ? 0.f : (float)(xmin * a.up_w);
+    b[1] = none ? 0.f : (float)(ymin * a.up_h);
+    b[2] = none ? 0.f : (float)(xmax * a.up_w);
+    b[3] = none ? 0.f : (float)(ymax * a.up_h);
+    a.empty[n] = none ? 1 : 0;
   }
 }
 
@@ -326,6 +433,25 @@ extern "C" int lgd_sam_attn_prompt_f32(const float* attn, int N, int hm, int wm,
   a.hm = hm, a.wm = wm, a.radius = radius, a.up_w = up_w, a.up_h = up_h;
   a.sigma = sigma, a.mask_th = mask_th;
   hipLaunchKernelGGL(sam_attn_prompt_kernel, dim3((unsigned)N), dim3(PROMPT_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_sam_attn_box_prompt_f32(const float* attn, int N, int hm, int wm, float sigma, float mask_th,
+                                           int n_open, int up_w, int up_h, uint8_t* coarse, float* boxes,
+                                           int32_t* empty, float* smooth, void* stream) {
+  if (!attn || !coarse || !boxes || !empty) return LGD_ERR_ARG;
+  if (N <= 0 || hm <= 0 || wm <= 0 || !(sigma > 0.f) || up_w <= 0 || up_h <= 0 || n_open < 0) return LGD_ERR_ARG;
+  if (misaligned(attn, 4) || misaligned(boxes, 4) || misaligned(empty, 4) || misaligned(smooth, 4)) return LGD_ERR_ARG;
+  const int radius = (int)(4.0 * (double)sigma + 0.5);  // scipy: truncate = 4.0
+  if (N > TAIL_MAX_N || (long)hm * wm > PROMPT_MAX_PIX || radius > PROMPT_MAX_RADIUS || n_open > PROMPT_MAX_OPEN)
+    return LGD_ERR_UNSUPPORTED;
+  (void)hipGetLastError();
+  BoxPromptArgs a;
+  a.attn = attn, a.coarse = coarse, a.boxes = boxes, a.empty = empty, a.smooth = smooth;
+  a.hm = hm, a.wm = wm, a.radius = radius, a.n_open = n_open, a.up_w = up_w, a.up_h = up_h;
+  a.sigma = sigma, a.mask_th = mask_th;
+  hipLaunchKernelGGL(sam_attn_box_prompt_kernel, dim3((unsigned)N), dim3(PROMPT_THREADS), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
   return lgd_check_launch();
 }

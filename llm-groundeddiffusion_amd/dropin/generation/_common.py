@@ -101,11 +101,14 @@ def build_layout(spec, bg_seed, fg_seed_start, so_negative_prompt, overall_negat
                         bg_seed=bg_seed, fg_seed_start=fg_seed_start)
 
 
-def sam_refiner(model_dict, height, width, sam_resize=None, **kw):
+def sam_refiner(model_dict, height, width, sam_resize=None, sam_attn_box=None, **kw):
     """The SAM mask refiner of the plugin when `model_dict` carries a SAM model (generate.py:126-127 merges
     `sam.load_sam()` into it), else None = box masks.  sam_resize: None (the default) keeps the processor `model_dict`
     carries; "torch" or "pillow" asks for that resize of `DeviceSamProcessor` — a device processor of the other kind is
-    rebuilt with it, the Hugging Face host processor has no such choice and is refused."""
+    rebuilt with it, the Hugging Face host processor has no such choice and is refused.  sam_attn_box: None (the
+    default) keeps the per-image host path for the box prompt of an attention map (`use_box_input`); "device" makes that
+    prompt on the device for all boxes at once (`SamRefiner(attn_box="device")`) and is refused without the device
+    processor."""
     has = ("sam_model" in model_dict) if isinstance(model_dict, dict) else hasattr(model_dict, "sam_model")
     if not has:
         return None
@@ -118,6 +121,12 @@ def sam_refiner(model_dict, height, width, sam_resize=None, **kw):
                              "(wrap_sam(..., 'device') or 'device-pillow'); model_dict carries the host processor")
         if processor.resize != sam_resize:
             processor = DeviceSamProcessor(processor.dev, processor.target, resize=sam_resize)
+    if sam_attn_box is not None:
+        if sam_attn_box == "device" and not isinstance(processor, DeviceSamProcessor):
+            raise ValueError("sam_attn_box='device' makes the attention map's box prompt on the device and needs the "
+                             "device processor (wrap_sam(..., 'device') or 'device-pillow'); model_dict carries the host "
+                             "processor")
+        kw["attn_box"] = sam_attn_box
     return SamRefiner(dict(sam_model=md["sam_model"], sam_processor=processor), height=height, width=width, **kw)
 
 

@@ -18,14 +18,17 @@ def run(spec, bg_seed=1, overall_prompt_override="", fg_seed_start=20, frozen_st
         so_negative_prompt=DEFAULT_SO_NEGATIVE_PROMPT, overall_negative_prompt=DEFAULT_OVERALL_NEGATIVE_PROMPT,
         mask_th_for_point=0.25, so_horizontal_center_only=False, align_with_overall_bboxes=True,
         horizontal_shift_only=False, use_fast_schedule=False, so_vertical_placement="floor_padding",
-        so_floor_padding=0.2, use_box_input=False, use_ref_ca=True, use_autocast=False, verbose=False):
+        so_floor_padding=0.2, use_box_input=False, use_ref_ca=True, use_autocast=False, verbose=False, sam_attn_box=None):
     """Argument names and defaults of generation/lmd.py:215-256 (incl. so_center_box=True /
     align_with_overall_bboxes=True: per-box generations run on a centred box, histories, masks and
     reference maps are shifted back onto the overall boxes before composition).  When `models.model_dict` carries
     a SAM model (generate.py:126-127 `model_dict.update(sam.load_sam())`) every per-box mask is SAM's refinement of the
     object token's attention map (generation/lmd.py:124-149) with `mask_th_for_point` / `use_box_input`; otherwise the
     masks are the box masks.  `use_autocast=False` (the reference's default here: fp32) is answered with
-    fp16 compute / fp32 accumulation and ONE RuntimeWarning (`_common.note_precision`)."""
+    fp16 compute / fp32 accumulation and ONE RuntimeWarning (`_common.note_precision`).
+    `sam_attn_box` is the one keyword the reference does not have: None keeps the per-image host path for
+    `use_box_input=True`, "device" makes the box prompts of all attention maps in one device pass
+    (`_common.sam_refiner`; it needs the device processor and is refused with a ValueError otherwise)."""
     if not use_autocast:                       # the reference's default for this method: fp32 (generation/lmd.py:254,375)
         note_precision("generation.lmd.run", "use_autocast=False")
     if num_inference_steps <= 10:
@@ -33,7 +36,8 @@ def run(spec, bg_seed=1, overall_prompt_override="", fg_seed_start=20, frozen_st
         print("note: the reference's SAM point prompt aggregates maps from step 10 on; with <=10 steps it would fail")
     sm = models.model_dict.sampler
     refiner = sam_refiner(models.model_dict, height, width, discourage_mask_below_coarse_iou=0.25,
-                          use_box_input=use_box_input, mask_th_for_point=mask_th_for_point, verbose=verbose)
+                          use_box_input=use_box_input, mask_th_for_point=mask_th_for_point, verbose=verbose,
+                          sam_attn_box=sam_attn_box)
     lay = build_layout(spec, bg_seed, fg_seed_start, so_negative_prompt, overall_negative_prompt, height, width,
                        overall_prompt_override, verbose)
     out = lmd_generate(sm, lay, num_inference_steps=num_inference_steps, frozen_step_ratio=frozen_step_ratio,

@@ -1207,6 +1207,23 @@ def sam_attn_prompt(attn, sigma, mask_th, up_w, up_h, *, want_smooth=False):
     return coarse, points, smooth
 
 
+def sam_attn_box_prompt(attn, sigma, mask_th, n_open, up_w, up_h, *, want_smooth=False):
+    """LMD's box prompt and opened coarse mask from the object token's attention maps (lgd_sam_attn_box_prompt_f32).  attn
+    fp32 [N, hm, wm] -> (coarse uint8 [N, hm, wm] after n_open erosions and n_open dilations, boxes fp32 [N, 4] =
+    (xmin * up_w, ymin * up_h, xmax * up_w, ymax * up_h) of the mask's bounding box grown by one, empty int32 [N] = 1
+    where the opened mask has no pixel (its box is 0, 0, 0, 0)[, smoothed map]).  Nothing is read back."""
+    if attn.dtype != F32 or attn.dim() != 3 or not attn.is_contiguous():
+        raise RuntimeError("sam_attn_box_prompt: attn is a contiguous fp32 [N, hm, wm] tensor")
+    N, hm, wm = attn.shape
+    coarse = torch.empty((N, hm, wm), device=attn.device, dtype=torch.uint8)
+    boxes = torch.empty((N, 4), device=attn.device, dtype=F32)
+    empty = torch.empty((N,), device=attn.device, dtype=torch.int32)
+    smooth = torch.empty_like(attn) if want_smooth else None
+    _call("lgd_sam_attn_box_prompt_f32", _p(attn), N, hm, wm, float(sigma), float(mask_th), int(n_open), int(up_w),
+          int(up_h), _p(coarse), _p(boxes), _p(empty), _p(smooth), _stream())
+    return (coarse, boxes, empty, smooth) if want_smooth else (coarse, boxes, empty)
+
+
 # ---------------------------------------------------------------------------------------------
 # the hand-off between the two stages of LMD / LMD+ (csrc/handoff.hip; the tables are packed by lgd_amd.handoff)
 # ---------------------------------------------------------------------------------------------

@@ -161,10 +161,13 @@ def _so_mask(refiner, kind, image, box, L, token_attn=None):
 
 def _batched(refiner, kind):
     """Whether the refiner takes all boxes in one call (SamRefiner.boxes / .attns) or one at a time (.box / .attn).  The
-    box prompt of an attention map (`use_box_input`) is always made per image."""
+    box prompt of an attention map (`use_box_input`) is made per image unless the refiner opted in to the device path
+    (`attn_box="device"`)."""
     if refiner is None or not getattr(refiner, "batched", False):
         return False
-    return kind == "box" or not getattr(refiner, "attn_kw", {}).get("use_box_input", False)
+    if kind == "box" or not getattr(refiner, "attn_kw", {}).get("use_box_input", False):
+        return True
+    return getattr(refiner, "attn_box", "host") == "device"
 
 
 def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ratio, guidance_attn_keys, use_fast_schedule,

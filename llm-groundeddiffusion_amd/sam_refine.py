@@ -15,6 +15,8 @@ Reference quirks kept on purpose: `sam()` returns the predicted IoUs of image 0 
 `sam_refine_boxes` scores every box of every image with them (the plugins call it with one image and one box);
 `sam_refine_attn(use_box_input=True)` hands the processor a two-level box list (:141-144), which transformers refuses
 ("Input boxes must be a list of list of list of floating points") — the plugins' default is the point prompt.
+`SamRefiner(use_box_input=True, attn_box="device").attns` builds that box on the device and hands the model a proper
+(N, 1, 4) tensor.
 """
 import numpy as np
 import torch
@@ -292,17 +294,26 @@ class SamRefiner:
     MODEL_CHUNK images -> ops.sam_mask_tail (for `attns`, ops.sam_attn_prompt first).  They need the device processor.
     `batched` tells the pipelines which pair to call: None = on exactly when the processor is `DeviceSamProcessor`
     (measured faster there), False = the per-image path only.  `attns` covers the point prompt; with
-    `use_box_input` the attention maps go through `attn` whatever `batched` says (the box prompt needs an erosion, which
-    is host code).  Each item is scored with its own predicted IoUs."""
+    `use_box_input` the attention maps go through `attn` whatever `batched` says, unless `attn_box="device"` opts in to
+    the box prompt made on the device (ops.sam_attn_box_prompt: smoothing, threshold, opening and bounding box in one
+    launch), which `attns` then serves for the whole batch.  `attn_box="host"` (the default) keeps `attn`'s scipy
+    opening; "device" needs the device processor.  Each item is scored with its own predicted IoUs."""
     MODEL_CHUNK = 8
+    ATTN_BOXES = ("host", "device")
 
     def __init__(self, sam_model_dict, height=512, width=512, discourage_mask_below_confidence=0.85,
                  discourage_mask_below_coarse_iou=0.25, use_box_input=False, gaussian_sigma=None, mask_th_for_box=0.05,
-                 n_erode_dilate_mask_for_box=1, mask_th_for_point=0.25, verbose=False, batched=None):
+                 n_erode_dilate_mask_for_box=1, mask_th_for_point=0.25, verbose=False, batched=None,
+                 attn_box="host"):
         self.md, self.verbose = sam_model_dict, verbose
         on_device = bool(getattr(sam_model_dict["sam_processor"], "on_device", False))
         if batched and not on_device:
             raise ValueError("batched refinement needs the device processor (wrap_sam(..., sam_processor='device'))")
+        if attn_box not in self.ATTN_BOXES:
+            raise ValueError(f"SamRefiner: attn_box {attn_box!r} is none of {self.ATTN_BOXES}")
+        if attn_box == "device" and not on_device:
+            raise ValueError("attn_box='device' needs the device processor (wrap_sam(..., sam_processor='device'))")
+        self.attn_box = attn_box
         self.batched = on_device if batched is None else bool(batched)
         self.common = dict(height=height, width=width, H=height // 8, W=width // 8,
                            discourage_mask_below_confidence=discourage_mask_below_confidence,
@@ -368,15 +379,32 @@ class SamRefiner:
 
     def attns(self, images, token_attns):
         """LMD for N (image, attention map) pairs: token_attns fp32 (N, hm, wm), a device tensor or a list of arrays ->
-        (bool masks (N, H/8, W/8), confidences fp32 (N)), both on the device.  The point-prompt branch only."""
+        (bool masks (N, H/8, W/8), confidences fp32 (N)), both on the device.  The point-prompt branch, and with
+        `attn_box="device"` the box-prompt branch (`use_box_input`): the candidates are then scored against the OPENED
+        mask, as `attn` scores them.
+
+        The box branch reads the N `empty` flags of ops.sam_attn_box_prompt once, before the model runs: 4 N bytes, the
+        only host read of the call.  The reference fails on an empty opened mask (`min()` of an empty sequence in
+        utils.binary_mask_to_box, which generate.py logs before it skips the prompt); running SAM on the zero box and
+        handing on its mask would silently differ from that, so `attns` raises ValueError naming the empty items."""
         from . import ops
-        if self.attn_kw["use_box_input"]:
-            raise NotImplementedError("attns() covers the point prompt; the box prompt of the attention map is attn()'s")
+        box = bool(self.attn_kw["use_box_input"])
+        if box and self.attn_box != "device":
+            raise NotImplementedError("attns() covers the point prompt; the box prompt of the attention map is attn()'s "
+                                      "unless the refiner was built with attn_box='device'")
         dev = self._device_processor().dev
         if not torch.is_tensor(token_attns):
             token_attns = torch.from_numpy(np.stack([np.asarray(t, dtype=np.float32) for t in token_attns]))
         maps = _upload(token_attns, dev).to(torch.float32).contiguous()
         up_w, up_h = self.common["height"] // maps.shape[2], self.common["width"] // maps.shape[1]     # (w, h) as attn()
+        if box:
+            coarse, boxes, empty = ops.sam_attn_box_prompt(maps, self.attn_kw["gaussian_sigma"], self.attn_kw["mask_th_for_box"],
+                                                           self.attn_kw["n_erode_dilate_mask_for_box"], up_w, up_h)
+            gone = torch.nonzero(empty).flatten().tolist()         # the one host read: 4 N bytes
+            if gone:
+                raise ValueError(f"The mask is empty: the opened attention mask of item(s) {gone} of {maps.shape[0]} has no "
+                                 "pixel, so there is no box to prompt SAM with")
+            return self._tail(images, coarse, input_boxes=boxes.reshape(-1, 1, 4))
         coarse, points, _ = ops.sam_attn_prompt(maps, self.attn_kw["gaussian_sigma"], self.attn_kw["mask_th_for_point"],
                                                 up_w, up_h)
         return self._tail(images, coarse, input_points=points.reshape(-1, 1, 1, 2))
