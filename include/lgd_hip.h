@@ -485,6 +485,28 @@ int lgd_cfg_multistep_step_f32(const float* eps, const float* x, float* x_out, f
  * row dyn[0], hist holds dyn[0] + 2 latents and shares no byte with another operand. */
 int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_out, float* ets, float* cur_sample,
                           const float* coef_table, const int32_t* dyn, float* hist, int B, int C, int HW, void* stream);
+/* The same fused step for the order-4 LINEAR MULTISTEP sampler in sigma space (additive export: LGD_ABI_VERSION stays
+ * 12) — [ext] diffusers 0.18.0 LMSDiscreteScheduler, one of the k-diffusion samplers `generate.py --scheduler NAME` hands
+ * to models.load_sd(scheduler_cls=...) (models/models.py:50-53).  For that family the loops of models/pipelines.py call
+ * scheduler.scale_model_input before the UNet (:42, :196, :261, :422, :573: lgd_scale_rows_f32 here) and
+ * latent_backward_guidance takes its `sigmas` branch, latents - grad * sigmas[index]**2 (:60-61: lgd_axpy_f32 here).  One
+ * launch per step i = dyn[0], after the UNet:
+ *   m = eu + gs*(ec-eu);  x0 = c0 x + c1 m          (epsilon: 1, -sigma;  v: 1/(sigma^2+1), -sigma/sqrt(sigma^2+1))
+ *   d = (x - x0) * inv_sigma                         (the derivative of step i)
+ *   x' = x + w[slot] d + sum_{s != slot} w[s] ring[s]
+ *   ring[slot] = d;  blend / hist as lgd_cfg_ddim_step_f32.   x_out may alias x.
+ * w holds the LMS coefficients (integrals of the Lagrange basis polynomials over [sigma_i, sigma_{i+1}]) permuted onto
+ * ring slots by the host, the derivative of step j living in slot j % 4; a weight is 0 where the order min(i+1, 4) does
+ * not reach.  coef_table: device fp32 [T][16] = {c0, c1, inv_sigma, w[0], w[1], w[2], w[3], guidance_scale, slot, 0...}
+ * (host: scheduler.LMSDiscreteScheduler.lms_table); the slot is taken modulo 4.  ring: fp32 [4][B,C,L,L].  Slot `slot` is
+ * never read and always written; another slot is read only where its weight is not 0; nothing else of ring is written.
+ * Preconditions: those of lgd_cfg_ddim_step_f32, and ring non-NULL; B*C*HW % 4 == 0; eps, x, x_out, ring and hist
+ * 16-byte aligned.  The ring (four latents) is apart from eps, x, x_out, mask, row 0 of coef_table, dyn and the first two
+ * latents of frozen_ref and hist.  Not checked (the step count is not an argument): coef_table holds row dyn[0], frozen_ref
+ * and hist hold dyn[0] + 2 latents and share no byte with x_out, the ring or each other. */
+int lgd_cfg_lms_step_f32(const float* eps, const float* x, float* x_out, float* ring, const float* coef_table,
+                         const int32_t* dyn, const float* frozen_ref, const float* mask, float* hist, int B, int C, int HW,
+                         void* stream);
 /* One MultiDiffusion step (additive export: LGD_ABI_VERSION stays 12) — generation/multidiffusion.py:226-289 of the
  * reference with its single 512x512 view, indep_uncond=True and normalization=False (count == 1), DDIM eta 0.  P region
  * prompts (row 0 the background), padded to Pp UNet rows; one launch after the UNet of step i = dyn[0]:

@@ -86,6 +86,7 @@ SIGNATURES = {
     "lgd_cfg_ddim_step_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lgd_cfg_multistep_step_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lgd_cfg_plms_step_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lgd_cfg_lms_step_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lgd_multidiffusion_step_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lgd_multidiffusion_views_f32": [_P] * 12 + [_I] * 14 + [_P],
     "lgd_axpy_f32": [_P, _P, _P, _P, _I, _P, _L, _L, _P],

@@ -386,6 +386,60 @@ __global__ __launch_bounds__(256) void cfg_plms_kernel(
   }
 }
 
+// Classifier-free guidance + one step of the order-4 linear multistep sampler in sigma space ([ext] diffusers
+// LMSDiscreteScheduler) + frozen-mask blend + history: see lgd_hip.h.  Four fp32 lanes per thread (16-byte accesses),
+// grid-stride over n/4 vectors; coefficient row dyn[0] = {c0, c1, 1/sigma, w_0..w_3 by ring slot, gs, slot, ...}.  The
+// host has permuted the LMS coefficients onto slots.  This step's own slot is not read (its weight multiplies the
+// fresh derivative); another slot is read only where its weight is non-zero, and the own slot is written after them.
+__global__ __launch_bounds__(256) void cfg_lms_kernel(
+    const float* __restrict__ eps, const float* x, float* x_out, float* __restrict__ ring,
+    const float* __restrict__ coef_table, const int32_t* __restrict__ dyn, const float* __restrict__ frozen_ref,
+    const float* __restrict__ mask, float* __restrict__ hist, long n, int CHW, int HW) {
+  const int step = dyn[0];
+  const int frozen_steps = dyn[1];
+  const float* c = coef_table + step * 16;
+  const float c0 = c[0], c1 = c[1], inv_sigma = c[2], gs = c[7];
+  const int slot = (int)c[8] & 3;  // a slot outside the ring cannot address past it
+  const float w0 = slot == 0 ? 0.f : c[3], w1 = slot == 1 ? 0.f : c[4], w2 = slot == 2 ? 0.f : c[5],
+              w3 = slot == 3 ? 0.f : c[6];
+  const float w_self = c[3 + slot];
+  const bool blend = frozen_ref && mask && step < frozen_steps;
+  const long nv = n >> 2;
+  const f32x4* eu4 = reinterpret_cast<const f32x4*>(eps);
+  const f32x4* ec4 = reinterpret_cast<const f32x4*>(eps + n);
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+  f32x4* r0 = reinterpret_cast<f32x4*>(ring);
+  f32x4* r1 = reinterpret_cast<f32x4*>(ring + n);
+  f32x4* r2 = reinterpret_cast<f32x4*>(ring + 2 * n);
+  f32x4* r3 = reinterpret_cast<f32x4*>(ring + 3 * n);
+  f32x4* rs = reinterpret_cast<f32x4*>(ring + (long)slot * n);
+  for (long v = blockIdx.x * 256L + threadIdx.x; v < nv; v += gridDim.x * 256L) {
+    const f32x4 eu = eu4[v], ec = ec4[v];
+    const f32x4 m = eu + gs * (ec - eu);
+    const f32x4 xv = x4[v];
+    const f32x4 x0 = c0 * xv + c1 * m;
+    const f32x4 d = (xv - x0) * inv_sigma;
+    f32x4 xn = xv + w_self * d;
+    if (w0 != 0.f) xn += w0 * r0[v];
+    if (w1 != 0.f) xn += w1 * r1[v];
+    if (w2 != 0.f) xn += w2 * r2[v];
+    if (w3 != 0.f) xn += w3 * r3[v];
+    rs[v] = d;
+    if (blend) {
+      // CHW % 4 == 0 is not given, HW % 4 == 0 neither: the four lanes may straddle an image or a mask row
+      const long e = v << 2;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const long i = e + k;
+        const float mk = mask[(i / CHW) * HW + (i % HW)];
+        xn[k] = frozen_ref[(long)(step + 1) * n + i] * mk + xn[k] * (1.f - mk);
+      }
+    }
+    reinterpret_cast<f32x4*>(x_out)[v] = xn;
+    if (hist) reinterpret_cast<f32x4*>(hist + (long)(step + 1) * n)[v] = xn;
+  }
+}
+
 // One MultiDiffusion step over P region prompts (generation/multidiffusion.py of the reference, one 512x512 view,
 // indep_uncond, no normalization): see lgd_hip.h.  Four fp32 lanes of one latent plane per thread (16-byte accesses;
 // HW % 4 == 0, so the four lanes share one mask row), one wave per workgroup so that the 16K-element SD latent spreads
@@ -1013,6 +1067,29 @@ extern "C" int lgd_cfg_plms_step_f32(const float* eps, const float* x, float* x_
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(cfg_plms_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eps,
                      x, x_out, ets, cur_sample, coef_table, dyn, hist, n);
+  return lgd_check_launch();
+}
+
+extern "C" int lgd_cfg_lms_step_f32(const float* eps, const float* x, float* x_out, float* ring, const float* coef_table,
+                                    const int32_t* dyn, const float* frozen_ref, const float* mask, float* hist, int B,
+                                    int C, int HW, void* stream) {
+  if (!ring || bad_step_f32(eps, x, x_out, coef_table, dyn, frozen_ref, mask, hist, B, C, HW)) return LGD_ERR_ARG;
+  const long n = (long)B * C * HW;
+  if ((n & 3) || misaligned(eps, 16) || misaligned(x, 16) || misaligned(x_out, 16) || misaligned(ring, 16) ||
+      misaligned(hist, 16))
+    return LGD_ERR_ARG;  // 16-byte vectors: every latent starts on a vector boundary
+  {
+    const int64_t nb = (int64_t)n * 4;  // the ring is read and rewritten: apart from every other operand
+    if (overlaps(ring, 4 * nb, eps, 2 * nb) || overlaps(ring, 4 * nb, x, nb) || overlaps(ring, 4 * nb, x_out, nb) ||
+        overlaps(ring, 4 * nb, mask, (int64_t)B * HW * 4) || overlaps(ring, 4 * nb, coef_table, 16 * 4) ||
+        overlaps(ring, 4 * nb, dyn, 2 * 4))
+      return LGD_ERR_ARG;
+    // frozen_ref and hist hold step + 2 latents, and the step is read on the device: the two every step addresses
+    if (overlaps(ring, 4 * nb, frozen_ref, 2 * nb) || overlaps(ring, 4 * nb, hist, 2 * nb)) return LGD_ERR_ARG;
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  hipLaunchKernelGGL(cfg_lms_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eps, x,
+                     x_out, ring, coef_table, dyn, frozen_ref, mask, hist, n, C * HW, HW);
   return lgd_check_launch();
 }
 

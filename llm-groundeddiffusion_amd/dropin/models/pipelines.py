@@ -5,8 +5,9 @@ Implemented: latent_backward_guidance :16-82, decode :117-127, generate_semantic
 gligen_enable_fuser :280-283, prepare_gligen_condition :285-321, generate_gligen :323-473,
 generate_partial_frozen :541-599, and their `use_boxdiff=True` branch (:187-188, :564-565: one gradient step on the
 BoxDiff energy of utils/boxdiff.py per denoising step, csrc/boxdiff.hip), and generate :250-279 (the plain CFG loop,
-under the DDIM, DPM-Solver++ or PNDM scheduler found at `model_dict[scheduler_key]`; PNDM runs the fused PLMS step of
-csrc/misc.hip), and DDIM inversion: encode :84-114 (the HIP VAE encoder; lgd_image_u8_to_nhwc8_f16 and
+under the DDIM, DPM-Solver++, PNDM, Euler or LMS scheduler found at `model_dict[scheduler_key]`; PNDM runs the fused PLMS
+step and LMS the fused LMS step of csrc/misc.hip; the guided loops run under `model_dict.scheduler`, whichever of DDIM,
+DPM-Solver++, Euler and LMS models.resolve_scheduler put there), and DDIM inversion: encode :84-114 (the HIP VAE encoder; lgd_image_u8_to_nhwc8_f16 and
 lgd_vae_sample_f32 of csrc/misc.hip, so that no torch arithmetic sits between the uint8 image and the scaled latents),
 get_inverse_timesteps :476-487 and invert :489-539 (lgd_amd.pipeline.invert_batch under `model_dict.inverse_scheduler`,
 which load_sd / build_model_dict / load_synthetic attach with load_inverse_scheduler=True)."""
@@ -17,6 +18,13 @@ import utils
 from lgd_amd.sampler import DEFAULT_GUIDANCE_ATTN_KEYS, prepare_gligen_condition as _gligen_condition  # noqa: F401
 from .models import process_input_embeddings, torch_device  # noqa: F401
 from .unet_2d_condition import GatedSelfAttentionDense
+
+
+def _scheduler(model_dict, key="scheduler"):
+    """The project's scheduler at model_dict[key], the one the call runs under (the reference reads it per call, so a
+    caller may have swapped it since the sampler was built); a foreign object (no `step_kind`) leaves the sampler's own."""
+    sch = model_dict.get(key) if isinstance(model_dict, dict) else getattr(model_dict, key, None)
+    return sch if hasattr(sch, "step_kind") else None
 
 
 def _sampler(model_dict):
@@ -116,7 +124,8 @@ def latent_backward_guidance(scheduler, unet, cond_embeddings, index, bboxes, ob
         z = lambda x: torch.cat([x, x])          # the sampler expects the [uncond; cond] pair; guidance uses item 0
         glt = (z(gl["boxes"]), z(gl["positive_embeddings"]), z(gl["masks"]))
     lat, new_loss, _ = sm.guidance_only(latents, cond_embeddings, T, index, dict(state=gs) if gs else
-                                        dict(bboxes=[], object_positions=[]), gligen=glt, fuser=fuser)
+                                        dict(bboxes=[], object_positions=[]), gligen=glt, fuser=fuser,
+                                        scheduler=scheduler if hasattr(scheduler, "step_kind") else None)
     return lat.to(latents.dtype), torch.tensor(new_loss if new_loss is not None else float(loss))
 
 
@@ -218,7 +227,7 @@ def generate_semantic_guidance(model_dict, latents, input_embeddings, num_infere
     r = sm.denoise(latents, text_embeddings, T, guidance_scale=guidance_scale, guidance=guid,
                    saved_cross_attn_keys=_keys_to_save(sm, return_saved_cross_attn, saved_cross_attn_keys),
                    return_cond_ca_only=return_cond_ca_only, return_token_ca_only=return_token_ca_only,
-                   **_fast_args(dynamic_num_inference_steps, fast_after_steps, fast_rate))
+                   scheduler=_scheduler(model_dict), **_fast_args(dynamic_num_inference_steps, fast_after_steps, fast_rate))
     T = r["latents_all"].shape[0] - 1 if r["latents_all"] is not None else T       # steps actually run
     return _finish(sm, model_dict, r, T, ret_saved=return_saved_cross_attn, return_box_vis=return_box_vis, bboxes=bboxes,
                    phrases=phrases, save_all_latents=save_all_latents, offload=offload_latents_to_cpu)
@@ -252,7 +261,7 @@ def generate_gligen(model_dict, latents, input_embeddings, num_inference_steps, 
                    frozen_steps=frozen_steps if frozen_mask is not None else 0, frozen_mask=frozen_mask,
                    saved_cross_attn_keys=_keys_to_save(sm, return_saved_cross_attn, saved_cross_attn_keys),
                    return_cond_ca_only=return_cond_ca_only, return_token_ca_only=return_token_ca_only,
-                   **_fast_args(dynamic_num_inference_steps, fast_after_steps, fast_rate))
+                   scheduler=_scheduler(model_dict), **_fast_args(dynamic_num_inference_steps, fast_after_steps, fast_rate))
     T = r["latents_all"].shape[0] - 1 if r["latents_all"] is not None else T       # steps actually run
     gligen_enable_fuser(model_dict.unet, False)           # pipelines.py:459-460
     return _finish(sm, model_dict, r, T, ret_saved=return_saved_cross_attn, return_box_vis=return_box_vis, bboxes=bboxes,
@@ -275,7 +284,8 @@ def generate_partial_frozen(model_dict, latents_all, frozen_mask, input_embeddin
         g["ref_maps"] = _ref_maps_from_saved(sm, ref, bboxes, keys, L, T)
         guid = g
     r = sm.denoise(latents_all, text_embeddings, T, guidance_scale=guidance_scale, guidance=guid,
-                   frozen_steps=frozen_steps, frozen_mask=frozen_mask, save_all_latents=False)
+                   frozen_steps=frozen_steps, frozen_mask=frozen_mask, save_all_latents=False,
+                   scheduler=_scheduler(model_dict))
     images = decode(model_dict.vae, r["latents"]) if model_dict.vae is not None else None
     return r["latents"], images
 
@@ -307,7 +317,7 @@ def invert(model_dict, latents, input_embeddings, num_inference_steps, guidance_
 def generate(model_dict, latents, input_embeddings, num_inference_steps, guidance_scale=7.5, no_set_timesteps=False,
              scheduler_key='scheduler'):
     """pipelines.py:250-279 -> (latents, images): classifier-free guidance with `model_dict[scheduler_key]` (DDIM,
-    DPMSolverMultistep or PNDM), every image of the batch an independent job of the sampler.  no_set_timesteps: the
+    DPMSolverMultistep, PNDM, EulerDiscrete or LMSDiscrete), every image of the batch an independent job of the sampler.  no_set_timesteps: the
     scheduler's schedule as it stands is run; it must be the one set_timesteps(num_inference_steps it was set for)
     produces, the only kind the sampler's tables express."""
     from lgd_amd.pipeline import sd_generate_batch

@@ -8,7 +8,7 @@ import torch
 
 from . import ops
 from .lanes import GATE
-from .scheduler import DDIM, MULTISTEP, PLMS
+from .scheduler import DDIM, LMS, MULTISTEP, PLMS
 
 F32 = torch.float32
 
@@ -42,7 +42,7 @@ class HipGraph:
 class StepKernel:
     """The fused CFG + scheduler step of one kind on one state's latents: its coefficient table (`capacity` rows) and the
     extra buffers that kernel carries between steps, at fixed addresses because captured graphs bake them."""
-    COLS = {DDIM: 4, MULTISTEP: 8, PLMS: 16}
+    COLS = {DDIM: 4, MULTISTEP: 8, PLMS: 16, LMS: 16}
 
     def __init__(self, kind, lat, capacity):
         self.kind = kind
@@ -52,11 +52,15 @@ class StepKernel:
         elif kind == PLMS:                                  # ring of the last three outputs, saved sample
             self.ets = torch.zeros((3,) + tuple(lat.shape), device=lat.device, dtype=F32)
             self.cur_sample = torch.zeros_like(lat)
+        elif kind == LMS:                                   # ring of the last four derivatives
+            self.ring = torch.zeros((4,) + tuple(lat.shape), device=lat.device, dtype=F32)
 
     def load(self, scheduler, guidance_scale, timesteps):
         dev = self.tab.device
         if self.kind == PLMS:
             rows = scheduler.plms_table(guidance_scale, dev, timesteps=timesteps)
+        elif self.kind == LMS:
+            rows = scheduler.lms_table(guidance_scale, dev, timesteps=timesteps)
         elif self.kind == MULTISTEP:
             rows = scheduler.multistep_table(guidance_scale, dev, timesteps=timesteps)
         else:
@@ -67,6 +71,8 @@ class StepKernel:
     def launch(self, eps, lat, dyn, frozen_ref=None, mask=None, hist=None):
         if self.kind == PLMS:
             ops.cfg_plms_step(eps, lat, lat, self.ets, self.cur_sample, self.tab, dyn, hist=hist)
+        elif self.kind == LMS:
+            ops.cfg_lms_step(eps, lat, lat, self.ring, self.tab, dyn, frozen_ref=frozen_ref, mask=mask, hist=hist)
         elif self.kind == MULTISTEP:
             ops.cfg_multistep_step(eps, lat, lat, self.x0_prev, self.tab, dyn, frozen_ref=frozen_ref, mask=mask, hist=hist)
         else:

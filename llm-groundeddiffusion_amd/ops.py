@@ -930,6 +930,18 @@ def cfg_plms_step(eps, x, x_out, ets, cur_sample, coef_table, dyn, *, hist=None)
     return x_out
 
 
+def cfg_lms_step(eps, x, x_out, ring, coef_table, dyn, *, frozen_ref=None, mask=None, hist=None):
+    """CFG + one step of the order-4 linear multistep sampler in sigma space (LMSDiscreteScheduler); coef_table fp32
+    [T][16], ring fp32 [4, *x.shape], see lgd_hip.h."""
+    _step_operands("cfg_lms_step", eps, x, x_out, coef_table, 16, dyn, frozen_ref, mask, hist)
+    B, C_, L, _ = x.shape
+    _operands("cfg_lms_step", ("ring", ring, F32, 4 * x.numel()))
+    _prof("cfg_lms_kernel", 4.0 * x.numel() * 9,
+          lambda: _call("lgd_cfg_lms_step_f32", _p(eps), _p(x), _p(x_out), _p(ring), _p(coef_table), _p(dyn),
+                        _p(frozen_ref), _p(mask), _p(hist), B, C_, L * L, _stream()))
+    return x_out
+
+
 def _md_operands(fn, eps, x_in, latent, masks, coef_table, dyn, bg, noise, picks, hist, P, plane, bg_plane, n_picks,
                  n_steps, n_boot, prep):
     """The operands the two MultiDiffusion entry points share: eps the size of x_in (not read with prep), masks at least P

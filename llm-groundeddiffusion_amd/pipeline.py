@@ -88,8 +88,12 @@ class CachedLayout:
             bg_seed=index, fg_seed_start=index + 123456789)                      # generate.py:226-229,317-344
 
 
-def get_input_latents_list(bg_seed, fg_seed_start, so_boxes, fg_blending_ratio, in_channels=4, H=64, W=64):
-    return _input_latents_list(bg_seed, fg_seed_start, so_boxes, fg_blending_ratio, in_channels, H, W)
+def get_input_latents_list(bg_seed, fg_seed_start, so_boxes, fg_blending_ratio, in_channels=4, H=64, W=64,
+                           init_noise_sigma=1.0):
+    """utils/latents.py:120-161: unit noise composed per box, times the scheduler's init_noise_sigma (:154,:158; 1 for
+    DDIM, DPM-Solver++ and PNDM, sigma_max for the sigma-space samplers)."""
+    return _input_latents_list(bg_seed, fg_seed_start, so_boxes, fg_blending_ratio, in_channels, H, W,
+                               init_noise_sigma=float(init_noise_sigma))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -180,7 +184,8 @@ def _two_stage_setup(sampler, lays, T, height, frozen_step_ratio, fg_blending_ra
     keys = [tuple(k) for k in (guidance_attn_keys or DEFAULT_GUIDANCE_ATTN_KEYS)]
     so_boxes = [_centered_so_boxes(lay, so_center_box, **centered_box_kwargs) for lay in lays]    # lmd.py:314-324
     prep = [get_input_latents_list(lay.bg_seed, lay.fg_seed_start, so_boxes[li], fg_blending_ratio,
-                                   sampler.eng.cfg.in_channels, L, L) for li, lay in enumerate(lays)]
+                                   sampler.eng.cfg.in_channels, L, L, init_noise_sigma=sampler.scheduler.init_noise_sigma)
+            for li, lay in enumerate(lays)]
     fast_after = (max(frozen_steps, overall_max_index_step) if use_ref_ca else frozen_steps) if use_fast_schedule else None
     comp_steps = fast_after if use_fast_schedule else T                       # latents.py:46-48,77-78
     return L, frozen_steps, keys, so_boxes, prep, fast_after, comp_steps
@@ -412,7 +417,9 @@ def _single_shot(sampler, lays, keys, guidance_kw, *, num_inference_steps, guida
     C = sampler.eng.cfg.in_channels
     jobs = []
     for lay in lays:
-        lat = seeded_noise(lay.bg_seed, C, L, L) if start is None else torch.as_tensor(start[len(jobs)]).float()
+        # utils/latents.py:20-22: unit noise times init_noise_sigma (1 unless the scheduler works in sigma space)
+        lat = seeded_noise(lay.bg_seed, C, L, L) * float(sampler.scheduler.init_noise_sigma) if start is None else \
+            torch.as_tensor(start[len(jobs)]).float()
         overall_bboxes = [[list(lay.boxes[i]) for i in grp] for grp in lay.overall_groups]
         guid = None
         if overall_bboxes:
@@ -480,7 +487,7 @@ def sd_generate_batch(sampler: LMDSampler, texts, latents, num_inference_steps=5
     """Plain Stable Diffusion, the `sd` baseline (generation/stable_diffusion_generate.py -> StableDiffusionPipeline, whose
     denoising loop is models/pipelines.py:257-273): classifier-free guidance and the checkpoint's own sampler, by default
     PLMS (scheduler.PNDMScheduler.from_config of the sampler's scheduler; n steps = n + 1 UNet evaluations).  `scheduler`
-    may also be a DDIMScheduler / DPMSolverMultistepScheduler.  Independent images share UNet calls (denoise_batch:
+    may also be a DDIMScheduler / DPMSolverMultistepScheduler / EulerDiscreteScheduler / LMSDiscreteScheduler.  Independent images share UNet calls (denoise_batch:
     up to max_batch per call, padded to the buckets).
 
     texts: per image (2,77,Cx) = [uncond; cond];  latents: per image (1,C,L,L), or one (N,C,L,L) tensor, already scaled

@@ -10,8 +10,9 @@ Per step (all on one HIP stream, no host round trip except the reference's own `
                     grad-plan forward (B=1, cond only, stops at the last guidance key)
                     energy kernel  -> loss, d loss / d maps
                     grad-plan backward -> d loss / d latents ; latents -= sqrt(1-abar_t) * grad
+                    (a sigma-space scheduler: the plan's input is latents * c_in, latents -= sigma_t^2 * c_in * grad)
     main plan forward (B=2: [uncond; cond], optional cross-attention map capture)
-    fused CFG + DDIM + frozen-mask blend + history write
+    fused CFG + scheduler step (DDIM, DPM-Solver++ / Euler, PLMS or LMS) + frozen-mask blend + history write
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -21,7 +22,7 @@ from . import ops
 from .energy import BoxDiffTables, EnergyTables
 from .lanes import GATE
 from .loop import HipGraph, LoopState, StateCache, clamp_steps, run_steps  # noqa: F401 (HipGraph: importable from here)
-from .scheduler import MULTISTEP, PLMS, DDIMScheduler
+from .scheduler import C_IN_GCOL, LMS, MULTISTEP, PLMS, DDIMScheduler
 from .unet import N_OBJ_TOKENS, UNetEngine
 
 F32 = torch.float32
@@ -67,6 +68,11 @@ class GuidanceState:
         if isinstance(m, (list, tuple)):
             m = m[index] if len(m) > index else m[-1]
         return int(m)
+
+
+def _scaled(scheduler) -> bool:
+    """The scheduler scales the model input (scheduler.scales_model_input: the sigma-space samplers)."""
+    return bool(getattr(scheduler, "scales_model_input", False))
 
 
 class _State(LoopState):
@@ -221,35 +227,48 @@ class LMDSampler:
         return self._states.get((nb, C, L), lambda: _State(self.dev, nb, C, L, max(T, self.STATE_MIN_STEPS)),
                                 fits=lambda st: st.capacity >= T)
 
-    def _main_pass(self, plan, st: _State, step, nb: int):
-        """The launch sequence of one denoising step for nb images: CFG pair in, UNet, fused CFG + scheduler step."""
+    def _main_pass(self, plan, st: _State, step, nb: int, scaled: bool = False):
+        """The launch sequence of one denoising step for nb images: CFG pair in, UNet, fused CFG + scheduler step.
+        scaled: a sigma-space scheduler (scheduler.scales_model_input) — the pair is written by ONE lgd_scale_rows_f32 launch,
+        latents * c_in of step dyn[0] from st.gtab (scale_model_input, pipelines.py:196,261,422,573), in place of the copies."""
         def main_fn():
-            ops.copy_(plan.latents_in[:nb], st.lat)                          # torch.cat([latents]*2)
-            if not plan.latents_pair:                                        # a CFG pair plan reads the first half only
-                ops.copy_(plan.latents_in[nb:], st.lat)
+            if scaled:
+                pair = plan.latents_pair                                     # a CFG pair plan reads the first half only
+                ops.scale_rows(st.lat, plan.latents_in[:nb] if pair else plan.latents_in, st.gtab, self.eng.dyn, C_IN_GCOL,
+                               reps=1 if pair else 2)
+            else:
+                ops.copy_(plan.latents_in[:nb], st.lat)                      # torch.cat([latents]*2)
+                if not plan.latents_pair:
+                    ops.copy_(plan.latents_in[nb:], st.lat)
             plan.forward()
             step.launch(plan.eps_out, st.lat, self.eng.dyn, frozen_ref=st.frozen_ref, mask=st.mask, hist=st.hist)
         return main_fn
 
-    def _guide_pass(self, st: _State, nb: int, L: int, fuser: bool, gkeys):
+    def _guide_pass(self, st: _State, nb: int, L: int, fuser: bool, gkeys, scaled: bool = False):
         """(plan, forward, backward + latent update) of the guidance pass for a batch of nb images; the energy launch
         goes between the two: B=nb grad plan on the conditional text (second half of the text batch) and the
-        zero-masked GLIGEN half (pipelines.py:381-384)."""
+        zero-masked GLIGEN half (pipelines.py:381-384).  scaled: a sigma-space scheduler — the grad plan's input is
+        latents * c_in (pipelines.py:42), written into the plan's own fixed-address input; the gradient it returns is with
+        respect to that input, and column 0 of st.gtab carries the c_in of the chain rule next to sigma^2 (:60-61)."""
         eng = self.eng
         pg = eng.plan(nb, L, grad=True, fuser=fuser, stop_key=eng.last_key(gkeys), save_keys=gkeys,
                       text_batch_offset=nb, obj_batch_offset=0)
 
         def g_fwd():
-            pg.forward(st.lat)
+            if scaled:
+                ops.scale_rows(st.lat, pg.latents_in, st.gtab, eng.dyn, C_IN_GCOL)
+                pg.forward()
+            else:
+                pg.forward(st.lat)
 
         def g_bwd():
             grad = pg.backward(self.grad_scale)
             ops.axpy(grad, st.lat, st.gtab, eng.dyn, 0, active=st.active)       # pipelines.py:62-69
         return pg, g_fwd, g_bwd
 
-    def _guide_runners(self, st: _State, nb: int, L: int, fuser: bool, gkeys):
-        pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, fuser, gkeys)
-        name = ("guide", fuser, tuple(gkeys))
+    def _guide_runners(self, st: _State, nb: int, L: int, fuser: bool, gkeys, scaled: bool = False):
+        pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, fuser, gkeys, scaled)
+        name = ("guide", fuser, tuple(gkeys)) + (("scaled",) if scaled else ())     # two launch sequences, two graphs
         return pg, st.runner(name + ("fwd",), g_fwd, self.use_graphs), st.runner(name + ("bwd",), g_bwd, self.use_graphs)
 
     def _count(self, kind, fuser, nb):
@@ -290,10 +309,10 @@ class LMDSampler:
     # ------------------------------------------------------------------------------------------
     def guidance_only(self, latents: torch.Tensor, cond_embeddings: torch.Tensor, num_inference_steps: int,
                       index: int, guidance: dict, *, gligen=None, fuser: bool = False,
-                      trace: Optional[list] = None):
-        """One latent_backward_guidance call (pipelines.py:16-82) at step `index` of a T-step schedule.
-        Returns (latents, loss, state) like the reference."""
-        eng, sch, dev = self.eng, self.scheduler, self.dev
+                      trace: Optional[list] = None, scheduler=None):
+        """One latent_backward_guidance call (pipelines.py:16-82) at step `index` of a T-step schedule, under `scheduler`
+        (None: the sampler's own).  Returns (latents, loss, state) like the reference."""
+        eng, sch, dev = self.eng, self.scheduler if scheduler is None else scheduler, self.dev
         _, C, L, _ = latents.shape
         T = num_inference_steps
         st = self._state(1, C, L, T)
@@ -303,13 +322,14 @@ class LMDSampler:
         gkeys = [tuple(k) for k in (g.get("guidance_attn_keys") or DEFAULT_GUIDANCE_ATTN_KEYS)]
         gs = g.pop("state", None) or self.make_guidance(L, g.pop("bboxes"), g.pop("object_positions"), **g)
         if gs is not None and gs.kind == "boxdiff":
+            self._refuse_scaled_boxdiff(sch)
             gkeys = [tuple(k) for k in (g.get("guidance_attn_keys") or BOXDIFF_GUIDANCE_ATTN_KEYS)]
             st.gtab[:T, 0].copy_(torch.tensor([gs.step_scale(i, T) for i in range(T)], dtype=F32))
-        eng.prepare_timesteps([int(t) for t in sch.timesteps])
+        eng.prepare_timesteps([float(t) for t in sch.timesteps])
         cond = cond_embeddings.to(dev)
         eng.prepare_text(torch.cat([torch.zeros_like(cond), cond]))
         eng.set_step(index)
-        pg, gf, gb = self._guide_runners(st, 1, L, fuser, gkeys)
+        pg, gf, gb = self._guide_runners(st, 1, L, fuser, gkeys, _scaled(sch))
         if gligen is not None:
             eng.prepare_gligen(boxes=gligen[0], positive_embeddings=gligen[1], masks=gligen[2])
         st.lat.copy_(latents.to(dev, F32))
@@ -331,10 +351,11 @@ class LMDSampler:
             for nb in main_batches:
                 plan = eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys, pair_shared=True)
                 st = self._state(nb, eng.cfg.in_channels, L, T)
-                out.append(("main", f, nb, self._main_pass(plan, st, st.step_kernel(self.scheduler.step_kind), nb)))
+                out.append(("main", f, nb, self._main_pass(plan, st, st.step_kernel(self.scheduler.step_kind), nb,
+                                                           _scaled(self.scheduler))))
             for nb in guide_batches:
                 st = self._state(nb, eng.cfg.in_channels, L, T)
-                pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, f, keys)
+                pg, g_fwd, g_bwd = self._guide_pass(st, nb, L, f, keys, _scaled(self.scheduler))
 
                 # the energy launch between the two halves: a canonical two-box layout per image (its cost depends on
                 # the item count only, 2 boxes x 3 tokens x 4 keys + reference terms, not on the boxes)
@@ -410,6 +431,10 @@ class LMDSampler:
           tables and the history then follow the evaluation count, and guidance, GLIGEN, frozen steps, the fast schedule
           and first_step > 0 are refused.  A DDIMInverseScheduler (pipeline.invert_batch) runs its ascending schedule on
           the DDIM step kernel under the same refusals; with n_steps = T - 1 the history rows 0 .. T - 1 are this call's.
+          An EulerDiscreteScheduler / LMSDiscreteScheduler (sigma space: `generate.py --scheduler`) runs every loop with the
+          UNet input scaled by c_in = 1/sqrt(sigma^2 + 1) and the guidance step sigma^2 (pipelines.py:60-61); the latents
+          are expected times its init_noise_sigma.  The fast schedule and BoxDiff are refused under both, first_step > 0
+          under LMS (its ring of derivatives); Euler's rows carry no state, so partial schedules run.
         Returns per job dict(latents (1,C,L,L), latents_all (T_run+1,1,C,L,L), saved {key: [T_run,Bp,H,HW,Tp]},
         guidance_iters).
         """
@@ -420,7 +445,8 @@ class LMDSampler:
         _, C, L, _ = starts[0].shape
         self._refuse_undefined(sch.step_kind, fast=fast_after_steps is not None, partial=int(first_step) > 0,
                                conditioned=frozen_steps > 0 or use_gligen or any(j.guidance is not None for j in jobs),
-                               inverse=getattr(sch, "inverse", False))
+                               inverse=getattr(sch, "inverse", False), sigma_space=_scaled(sch),
+                               stateless=getattr(sch, "stateless_rows", False))
         st, ts, step = self._load_schedule(sch, nb, C, L, num_inference_steps, guidance_scale, fast_after_steps, fast_rate)
         Tr = len(ts)                                                          # steps actually run
         n_ground = int(gligen_scheduled_sampling_beta * Tr) if use_gligen else 0   # pipelines.py:405
@@ -431,16 +457,18 @@ class LMDSampler:
         def fuser_at(index):
             return bool(use_gligen and index < n_ground)                     # pipelines.py:408-414
         gstates, gkeys, energy = self._guidance_states(jobs, L, st, Tr)
+        if any(gs is not None and gs.kind == "boxdiff" for gs in gstates):
+            self._refuse_scaled_boxdiff(sch)
         max_guided = max([gs.max_index_step for gs in gstates if gs is not None] + [0])
 
         # ---- per-run constants (before graph capture so that warm-up launches see valid inputs)
-        eng.prepare_timesteps([int(t) for t in ts])
+        eng.prepare_timesteps(self._timestep_list(ts))
         eng.prepare_text(torch.cat([j.text[0:1] for j in jobs] + [j.text[1:2] for j in jobs]))
         eng.set_step(0)
         eng.dyn[1:2].fill_(0)
         plans_main, runners_main, runners_guide = self._plans_and_runners(
             st, step, jobs, L, {fuser_at(i) for i in range(Tr)}, {fuser_at(i) for i in range(min(max_guided, Tr))},
-            plan_keys, gkeys, use_gligen)
+            plan_keys, gkeys, use_gligen, _scaled(sch))
         first_step, last_step = self._load_call_state(st, jobs, starts, L, Tr, first_step, n_steps, frozen_steps)
         hw = self.map_hw(L)
         Bp = 1 if return_cond_ca_only else 2
@@ -469,8 +497,27 @@ class LMDSampler:
 
     # ---- the phases of _denoise_chunk, in its order
     @staticmethod
-    def _refuse_undefined(kind, *, fast, partial, conditioned, inverse=False):
-        """What a step kernel does not define is an error, not a fall-back.  inverse: a DDIMInverseScheduler drives it."""
+    def _refuse_scaled_boxdiff(sch):
+        if _scaled(sch):
+            raise RuntimeError("BoxDiff guidance under a sigma-space scheduler is not implemented: its step table "
+                               "(utils/boxdiff.py:229-234) would need the c_in of scale_model_input folded in")
+
+    @staticmethod
+    def _timestep_list(ts):
+        """The schedule as prepare_timesteps takes it: floats, so that the fractional timesteps of "linspace" spacing reach
+        the time embedding as they are (an integer schedule gives the same fp32 table as before, bit for bit)."""
+        return [float(t) for t in ts]
+
+    @staticmethod
+    def _refuse_undefined(kind, *, fast, partial, conditioned, inverse=False, sigma_space=False, stateless=False):
+        """What a step kernel does not define is an error, not a fall-back.  inverse: a DDIMInverseScheduler drives it;
+        sigma_space: a scheduler that carries `sigmas` (Euler, LMS); stateless: its rows read no earlier step's state."""
+        if sigma_space and fast:
+            raise RuntimeError("the fast schedule (utils/schedule.py) is not defined under a sigma-space scheduler: it shortens "
+                               "`timesteps` and leaves `sigmas` alone, so the reference pairs each step with the wrong sigma")
+        if kind == LMS and partial:
+            raise RuntimeError("partial schedules (first_step > 0) are not defined for LMSDiscreteScheduler: row first_step "
+                               "mixes in the derivatives of the three steps before it, which a run that starts here lacks")
         if inverse and (fast or partial or conditioned):
             raise RuntimeError("DDIMInverseScheduler runs the plain CFG loop only (pipelines.py:489-539): guidance, GLIGEN, "
                                "frozen steps, the fast schedule and partial schedules (first_step > 0) are not defined")
@@ -480,7 +527,7 @@ class LMDSampler:
         if kind == MULTISTEP and fast:
             raise RuntimeError("the fast schedule (utils/schedule.py) re-derives DDIM step sizes; not defined for the "
                                "multistep scheduler")
-        if kind == MULTISTEP and partial:
+        if kind == MULTISTEP and partial and not stateless:
             # row `first_step` of a second-order schedule mixes in the data prediction of step first_step - 1, which a
             # run that starts here does not have (the step kernel's x0_prev holds whatever run used this state last)
             raise RuntimeError("partial schedules (first_step > 0) are not defined for the multistep scheduler")
@@ -529,19 +576,19 @@ class LMDSampler:
             tables.merged([gs.energy if gs is not None else None for gs in gstates])
         return gstates, gkeys, energy
 
-    def _plans_and_runners(self, st, step, jobs, L, fusers_main, fusers_guide, plan_keys, gkeys, use_gligen):
+    def _plans_and_runners(self, st, step, jobs, L, fusers_main, fusers_guide, plan_keys, gkeys, use_gligen, scaled=False):
         """Plans + launch sequences (built / captured once per shape, cached on the state) per GLIGEN-fuser setting ->
         (main plans, main runners, guidance (plan, forward runner, backward runner))."""
         eng, nb = self.eng, len(jobs)
         # the CFG batch is [uncond halves; cond halves] of ONE set of latents (_main_pass): pair_shared
         plans = {f: eng.plan(2 * nb, L, fuser=f, save_keys=plan_keys, pair_shared=True) for f in fusers_main}
-        guides = {f: self._guide_runners(st, nb, L, f, gkeys) for f in fusers_guide}
+        guides = {f: self._guide_runners(st, nb, L, f, gkeys, scaled) for f in fusers_guide}
         if use_gligen:                                                        # after the plans exist
             boxes, embeddings, masks = (torch.cat([j.gligen[k][0:1] for j in jobs] + [j.gligen[k][1:2] for j in jobs])
                                         for k in range(3))            # [uncond halves; cond halves], like the text
             eng.prepare_gligen(boxes=boxes, positive_embeddings=embeddings, masks=masks)
-        mains = {f: st.runner(("main", f, tuple(plan_keys), step.kind, plan.pair_shared), self._main_pass(plan, st, step, nb),
-                              self.use_graphs)
+        mains = {f: st.runner(("main", f, tuple(plan_keys), step.kind, plan.pair_shared) + (("scaled",) if scaled else ()),
+                              self._main_pass(plan, st, step, nb, scaled), self.use_graphs)
                  for f, plan in plans.items()}
         return plans, mains, guides
 

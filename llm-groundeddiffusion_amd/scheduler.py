@@ -23,7 +23,9 @@ class _StepOutput:
 
 
 # `step_kind` of a scheduler class: the fused CFG + step kernel that its coefficient table drives (loop.StepKernel)
-DDIM, MULTISTEP, PLMS = "ddim", "multistep", "plms"
+DDIM, MULTISTEP, PLMS, LMS = "ddim", "multistep", "plms", "lms"
+# column of `guidance_step_table` that holds c_in = 1/sqrt(sigma^2 + 1) under a scheduler with `scales_model_input`
+C_IN_GCOL = 1
 
 
 class DDIMScheduler:
@@ -397,52 +399,94 @@ class PNDMScheduler(DDIMScheduler):
         raise RuntimeError("PNDMScheduler: the step of evaluation k is a row of plms_rows")
 
 
-class EulerDiscreteScheduler:
-    """[ext] diffusers EulerDiscreteScheduler as the SDXL refiner configures it (scheduler_config of
-    stabilityai/stable-diffusion-xl-refiner-1.0: scaled_linear betas 0.00085..0.012, 1000 train steps, timestep_spacing
-    "leading", steps_offset 1, epsilon prediction, linear sigma interpolation, no Karras sigmas, s_churn 0) — the sampler
-    behind generation/sdxl_refinement.py:29.  diffusers is absent from the sandbox: restated from the published
-    algorithm (Karras et al. 2022, Algorithm 2 without churn), parity unpinned at this boundary.
+class _SigmaSpaceScheduler:
+    """What the k-diffusion family of [ext] diffusers 0.18.0 shares (EulerDiscreteScheduler, LMSDiscreteScheduler): the
+    samplers `generate.py --scheduler NAME` reaches through models.load_sd(scheduler_cls=...) and for which
+    models/pipelines.py keeps the `sigmas` branch of latent_backward_guidance (:60-61) and calls scale_model_input before
+    every UNet evaluation.  They work in sigma space, x = x0 + sigma * eps with sigma = sqrt((1 - abar) / abar), and feed
+    the model x / sqrt(sigma^2 + 1).  diffusers is absent from the machines that run the suite: restated from the
+    published classes, parity unpinned at this boundary; pinned against line-for-line stateful restatements
+    (tests/sigma_sched_restate.py).
 
-    In sigma space (x = x0 + sigma * eps) one Euler step is linear in (x, x0):
-        x0 = x - sigma eps ;  x' = x + (sigma' - sigma) (x - x0) / sigma = (sigma'/sigma) x + (1 - sigma'/sigma) x0
-    so the device side is the fused `lgd_cfg_multistep_step_f32` kernel with rows {1, -sigma, sigma'/sigma,
-    1 - sigma'/sigma, 0, guidance_scale, c_in, 0}; c_in = 1/sqrt(sigma^2 + 1) (scale_model_input) is applied by
-    `lgd_scale_rows_f32` from the same row."""
-    step_kind = MULTISTEP
-    C_IN_COL = 6
+    `sigmas` holds the reversed training sigmas with 0 appended from construction on, and the schedule's own after
+    `set_timesteps`; `init_noise_sigma` reads whichever is current.  timestep_spacing: "linspace" (the class default,
+    hence what an SD 1.x / 2.x scheduler_config.json yields through from_config: it has no such key) has FRACTIONAL
+    timesteps, np.linspace(0, N_train - 1, n)[::-1]; "leading" is arange(n) * (N_train // n) + steps_offset; "trailing"
+    is round(arange(N_train, 0, -N_train / n)) - 1.  Sigmas of fractional timesteps are interpolated linearly.
 
-    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
-                 prediction_type="epsilon"):
-        if prediction_type != "epsilon":
-            raise NotImplementedError("EulerDiscreteScheduler: the refiner predicts epsilon")
+    Backward guidance under these samplers (pipelines.py:60-61) is latents - grad * sigma_i^2, the gradient taken with
+    respect to the latents; the grad plan returns it with respect to the UNet input x * c_in, c_in = 1/sqrt(sigma^2 + 1),
+    so `guidance_step_table` column 0 is sigma_i^2 * c_in_i (the chain rule) and column 1 is c_in_i itself, which
+    `lgd_scale_rows_f32` reads by dyn[0] in front of both UNet passes."""
+    scales_model_input = True         # the sampler scales the UNet input by guidance_step_table column C_IN_GCOL
+    stateless_rows = False            # True: a row reads nothing an earlier step left behind, partial schedules are defined
+    DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                    prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, use_karras_sigmas=False)
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=0,
+                 prediction_type="epsilon", timestep_spacing="linspace", beta_schedule="scaled_linear",
+                 use_karras_sigmas=False, interpolation_type="linear"):
+        name = type(self).__name__
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"{name}: prediction_type {prediction_type!r}")
+        if timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise NotImplementedError(f"{name}: timestep_spacing {timestep_spacing!r}")
+        if use_karras_sigmas:
+            raise NotImplementedError(f"{name}: use_karras_sigmas=True re-spaces the sigmas (Karras et al. 2022, eq. 5); "
+                                      "only the checkpoint's own sigmas are implemented")
+        if interpolation_type != "linear":
+            raise NotImplementedError(f"{name}: interpolation_type {interpolation_type!r}; only \"linear\" is implemented")
+        if beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            raise NotImplementedError(f"{name}: beta_schedule {beta_schedule!r}")
         self.config = _Cfg(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                           beta_schedule="scaled_linear", steps_offset=steps_offset, prediction_type=prediction_type,
-                           timestep_spacing="leading", interpolation_type="linear", use_karras_sigmas=False)
-        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+                           beta_schedule=beta_schedule, steps_offset=steps_offset, prediction_type=prediction_type,
+                           timestep_spacing=timestep_spacing, interpolation_type="linear", use_karras_sigmas=False)
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
         self.num_inference_steps = None
-        self.timesteps = None
-        self.sigmas = None
+        sig = self._train_sigmas()
+        self.sigmas = torch.from_numpy(np.concatenate([sig[::-1], [0.0]]).astype(np.float32))
+        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=float)[::-1].copy())
+
+    @classmethod
+    def from_config(cls, cfg):
+        """The scheduler a checkpoint's scheduler_config (a dict, or an object with `.config`) makes of this class: keys
+        the config lacks take the diffusers class defaults (DEFAULTS: linspace spacing, steps_offset 0), keys this class
+        does not read (clip_sample, set_alpha_to_one, skip_prk_steps, ...) are ignored as `from_config` ignores them."""
+        c = dict(cfg if isinstance(cfg, dict) else cfg.config)
+        kw = {k: c.get(k, d) for k, d in cls.DEFAULTS.items()}
+        if "interpolation_type" in c:
+            kw["interpolation_type"] = c["interpolation_type"]
+        return cls(**kw)
+
+    def _train_sigmas(self):
+        return (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
 
     def set_timesteps(self, num_inference_steps, device=None):
         self.num_inference_steps = num_inference_steps
-        n = self.config.num_train_timesteps
-        ts = (np.arange(0, num_inference_steps) * (n // num_inference_steps)).round()[::-1].copy().astype(np.float32)
-        ts += self.config.steps_offset
-        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        n, spacing = self.config.num_train_timesteps, self.config.timestep_spacing
+        if spacing == "linspace":
+            ts = np.linspace(0, n - 1, num_inference_steps, dtype=float)[::-1].copy()
+        elif spacing == "leading":
+            # fp32 timesteps: the SDXL refiner's schedule (sdxl.SDXLRefiner), kept to the bit
+            ts = (np.arange(0, num_inference_steps) * (n // num_inference_steps)).round()[::-1].copy().astype(np.float32)
+            ts += self.config.steps_offset
+        else:
+            ts = np.arange(n, 0, -n / num_inference_steps).round().copy().astype(float) - 1
+        sig = self._train_sigmas()
         sig = np.interp(ts, np.arange(0, len(sig)), sig)
         self.sigmas = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
         self.timesteps = torch.from_numpy(ts)
 
     @property
     def init_noise_sigma(self):
-        return float((self.sigmas.max() ** 2 + 1) ** 0.5)                   # "leading" spacing
-
-    def img2img_start(self, num_inference_steps, strength):
-        """StableDiffusionXLImg2ImgPipeline.get_timesteps (no denoising_start): index of the first step that runs."""
-        init = min(int(num_inference_steps * strength), num_inference_steps)
-        return max(num_inference_steps - init, 0)
+        """Of the current `sigmas`: the training ones before set_timesteps, the schedule's after."""
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return float(self.sigmas.max())
+        return float((self.sigmas.max() ** 2 + 1) ** 0.5)
 
     def index_of(self, t):
         return int((self.timesteps == float(t)).nonzero()[0])
@@ -454,11 +498,73 @@ class EulerDiscreteScheduler:
     def add_noise(self, original, noise, timestep):
         return original + noise * float(self.sigmas[self.index_of(timestep)])
 
+    def x0_coefficients(self, sigma):
+        """(c0, c1) of the data prediction x0 = c0 x + c1 m from the CFG-combined model output m."""
+        if self.config.prediction_type == "v_prediction":
+            return 1.0 / (sigma * sigma + 1.0), -sigma / (sigma * sigma + 1.0) ** 0.5
+        return 1.0, -sigma
+
+    def guidance_step_table(self, device, timesteps=None) -> torch.Tensor:
+        """fp32 [T][4] = {sigma_i^2 * c_in_i, c_in_i, 0, 0} (class docstring)."""
+        idx = range(len(self.timesteps)) if timesteps is None else map(self.index_of, timesteps)
+        rows = []
+        for i in idx:
+            s = float(self.sigmas[i])
+            c_in = 1.0 / (s * s + 1.0) ** 0.5
+            rows.append([s * s * c_in, c_in, 0.0, 0.0])
+        return torch.tensor(rows, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def fast_schedule(timesteps, fast_after_steps, fast_rate=2):
+        raise RuntimeError("the fast schedule (utils/schedule.py) shortens `timesteps` and leaves `sigmas` as they are: under "
+                           "a sigma-space scheduler the reference then pairs the wrong sigma with each step; not defined")
+
+    def dynamic_step_sizes(self, timesteps):
+        return None
+
+    def coef_table(self, guidance_scale, device, timesteps=None, step_ratios=None):
+        raise RuntimeError(f"{type(self).__name__} drives the {self.step_kind} step kernel, not lgd_cfg_ddim_step_f32")
+
+    def prev_timestep(self, t, index=None):
+        raise RuntimeError("sigma-space scheduler: the next noise level is the next entry of `sigmas`")
+
+
+class EulerDiscreteScheduler(_SigmaSpaceScheduler):
+    """[ext] diffusers 0.18.0 EulerDiscreteScheduler without churn (s_churn 0: deterministic; Karras et al. 2022,
+    Algorithm 2), epsilon and v_prediction, three timestep spacings (_SigmaSpaceScheduler).  The bare constructor is the
+    SDXL refiner's configuration (scheduler_config of stabilityai/stable-diffusion-xl-refiner-1.0: scaled_linear betas
+    0.00085..0.012, 1000 train steps, timestep_spacing "leading", steps_offset 1, epsilon) — the sampler behind
+    generation/sdxl_refinement.py:29; `from_config` of an SD 1.x / 2.x scheduler_config gives "linspace" spacing, what
+    `generate.py --scheduler EulerDiscreteScheduler` runs.  diffusers is absent from the machines that run the suite:
+    restated from the published class, parity unpinned at this boundary; pinned against tests/sigma_sched_restate.py.
+
+    In sigma space (x = x0 + sigma * eps) one Euler step is linear in (x, x0):
+        x0 = c0 x + c1 m ;  x' = x + (sigma' - sigma) (x - x0) / sigma = (sigma'/sigma) x + (1 - sigma'/sigma) x0
+    with (c0, c1) = (1, -sigma) for epsilon and (1/(sigma^2 + 1), -sigma/sqrt(sigma^2 + 1)) for v_prediction, so the device
+    side is the fused `lgd_cfg_multistep_step_f32` kernel with rows {c0, c1, sigma'/sigma, 1 - sigma'/sigma, 0,
+    guidance_scale, c_in, 0}; c_in = 1/sqrt(sigma^2 + 1) (scale_model_input) is applied by `lgd_scale_rows_f32` from the
+    same row (the refiner) or from guidance_step_table (sampler.LMDSampler).  The last step (sigma' = 0) returns x0."""
+    step_kind = MULTISTEP
+    stateless_rows = True             # C = 0 in every row: x0_prev is never read
+    C_IN_COL = 6
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
+                 prediction_type="epsilon", timestep_spacing="leading", beta_schedule="scaled_linear",
+                 use_karras_sigmas=False, interpolation_type="linear"):
+        super().__init__(num_train_timesteps, beta_start, beta_end, steps_offset, prediction_type, timestep_spacing,
+                         beta_schedule, use_karras_sigmas, interpolation_type)
+
+    def img2img_start(self, num_inference_steps, strength):
+        """StableDiffusionXLImg2ImgPipeline.get_timesteps (no denoising_start): index of the first step that runs."""
+        init = min(int(num_inference_steps * strength), num_inference_steps)
+        return max(num_inference_steps - init, 0)
+
     def multistep_rows(self, timesteps=None):
         rows = []
         for i in (range(len(self.timesteps)) if timesteps is None else map(self.index_of, timesteps)):
             s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
-            rows.append((1.0, -s, sn / s, 1.0 - sn / s, 0.0, 1.0 / (s * s + 1.0) ** 0.5))
+            c0, c1 = self.x0_coefficients(s)
+            rows.append((c0, c1, sn / s, 1.0 - sn / s, 0.0, 1.0 / (s * s + 1.0) ** 0.5))
         return rows
 
     def multistep_table(self, guidance_scale: float, device, timesteps=None) -> torch.Tensor:
@@ -466,7 +572,88 @@ class EulerDiscreteScheduler:
         return torch.tensor(rows, dtype=torch.float32, device=device)
 
     def step_host(self, model_output, index, sample):
-        """Torch form of one step exactly as the scheduler class writes it (tests)."""
-        s, sn = self.sigmas[index], self.sigmas[index + 1]
-        pred_original = sample - s * model_output
+        """Torch form of one step as the scheduler class writes it (tests); the fp32 sigmas enter as Python floats, so
+        that the arithmetic is the sample's own (fp64 samples: fp64 throughout)."""
+        s, sn = float(self.sigmas[index]), float(self.sigmas[index + 1])
+        if self.config.prediction_type == "v_prediction":
+            pred_original = model_output * (-s / (s ** 2 + 1) ** 0.5) + (sample / (s ** 2 + 1))
+        else:
+            pred_original = sample - s * model_output
         return sample + (sample - pred_original) / s * (sn - s)
+
+
+class LMSDiscreteScheduler(_SigmaSpaceScheduler):
+    """[ext] diffusers 0.18.0 LMSDiscreteScheduler (the linear multistep sampler of k-diffusion, order 4), epsilon and
+    v_prediction, on the sigmas, spacings, init_noise_sigma and scale_model_input of _SigmaSpaceScheduler; the bare
+    constructor is what `from_config` makes of an SD 1.x scheduler_config (scaled_linear betas, "linspace" spacing).
+    diffusers is absent from the machines that run the suite: restated from the published class, parity unpinned at this
+    boundary; pinned against tests/sigma_sched_restate.py.
+
+    One step with d_j = (x_j - x0_j) / sigma_j, the derivative of step j:
+        order = min(i + 1, 4) ;  x' = x + sum_{k < order} coeff_k d_{i-k}
+        coeff_k = integral over [sigma_i, sigma_{i+1}] of the Lagrange basis polynomial of node sigma_{i-k} among
+                  sigma_i ... sigma_{i-order+1}.
+    The class integrates with scipy.integrate.quad(epsrel=1e-4); the integrand is a polynomial of degree < 4, so
+    `lms_coefficients` integrates it exactly in fp64 (in u = tau - sigma_i, whose antiderivative vanishes at the lower
+    limit: no cancellation between the two ends).  The two agree to ~2e-12 relative (tests/test_sigma_schedulers_cpu.py):
+    the same sampler.
+
+    The device side is `lgd_cfg_lms_step_f32`: the derivatives live in a ring of 4 latents, d_j in slot j % 4, and
+    `lms_table` permutes the coefficients onto slots, rows {c0, c1, 1/sigma, w[0..3] by slot, guidance_scale, slot, 0...}
+    (16 columns), so the kernel does no modular arithmetic.  A slot's weight is 0 where the order does not reach it."""
+    step_kind = LMS                   # lms_table -> lgd_cfg_lms_step_f32
+    ORDER = 4
+    TABLE_COLS = 16
+
+    def lms_coefficients(self, index, order=None):
+        """coeff_k, k < min(index + 1, order): exact fp64 integrals of the Lagrange basis polynomials."""
+        order = min(index + 1, self.ORDER if order is None else order)
+        s = [float(self.sigmas[index - k]) for k in range(order)]
+        h = float(self.sigmas[index + 1]) - s[0]
+        out = []
+        for k in range(order):
+            num, den = np.poly1d([1.0]), 1.0
+            for j in range(order):
+                if j != k:
+                    num = num * np.poly1d([1.0, -(s[j] - s[0])])          # (u - (sigma_{i-j} - sigma_i))
+                    den *= s[k] - s[j]
+            out.append(float(np.polyint(num)(h)) / den)
+        return out
+
+    def lms_rows(self, timesteps=None, order=None):
+        """Per step: (c0, c1, 1/sigma, (w_0..w_3) by ring slot, slot of this step's derivative).  `timesteps`: the whole
+        schedule only — row i mixes in the derivatives of steps i-1 .. i-3 (sampler: first_step > 0 is refused)."""
+        if timesteps is not None and [float(t) for t in timesteps] != [float(t) for t in self.timesteps]:
+            raise RuntimeError("LMSDiscreteScheduler: rows exist for the whole schedule only (the ring carries the last "
+                               "three derivatives)")
+        rows = []
+        for i in range(len(self.timesteps)):
+            s = float(self.sigmas[i])
+            c0, c1 = self.x0_coefficients(s)
+            w = [0.0] * self.ORDER
+            for k, c in enumerate(self.lms_coefficients(i, order)):
+                w[(i - k) % self.ORDER] = c
+            rows.append((c0, c1, 1.0 / s, tuple(w), i % self.ORDER))
+        return rows
+
+    def lms_table(self, guidance_scale: float, device, timesteps=None) -> torch.Tensor:
+        """fp32 [T][16] = {c0, c1, 1/sigma, w_0, w_1, w_2, w_3, guidance_scale, slot, 0...} (lgd_hip.h)."""
+        rows = [[c0, c1, inv, *w, guidance_scale, float(slot)] + [0.0] * (self.TABLE_COLS - 9)
+                for c0, c1, inv, w, slot in self.lms_rows(timesteps)]
+        return torch.tensor(rows, dtype=torch.float32, device=device)
+
+    def host_state(self, like):
+        """Ring of `step_host`, shaped like one sample."""
+        return dict(ring=[torch.zeros_like(like) for _ in range(self.ORDER)])
+
+    def step_host(self, model_output, index, sample, state, order=None):
+        """Torch form of step `index` in the table form the kernel runs (tests): updates `state` (host_state) and
+        returns the new sample."""
+        c0, c1, inv, w, slot = self.lms_rows(order=order)[index]
+        d = (sample - (c0 * sample + c1 * model_output)) * inv
+        out = sample + w[slot] * d
+        for s in range(self.ORDER):
+            if s != slot and w[s] != 0.0:
+                out = out + w[s] * state["ring"][s]
+        state["ring"][slot] = d.clone()
+        return out

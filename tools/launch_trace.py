@@ -43,6 +43,7 @@ import torch
 
 # entry point -> index of its coefficient-table argument
 STEP_TABLE_ARG = {"lgd_cfg_ddim_step_f32": 3, "lgd_cfg_multistep_step_f32": 4, "lgd_cfg_plms_step_f32": 5,
+                  "lgd_cfg_lms_step_f32": 4,
                   "lgd_multidiffusion_step_f32": 7, "lgd_multidiffusion_views_f32": 9}
 
 
