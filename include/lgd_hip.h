@@ -329,6 +329,25 @@ int lgd_attn_causal_fwd_f16(const void* q, int64_t ldq, int64_t q_bs, const void
                             const void* v, int64_t ldv, int64_t v_bs, void* o, int64_t ldo, int64_t o_bs, int B,
                             int H, int S, int d, float scale, void* stream);
 
+/* Single-head attention forward for wide heads (additive export: LGD_ABI_VERSION stays 12; csrc/attn_wide.hip):
+ * O = softmax(scale Q K^T) V for 8 <= d <= 512, one launch, no score matrix.  Replaces, for the mid-block Attention of
+ * AutoencoderKL ([ext] diffusers models/attention_processor.py, AttnProcessor.__call__ with heads = 1: attn.to_q / to_k /
+ * to_v, get_attention_scores = baddbmm(q, k^T) * scale -> softmax(dim = -1), torch.bmm(probs, v)), the op sequence
+ * baddbmm -> softmax -> bmm; the projections and the GroupNorm stay with the caller.
+ *   q [B][Sq][d], k / v [B][Sk][d], o [B][Sq][d] fp16 views: row stride ld*, per-image stride bs* (elements; 0 on an input
+ *   repeats it for every image), so q and k may be the halves of one [B*S][2 d] projection.
+ * Arithmetic: inputs exact, Q K^T in fp32, scale * log2(e) applied to the fp32 logit, running max and row sum in fp32
+ * (the sum from the fp32 probabilities), v_exp_f32, P rounded to fp16 for P V, P V in fp32 (rescaled when the running max
+ * moves), one fp16 rounding of O.  No logit or probability is stored anywhere; no atomics, no workspace, no host
+ * synchronisation: bit-identical from run to run and under graph capture.
+ * Its own contract, not a row of lgd_attn_variant.  Refused before any runtime call — LGD_ERR_ARG: a NULL operand; B, Sq or
+ * Sk < 1; d < 8 or d % 8 != 0; ld / bs / base of an input not multiples of 8 / 16-byte aligned, of o not multiples of 4 /
+ * 8-byte aligned; an ld below d, a negative bs, images of o overlapping each other; o overlapping q, k or v.
+ * LGD_ERR_UNSUPPORTED: d > 512, B > 65535. */
+int lgd_attn_wide_f16(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int d, int64_t ldq,
+                      int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                      float scale, void* stream);
+
 /* lgd_attn_plan (additive export: LGD_ABI_VERSION stays 12): the variant code of the kernel instantiation a call with these arguments runs under the
  * current option state ("attn32", "attn32_nw", "attn32_var", "attn_w4", "attn_w4_pipe") — answered by the function the
  * launches themselves choose their kernel with; host only, nothing is launched.  code = family * 100000 + DP * 100 + sub (DP: the padded

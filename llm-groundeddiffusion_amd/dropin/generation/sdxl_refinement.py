@@ -23,8 +23,10 @@ pipe = None
 REFINE_SIZE = 1024                     # sdxl_refinement.py:26
 
 
-def init(offload_model=True, device="cuda", vae_ranges=None):
-    """sdxl_refinement.py:10-22.  vae_ranges: see _vae_ranges (the checkpoint's VAE sets config.force_upcast)."""
+def init(offload_model=True, device="cuda", vae_ranges=None, vae_attention=None):
+    """sdxl_refinement.py:10-22.  vae_ranges: see _vae_ranges (the checkpoint's VAE sets config.force_upcast).
+    vae_attention: "materialised" | "streamed", the VAE's mid-block attention (None: the VAE classes' default;
+    force_upcast does not select it)."""
     global pipe
     try:
         from diffusers import StableDiffusionXLImg2ImgPipeline
@@ -33,7 +35,7 @@ def init(offload_model=True, device="cuda", vae_ranges=None):
                            "diffusers, which is not installed here; use init_synthetic() for seeded random weights") from e
     hf = StableDiffusionXLImg2ImgPipeline.from_pretrained("stabilityai/stable-diffusion-xl-refiner-1.0",
                                                           torch_dtype=torch.float16, variant="fp16", use_safetensors=True)
-    pipe = from_diffusers(hf, device, vae_ranges)
+    pipe = from_diffusers(hf, device, vae_ranges, vae_attention)
     return pipe
 
 
@@ -55,10 +57,10 @@ def _vae_ranges(config, override, env):
     return vae.RangePlan.uniform(vae.FORCE_UPCAST_EXPONENT) if flag else None
 
 
-def from_diffusers(hf_pipe, device="cuda", vae_ranges=None):
+def from_diffusers(hf_pipe, device="cuda", vae_ranges=None, vae_attention=None):
     """A loaded StableDiffusionXLImg2ImgPipeline -> SDXLRefiner: weights are read from the modules' state dicts, the
     UNet configuration from `unet.config` (must be the refiner's topology family: text_time, linear projections).
-    vae_ranges: the VAE's range plan (see _vae_ranges)."""
+    vae_ranges: the VAE's range plan (see _vae_ranges).  vae_attention: as init's."""
     from lgd_amd import clip, vae, weights
     from lgd_amd.scheduler import EulerDiscreteScheduler
     from lgd_amd.unet import UNetEngine
@@ -78,17 +80,18 @@ def from_diffusers(hf_pipe, device="cuda", vae_ranges=None):
     vsd = hf_pipe.vae.state_dict()
     ranges = _vae_ranges(hf_pipe.vae.config, vae_ranges, _os.environ)
     sch = hf_pipe.scheduler.config
-    return _sdxl.SDXLRefiner(eng, vae.HipVAEEncoder(vsd, device, ranges=ranges), vae.HipVAEDecoder(vsd, device, ranges=ranges),
+    kw = vae.attention_kw(vae_attention)
+    return _sdxl.SDXLRefiner(eng, vae.HipVAEEncoder(vsd, device, ranges=ranges, **kw), vae.HipVAEDecoder(vsd, device, ranges=ranges, **kw),
                              text_encoder=clip.from_hf(hf_pipe.text_encoder_2, device), tokenizer=hf_pipe.tokenizer_2,
                              scheduler=EulerDiscreteScheduler(sch.num_train_timesteps, sch.beta_start, sch.beta_end,
                                                               sch.steps_offset, sch.prediction_type),
                              scaling_factor=hf_pipe.vae.config.scaling_factor)
 
 
-def init_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ranges=None):
+def init_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ranges=None, vae_attention=None):
     """Offline stand-in for init(): the refiner's networks with seeded random parameters."""
     global pipe
-    pipe, _ = _sdxl.build_synthetic(config, device, seed, vae_ranges=vae_ranges)
+    pipe, _ = _sdxl.build_synthetic(config, device, seed, vae_ranges=vae_ranges, vae_attention=vae_attention)
     return pipe
 
 

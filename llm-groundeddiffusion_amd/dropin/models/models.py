@@ -115,7 +115,8 @@ def load_synthetic(name="sd14_gligen", seed=0, device="cuda", with_vae=True, loa
 
 
 def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_scheduler=False,
-            use_dpm_multistep_scheduler=False, scheduler_cls=None, vae_ranges=None, safety_checker=False):
+            use_dpm_multistep_scheduler=False, scheduler_cls=None, vae_ranges=None, safety_checker=False,
+            vae_attention=None):
     """models/models.py:16-62.  Needs the Hugging Face checkpoint (diffusers + network/cache); the UNet
     state dict is repacked into the HIP engine's arenas, the CLIP text tower runs on the HIP kernels
     (lgd_amd.clip), the VAE's state dict is repacked for the HIP kernels (lgd_amd.vae.HipVAE: the decoder at once, the
@@ -123,6 +124,7 @@ def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_s
     checks against it).  load_inverse_scheduler (models/models.py:57-59): model_dict.inverse_scheduler for
     pipelines.invert.  vae_ranges: the range plan of a VAE whose config sets force_upcast (the SDXL VAE), by the rule
     of generation.sdxl_refinement._vae_ranges: RangePlan.uniform(8) when none is given, none for an fp16-safe VAE.
+    vae_attention: "materialised" | "streamed", the HIP VAE's mid-block attention (None: HipVAE's default).
     safety_checker=True, or LGD_SAFETY_CHECKER=1 in the environment: the checkpoint's `safety_checker` and
     `feature_extractor` subfolders are loaded and model_dict carries `safety_checker` (lgd_amd.safety.HipSafetyChecker)
     and `safety_processor`; generation.stable_diffusion_generate.run then blanks what the checker flags, as the
@@ -172,10 +174,10 @@ def load_sd(key="runwayml/stable-diffusion-v1-5", use_fp16=False, load_inverse_s
         dec = _HFVae()
     else:
         from generation.sdxl_refinement import _vae_ranges
-        from lgd_amd.vae import HipVAE
+        from lgd_amd.vae import HipVAE, attention_kw
         dec = HipVAE.from_state_dict(vae.state_dict(), torch_device,             # models/models.py:41 on the HIP kernels
                                      scaling_factor=getattr(vae.config, "scaling_factor", 0.18215),
-                                     ranges=_vae_ranges(vae.config, vae_ranges, _os.environ))
+                                     ranges=_vae_ranges(vae.config, vae_ranges, _os.environ), **attention_kw(vae_attention))
     md = build_model_dict(cfg, {k: v.float() for k, v in hf.state_dict().items()}, vae=dec, tokenizer=tok,
                           text_encoder=te, scheduler_config=raw_cfg,
                           use_dpm_multistep_scheduler=use_dpm_multistep_scheduler,

@@ -658,6 +658,21 @@ def attn_fwd(q, k, v, o, B, H, Sq, Sk, d, scale, *, lse=None, q_view=None, k_vie
     return o
 
 
+def attn_wide(q, k, v, o, B, Sq, Sk, d, scale, *, q_view=None, k_view=None, v_view=None, o_view=None):
+    """Single-head attention for heads up to 512 wide (lgd_attn_wide_f16): o = softmax(scale q k^T) v with fp32 logits
+    and no score matrix.  Views (ld, batch_stride) as attn_fwd's, default contiguous [B, S, d]."""
+    dq_, dk_ = _default_views(1, Sq, Sk, d)
+    qv, kv, vv, ov = q_view or dq_, k_view or dk_, v_view or dk_, o_view or dq_
+    fn = lambda: _call("lgd_attn_wide_f16", _p(q), _p(k), _p(v), _p(o), B, Sq, Sk, d, qv[0], kv[0], vv[0], ov[0],
+                       qv[1], kv[1], vv[1], ov[1], float(scale), _stream())
+    if PROFILER is not None:
+        PROFILER.wrap(f"attn_wide_kernel d={d}", 4.0 * B * Sq * Sk * d, 2.0 * B * d * (2 * Sq + 2 * Sk), fn, "attn_path",
+                      shape=f"B{B}_Sq{Sq}_Sk{Sk}")
+    else:
+        fn()
+    return o
+
+
 def attn_bwd(q, k, v, o, go, lse, delta, gq, gk, gv, B, H, Sq, Sk, d, scale, *, q_view=None,
              k_view=None, v_view=None, o_view=None, go_view=None, gq_view=None, gk_view=None,
              gv_view=None, sk_grad=None):

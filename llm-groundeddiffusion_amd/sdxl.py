@@ -170,12 +170,15 @@ class SDXLRefiner:
 
 
 def build_synthetic(config="sdxl_refiner", device="cuda", seed=0, vae_ch=(128, 256, 512, 512), vae_layers=2,
-                    vae_ranges=None):
+                    vae_ranges=None, vae_attention=None):
     """The refiner with seeded random parameters of the real architectures (no checkpoints in the sandbox):
     UNet `config`, SD / SDXL VAE encoder + decoder.  No text tower (callers pass embeddings).  vae_ranges: the
-    vae.RangePlan both VAE halves are built with (None: plain fp16)."""
+    vae.RangePlan both VAE halves are built with (None: plain fp16).  vae_attention: "materialised" | "streamed", how
+    both halves run their mid-block attention (None: the classes' default)."""
     from . import vae, weights
     cfg = weights.CONFIGS[config]
     eng = UNetEngine(cfg, device, weights.synth_state_dict(cfg, seed), max_text_batch=2)
     sd = vae.synth_aekl_state_dict(vae_ch, vae_layers, seed=seed)
-    return SDXLRefiner(eng, vae.HipVAEEncoder(sd, device, ranges=vae_ranges), vae.HipVAEDecoder(sd, device, ranges=vae_ranges)), sd
+    kw = vae.attention_kw(vae_attention)
+    return SDXLRefiner(eng, vae.HipVAEEncoder(sd, device, ranges=vae_ranges, **kw),
+                       vae.HipVAEDecoder(sd, device, ranges=vae_ranges, **kw)), sd

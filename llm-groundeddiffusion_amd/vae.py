@@ -1,5 +1,6 @@
 """The VAE ([ext] diffusers AutoencoderKL, SD 1.x / 2.x / SDXL config) on the lgd_hip kernels: implicit-GEMM convolutions,
-GroupNorm+SiLU, and for the single mid-block attention three batched GEMM launches + a row softmax for the whole batch.
+GroupNorm+SiLU, and for the single mid-block attention three batched GEMM launches + a row softmax for the whole batch
+(attention="streamed": the projections + one lgd_attn_wide_f16 launch with fp32 logits and no score matrix).
 HipVAEDecoder sits inside the images/s window because pipelines.decode (models/pipelines.py:117-127, 588-595) runs once
 per box and once per image; HipVAEEncoder serves the refiner, the inversion and the
 MultiDiffusion background passes; HipVAE is the `vae` of `model_dict`: the decoder, with its encoder built on first use.
@@ -183,6 +184,13 @@ _NO_PLAN = RangePlan()
 # what _Blocks._res / _attn run under when a caller hands them no record: no scale, nothing probed
 _RES_1 = types.SimpleNamespace(eps1=1.0, a1=1.0, eps2=1.0, a2=1.0, sc=None, sc_bias=None, site=None, site_inner=None)
 _ATTN_1 = types.SimpleNamespace(eps=1.0, a_out=1.0, site=None, site_a=None)
+# how the mid-block attention runs: over a materialised fp16 score matrix (the default), or through lgd_attn_wide_f16
+ATTENTION_MODES = ("materialised", "streamed")
+
+
+def attention_kw(vae_attention):
+    """The keyword a builder's `vae_attention=` (None: the class default) hands to the VAE classes."""
+    return {} if vae_attention is None else {"attention": vae_attention}
 
 
 class _Pack:
@@ -251,11 +259,13 @@ class _Blocks:
     """What the decoder and the encoder share at run time: the kernels, the device, the GroupNorm constants and the two
     blocks over a channels-last fp16 map x [B*H*W, C]."""
 
-    def __init__(self, device, groups, eps):
+    def __init__(self, device, groups, eps, attention="materialised"):
         from . import ops
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"attention is one of {ATTENTION_MODES}, got {attention!r}")
         self.ops = ops
         self.dev = torch.device(device)
-        self.groups, self.eps = groups, eps
+        self.groups, self.eps, self.attention = groups, eps, attention
         self._probe = None                   # calibration only (probe_ranges): called with (Site, stored tensor)
 
     def _plan(self, pk, part, ranges):
@@ -309,16 +319,24 @@ class _Blocks:
 
     def _attn(self, p, x, B, H, W, r=_ATTN_1):
         """Single-head attention over the H*W positions at width C (512): the head is wider than the flash kernels'
-        160, so the batch runs as three BATCHED GEMM launches + one row softmax:
+        160.  attention = "materialised": the batch runs as three BATCHED GEMM launches + one row softmax:
             scores[b] = q[b] k[b]^T      ->  P = softmax(scores)      (q, k carry C^-1/4 each)
             vt[b]     = Wv n[b]^T        (V^T directly from the projection: no transpose pass)
-            out[b]    = P[b] vt[b]^T + bv   (rows of P sum to 1, so V's bias is added once, behind the product)"""
+            out[b]    = P[b] vt[b]^T + bv   (rows of P sum to 1, so V's bias is added once, behind the product)
+        attention = "streamed": v = n Wv^T + bv in row layout from the same packed weights, then ONE lgd_attn_wide_f16
+        launch that reads q and k as the halves of the [B*S, 2C] projection (scale 1: the weights carry it): fp32 logits,
+        no score matrix, memory linear in S."""
         ops = self.ops
         S = H * W
         C = x.shape[1]
         F16 = torch.float16
         n = ops.groupnorm(x, B, S, self.groups, self.eps * r.eps, p["n"][0], p["n"][1], False)
         qk = ops.linear(n, p["qk"][0], p["qk"][1])                                  # [B*S, 2C]
+        if self.attention == "streamed":
+            v = ops.linear(n, p["v"], p["vb"])                                      # [B*S, C]
+            a = torch.empty((B * S, C), device=self.dev, dtype=F16)
+            ops.attn_wide(qk, qk[:, C:], v, a, B, S, S, C, 1.0, q_view=(2 * C, S * 2 * C), k_view=(2 * C, S * 2 * C))
+            return self._see(r.site, ops.linear(self._see(r.site_a, a), p["o"][0], p["o"][1], res=x, alpha=r.a_out))
         sc = torch.empty((B * S, S), device=self.dev, dtype=F16)
         ops.gemm_launch(ops.gemm_desc(qk, qk[:, C:], sc, S, S, C, lda0=2 * C, ldw=2 * C, ldc=S, nb_o=B,
                                       a_bs=(S * 2 * C, 0), w_bs=(S * 2 * C, 0), c_bs=(S * S, 0)))
@@ -338,10 +356,11 @@ class HipVAEDecoder(_Blocks):
 
     HipVAEDecoder(state_dict | module with `aekl_state_dict()`, device).  The state dict is AutoencoderKL's (encoder keys are ignored);
     the decoder's shape (channels per up block, resnets per block, which blocks upsample) is read off the keys.
-    ranges: a RangePlan for a VAE whose activations leave the fp16 range (None = RangePlan.uniform(0): plain fp16)."""
+    ranges: a RangePlan for a VAE whose activations leave the fp16 range (None = RangePlan.uniform(0): plain fp16).
+    attention: "materialised" (default) or "streamed" — how the mid-block attention runs (_Blocks._attn)."""
 
-    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, ranges=None):
-        super().__init__(device, groups, eps)
+    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, ranges=None, attention="materialised"):
+        super().__init__(device, groups, eps, attention)
         pk = _Pack(_state_dict(source), self.dev, "decoder", "post_quant_conv")
         sd = pk.sd
         self._plan(pk, "decoder", ranges)
@@ -389,9 +408,11 @@ class HipVAEDecoder(_Blocks):
     @torch.no_grad()
     def decode(self, z):
         """z (B, C, Hl, Wl) -> (B, 3, 8 Hl, 8 Wl); Hl and Wl need not be equal (a MultiDiffusion panorama).  The mid-block
-        attention runs over all Hl*Wl positions with a materialised fp16 score matrix of (Hl*Wl)^2 elements per image:
-        32 MB at 64 x 64, 512 MB at the 64 x 256 latent of a 512 x 2048 panorama.  That is accepted: it is one call per
-        image."""
+        attention runs over all Hl*Wl positions.  Under attention = "materialised" (the default) that is a materialised
+        fp16 score matrix of (Hl*Wl)^2 elements per image — 32 MB at 64 x 64, 512 MB at the 64 x 256 latent of a
+        512 x 2048 panorama — whose logits are STORED in fp16: a logit above 65504 turns its row, and the image, into NaN.
+        Under attention = "streamed" one lgd_attn_wide_f16 launch keeps the logits in fp32 and stores no scores at all:
+        the temporaries of the attention are six [B*Hl*Wl, C] fp16 tensors."""
         ops, rs = self.ops, self.rs
         z = z.to(self.dev, torch.float32).contiguous()
         B, _, H, W = z.shape
@@ -497,8 +518,8 @@ class HipVAEEncoder(_Blocks):
     position past the border reads the zero the asymmetric pad adds) — 4x the flops of three small convolutions,
     once per image."""
 
-    def __init__(self, state_dict, device, groups: int = 32, eps: float = 1e-6, ranges=None):
-        super().__init__(device, groups, eps)
+    def __init__(self, state_dict, device, groups: int = 32, eps: float = 1e-6, ranges=None, attention="materialised"):
+        super().__init__(device, groups, eps, attention)
         pk = _Pack(state_dict, self.dev, "encoder", "quant_conv")
         sd = pk.sd
         self._plan(pk, "encoder", ranges)
@@ -602,9 +623,10 @@ class HipVAE(HipVAEDecoder):
     encoder is a HipVAEEncoder over the same AutoencoderKL state dict, built on first use (a generation-only run never
     packs it)."""
 
-    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215, ranges=None):
+    def __init__(self, source, device, groups: int = 32, eps: float = 1e-6, scaling_factor: float = 0.18215, ranges=None,
+                 attention="materialised"):
         sd = _state_dict(source)
-        super().__init__(sd, device, groups, eps, ranges=ranges)
+        super().__init__(sd, device, groups, eps, ranges=ranges, attention=attention)
         self._encoder_sd = {k: v for k, v in sd.items() if k.startswith(("encoder.", "quant_conv."))}
         self._encoder = None
         self.config = _Config(scaling_factor=scaling_factor)
@@ -615,7 +637,8 @@ class HipVAE(HipVAEDecoder):
             if "encoder.conv_in.weight" not in self._encoder_sd:
                 raise RuntimeError("this VAE was built from a state dict without encoder weights: it cannot encode")
             # (a plan names AutoencoderKL's modules: the encoder takes its half by name)
-            self._encoder = HipVAEEncoder(self._encoder_sd, self.dev, self.groups, self.eps, ranges=self.ranges)
+            self._encoder = HipVAEEncoder(self._encoder_sd, self.dev, self.groups, self.eps, ranges=self.ranges,
+                                          attention=self.attention)
             self._encoder_sd = None
         return self._encoder
 
@@ -649,18 +672,19 @@ CALIBRATION_EXPONENT = 12        # true magnitudes up to 65504 * 2^12 = 2.7e8 st
 
 
 @torch.no_grad()
-def probe_ranges(source, device, ranges, latents=None, images=None):
+def probe_ranges(source, device, ranges, latents=None, images=None, attention="materialised"):
     """Runs the decoder on `latents` (B, z, H, W) and / or the encoder on `images` (B, 3, S, S in [-1, 1]) eagerly under
     `ranges` and measures every fp16 tensor the blocks store — the stream behind each block, each conv1 output, the
     attention's `a` — with lgd_range_f16: {Site: (largest finite STORED magnitude, number of non-finite elements)}.
-    The probes write into one device table; there is one download, at the end."""
+    The probes write into one device table; there is one download, at the end.  attention: as the VAE classes take it
+    (the sites are the same under either setting)."""
     from . import ops
     sd, dev = _state_dict(source), torch.device(device)
     halves = []
     if latents is not None:
-        halves.append((HipVAEDecoder(sd, dev, ranges=ranges), "decode", latents))
+        halves.append((HipVAEDecoder(sd, dev, ranges=ranges, attention=attention), "decode", latents))
     if images is not None:
-        halves.append((HipVAEEncoder(sd, dev, ranges=ranges), "encode_moments", images))
+        halves.append((HipVAEEncoder(sd, dev, ranges=ranges, attention=attention), "encode_moments", images))
     if not halves:
         raise ValueError("nothing to measure: pass latents for the decoder, images for the encoder, or both")
     sites = [s for half, _, _ in halves for s in half.sites]
@@ -674,13 +698,13 @@ def probe_ranges(source, device, ranges, latents=None, images=None):
     return {s: (peaks[i], bad[i]) for s, i in row.items()}
 
 
-def calibrate_ranges(source, device, latents=None, images=None, headroom_bits=4) -> RangePlan:
+def calibrate_ranges(source, device, latents=None, images=None, headroom_bits=4, attention="materialised") -> RangePlan:
     """The plan for a VAE whose checkpoint is at hand: runs the given inputs once at RangePlan.uniform(12), takes the
     peak of every stored tensor (probe_ranges) and returns RangePlan.from_peaks of the true magnitudes, peak * 2^12 —
     stored peaks of these inputs then are <= 2^(16 - headroom_bits).  An eager, offline call: nothing of it runs inside
     a product path.  Raises if a tensor is non-finite even at that exponent."""
     k = CALIBRATION_EXPONENT
-    seen = probe_ranges(source, device, RangePlan.uniform(k), latents, images)
+    seen = probe_ranges(source, device, RangePlan.uniform(k), latents, images, attention=attention)
     bad = [f"{s.name} ({n})" for s, (_, n) in seen.items() if n]
     if bad:
         raise RuntimeError(f"non-finite values at exponent {k}, no power-of-two range plan holds this VAE on these inputs: "
