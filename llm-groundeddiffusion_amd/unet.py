@@ -69,7 +69,9 @@ class Op:
     def __init__(self, fwd, make_bwd=None, gouts=(), passthrough=None, meta=None):
         self.fwd = fwd
         # plain-data description of the op (kind, input / output Acts with their views, side outputs, scratch, parameter
-        # names of the state dict, geometry, the inputs that are constants of a run).  Written when the plan is built and
+        # names of the state dict, geometry, the inputs that are constants of a run, and `pair`: the op's PairMode inside the
+        # shared prefix of a CFG pair plan, or None — a LayerNorm whose PairMode was turned to DUP runs in full, and the
+        # statistics pass of an ln_linear in pair mode is always HALF).  Written when the plan is built and
         # read by tests only (tests/unet_plan_cases.py): no launch closure looks at it
         self.meta = meta
         self.make_bwd = make_bwd    # (acc flags for gouts) -> callable
@@ -190,11 +192,11 @@ class Plan:
         d = ops.gemm_desc(x.t, W, y.t, M, N, K, lda0=x.C, bias=b, res=res.t if res else None,
                           ldr=res.C if res else 0, alpha=alpha, epi=EPI_GEGLU if geglu else 0,
                           ldc=y.C)
-        self._pair_op([x, res], y, half, d)
+        pm = self._pair_op([x, res], y, half, d)
         # q/k/v/out projections count towards the "attention path" of the benchmark's roofline report
         tag = "attn_path" if any(t in name for t in (".attn1.", ".attn2.", ".fuser.attn.")) else None
         fwd = lambda: ops.gemm_launch(d, tag)
-        meta = dict(kind="linear", name=name, ins=[x], res=res, out=y, rows=M, desc=d, alpha=alpha, geglu_epilogue=geglu,
+        meta = dict(kind="linear", name=name, ins=[x], res=res, out=y, rows=M, desc=d, alpha=alpha, geglu_epilogue=geglu, pair=pm,
                     params=dict(weight=self._sd_names(name), bias=f"{name}.bias" if bias else None,
                                 geglu_rows=name.endswith(".net.0.proj"),
                                 alpha=self._gate_name(name)))
@@ -236,6 +238,7 @@ class Plan:
         M = B * Ho * Ho
         y = self._act(M, Cout)
         eng = self.eng
+        pm = None
         if temb_off is not None and eng.temb_rows > 1:
             # text_time conditioning (SDXL): the time embedding differs per image (pooled text + size / score ids), the
             # GEMM epilogue takes ONE bias2 vector per launch -> one launch per image (1024^2 refiner: 16384 rows each)
@@ -254,10 +257,10 @@ class Plan:
                               lda1=c1, taps=9, hin=H, win=H, hout=Ho, wout=Ho, stride=stride,
                               ups=1 if ups else 0, bias=b, bias2=bias2, res=res.t if res else None,
                               ldr=res.C if res else 0, ldc=Cout)
-            self._pair_op([x, x1, res], y, half, d)
+            pm = self._pair_op([x, x1, res], y, half, d)
             fwd = lambda: ops.gemm_launch(d)
         meta = dict(kind="conv", name=name, ins=[x] + ([x1] if x1 else []), res=res, out=y, H=H, stride=stride, ups=bool(ups),
-                    temb_off=temb_off, scratch=[], params=dict(weight=[f"{name}.weight"], bias=f"{name}.bias"),
+                    temb_off=temb_off, scratch=[], pair=pm, params=dict(weight=[f"{name}.weight"], bias=f"{name}.bias"),
                     const=["temb"] if temb_off is not None else [])
         if not self.grad:
             self._add(fwd, meta=meta)
@@ -346,7 +349,7 @@ class Plan:
         else:
             fwd = lambda: ops.groupnorm(x.t, B, HW, G, eps, gm, bt, silu, x1=xt1, out=y.t, part=part, stats=stats)
         meta = dict(kind="groupnorm", name=name, ins=[x] + ([x1] if x1 else []), out=y, HW=HW, G=G, eps=eps, silu=silu,
-                    side=dict(part=part, stats=stats), scratch=[part],
+                    side=dict(part=part, stats=stats), scratch=[part], pair=pm,
                     params=dict(weight=f"{name}.weight", bias=f"{name}.bias"))
         if not self.grad:
             self._add(fwd, meta=meta)
@@ -381,7 +384,7 @@ class Plan:
         fwd = lambda: ops.layernorm(x.t, gm, bt, out=y.t, ldy=ldy or C, stats=stats, rows=x.rows,
                                     rows_per_batch=rpb, x_bs=x_bs, y_bs=y_bs, pair=PAIR_HALF if y.pair is not None else 0)
         meta = dict(kind="layernorm", name=name, ins=[x], out=y, rows=x.rows, ldy=ldy or C, rows_per_batch=rpb, x_bs=x_bs,
-                    y_bs=y_bs, S=S, eps=1e-5, side=dict(stats=stats), params=dict(weight=f"{name}.weight", bias=f"{name}.bias"),
+                    y_bs=y_bs, S=S, eps=1e-5, side=dict(stats=stats), pair=pm, params=dict(weight=f"{name}.weight", bias=f"{name}.bias"),
                     const=["grounding_rows"] if out_t is not None else [])
         if not self.grad:
             self._add(fwd, meta=meta)
@@ -417,10 +420,11 @@ class Plan:
         tag = "attn_path" if any(t in name for t in (".attn1.", ".attn2.", ".fuser.attn.")) else None
         xt = x.t
         # the statistics are read by this GEMM only: in pair mode it reads those of the first M / 2 rows
-        sp = PAIR_HALF if self._pair_op([x], y, half, d) is not None else 0
+        pm = self._pair_op([x], y, half, d)
+        sp = PAIR_HALF if pm is not None else 0
         self._add(lambda: (ops.layernorm_stats(xt, K, stats=stats, rows=M, pair=sp), ops.gemm_launch(d, tag)),
                   meta=dict(kind="ln_linear", name=name, norm=norm, ins=[x], out=y, rows=M, desc=d, geglu_epilogue=geglu,
-                            side=dict(stats=stats), params=dict(weight=self._sd_names(name), bias=f"{name}.bias" if has_b else None,
+                            side=dict(stats=stats), pair=pm, params=dict(weight=self._sd_names(name), bias=f"{name}.bias" if has_b else None,
                                                                 norm_weight=f"{norm}.weight", norm_bias=f"{norm}.bias",
                                                                 geglu_rows=name.endswith(".net.0.proj"))))
         return y
@@ -442,7 +446,7 @@ class Plan:
         fwd = lambda: ops.attn_fwd(qt, kt, vt, o.t, B, heads, S, Sk, d, scale, lse=lse,
                                    q_view=view, k_view=view, v_view=view, pair=pm.mode if pm is not None else 0)
         meta = dict(kind="self_attn", ins=[qkv], out=o, heads=heads, S=S, Sk=Sk, d=d, scale=scale, view=view,
-                    side=dict(lse=lse), scratch=[], sk_grad=S, const=["grounding_rows"] if Sk > S else [])
+                    side=dict(lse=lse), scratch=[], sk_grad=S, pair=pm, const=["grounding_rows"] if Sk > S else [])
         if not self.grad:
             self._add(fwd, meta=meta)
             return o
@@ -607,14 +611,15 @@ class Plan:
                              wout=L, bias=w.f["conv_in.b"], ldc=c0, splits=1)
         f_in = 2.0 * B * L * L * c0 * 9 * cfg.in_channels                   # algorithmic: the filter has 9 x 4 taps, not 72
         self._pair = self.pair_shared
-        if self._pair_op([], None, False, d_in) is not None:
+        pm_in = self._pair_op([], None, False, d_in)
+        if pm_in is not None:
             # the second half of latents_in is never read: the caller need not fill it (LMDSampler._main_pass)
             self.latents_pair = True
             lat = lat[:B // 2]
             f_in *= 0.5
         lat8_in = lat8[:lat.shape[0] * L * L]              # the rows the converter writes: the first half under the pair
         self._add(lambda: (ops.nchw_to_nhwc8(lat, out=lat8_in), ops.gemm_launch(d_in, None, f_in)),
-                  meta=dict(kind="conv_in", ins=[lat], out=x0, H=L, scratch=[lat8_in], desc=d_in,
+                  meta=dict(kind="conv_in", ins=[lat], out=x0, H=L, scratch=[lat8_in], desc=d_in, pair=pm_in,
                             params=dict(weight=["conv_in.weight"], bias="conv_in.bias")))
         skips = [(x, L)]
         H = L
