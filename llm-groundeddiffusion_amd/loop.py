@@ -124,6 +124,16 @@ def clamp_steps(first_step, n_steps, total):
     return first, total if n_steps is None else min(total, first + int(n_steps))
 
 
+def history_of(hist, rows, first, last):
+    """The history a call returns: rows first .. last of the state's `hist` (the start it ran from and the steps it ran),
+    every other row of hist[:rows] zero.  The state keeps whatever earlier calls wrote in those rows; a call never returns it."""
+    if first == 0 and last == rows - 1:
+        return hist[:rows].clone()
+    out = torch.zeros_like(hist[:rows])
+    out[first:last + 1].copy_(hist[first:last + 1])
+    return out
+
+
 def run_steps(eng, first, last, body):
     for index in range(first, last):
         GATE.checkpoint()                    # lanes.py: a safe point per step, another lane may be waiting to capture

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .loop import LoopState, clamp_steps, run_steps
+from .loop import LoopState, clamp_steps, history_of, run_steps
 from .scheduler import DDIMScheduler
 
 F32 = torch.float32
@@ -283,7 +283,8 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
     first_step / n_steps: run only those steps, from `start_latent` as the state before step first_step; the frozen
     bootstrapping noise is then `noise` (by default the start latent, as in the reference).
     Returns dict(latent (1,C,L,L), image uint8 (H,W,3) truncated like ToPILImage or None, latents_all (T+1,1,C,L,L)
-    with save_all_latents, inputs: per step run the (P,C,L,L) UNet input rows with record_inputs).
+    with save_all_latents (rows first_step .. the last step run are this call's, every other row zero: loop.history_of),
+    inputs: per step run the (P,C,L,L) UNet input rows with record_inputs).
 
     A start latent (1, C, Hp, Wp) other than 64 x 64 (with masks (P, 1, Hp, Wp)), indep_uncond=False (prompt 0's
     unconditional prediction for every prompt of a view) or normalization=True (value / count over the overlaps) take
@@ -359,7 +360,7 @@ def multidiffusion_generate(sampler, texts, masks, start_latent, bg_latents, pic
     lat = st.lat.reshape(1, C, L, L).clone()
     image = decode_truncating(sampler.vae, lat)[0] if decode else None
     return dict(latent=lat, image=image, inputs=inputs,
-                latents_all=st.hist[:T + 1].clone().unsqueeze(1) if save_all_latents else None)
+                latents_all=history_of(st.hist, T + 1, first_step, last_step).unsqueeze(1) if save_all_latents else None)
 
 
 @torch.no_grad()
@@ -461,7 +462,7 @@ def _generate_views(sampler, texts, masks, start_latent, bg_latents, picks, step
     lat = st.lat.reshape(1, C, Hp, Wp).clone()
     image = decode_truncating(sampler.vae, lat)[0] if decode else None
     return dict(latent=lat, image=image, inputs=inputs, views=views,
-                latents_all=st.hist[:T + 1].clone().unsqueeze(1) if save_all_latents else None)
+                latents_all=history_of(st.hist, T + 1, first_step, last_step).unsqueeze(1) if save_all_latents else None)
 
 
 @torch.no_grad()

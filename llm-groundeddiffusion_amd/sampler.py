@@ -21,7 +21,7 @@ import torch
 from . import ops
 from .energy import BoxDiffTables, EnergyTables
 from .lanes import GATE
-from .loop import HipGraph, LoopState, StateCache, clamp_steps, run_steps  # noqa: F401 (HipGraph: importable from here)
+from .loop import HipGraph, LoopState, StateCache, clamp_steps, history_of, run_steps  # noqa: F401 (HipGraph: importable from here)
 from .scheduler import C_IN_GCOL, LMS, MULTISTEP, PLMS, DDIMScheduler
 from .unet import N_OBJ_TOKENS, UNetEngine
 
@@ -437,6 +437,9 @@ class LMDSampler:
           under LMS (its ring of derivatives); Euler's rows carry no state, so partial schedules run.
         Returns per job dict(latents (1,C,L,L), latents_all (T_run+1,1,C,L,L), saved {key: [T_run,Bp,H,HW,Tp]},
         guidance_iters).
+        Rows a call does not write: latents_all keeps its T_run + 1 rows under a partial schedule; rows first_step (the start)
+        .. last_step (the last step run) are this call's and every other row is ZERO (loop.history_of) — never what an
+        earlier call on the same state left there.
         """
         eng, dev = self.eng, self.dev
         sch = self.scheduler if scheduler is None else scheduler
@@ -489,7 +492,7 @@ class LMDSampler:
                     m = maps[k][nb + b:nb + b + 1] if return_cond_ca_only else maps[k][[b, nb + b]]
                     saved[b][k][index].copy_(m[..., int(j.token):int(j.token) + 1] if j.token is not None else m)
         run_steps(eng, first_step, last_step, one_step)
-        hist = st.hist[:Tr + 1].clone() if save_all_latents else None
+        hist = history_of(st.hist, Tr + 1, first_step, last_step) if save_all_latents else None
         return [dict(latents=st.lat[b:b + 1].clone(), latents_all=hist[:, b:b + 1] if hist is not None else None,
                      saved=saved[b], guidance_iters=gstates[b].iterations if gstates[b] is not None else 0,
                      guidance_iters_fuser_on=gstates[b].iterations_fuser_on if gstates[b] is not None else 0)
@@ -600,6 +603,9 @@ class LMDSampler:
         st.hist[first_step].copy_(st.lat)
         st.mask.zero_()
         if frozen_steps > 0:
+            # step i < frozen_steps blends row i + 1 of EVERY image in, weighted by its mask (0 * NaN is NaN): the rows
+            # that no job of this call loads (no mask, no history, a history that ends early) are zero, not an earlier call's
+            st.frozen_ref[1:int(frozen_steps) + 1].zero_()
             for b, j in enumerate(jobs):
                 if j.frozen_mask is not None and j.latents.dim() == 5:
                     rows = min(j.latents.shape[0], st.frozen_ref.shape[0])   # a fast-schedule history is shorter
