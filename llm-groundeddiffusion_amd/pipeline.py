@@ -308,7 +308,9 @@ def lmd_plus_generate_batch(sampler: LMDSampler, lays: List[CachedLayout], *, nu
     the energy's default weights, lmd_plus.py:320-328) for a batch of independent layouts: the per-box generations of ALL layouts run
     as one batched denoising call (B = 2 x total boxes), then the overall generations of all layouts as
     another (B = 2 x layouts; guidance pass B = layouts with a per-image loop exit).  Results per layout
-    are independent of how layouts are batched (images only share kernel launches).
+    are independent of how layouts are batched only up to the arithmetic of the launches they share (the GEMM tiles
+    follow the batch, and the guided loop amplifies the difference); lgd_amd.runset's batching="layout" gives every
+    layout its own call, and with it bit-identical results however a set is split.
     overall_first_step / overall_n_steps / overall_start (one latent tensor per layout): run only those steps of the
     overall generation, from the given state — the teacher-forcing hook of the parity tests.
     handoff: where alignment, composition and the reference-map gather between the two stages run — "host" (hostprep, box
